@@ -5,15 +5,20 @@ One "step" = one network evaluation of the TV2V hot path on the CFG-doubled batc
 (OpenAIWrapperControlLDM3DTV2V.forward: hint remap -> ControlNet2D on 34 frames -> pseudo-3D UNet ->
 eps), B=2 (uncond+cond), T=17 keyframes, latent 64x96, context 77x768, hint 3x512x768 per frame —
 77.68 TFLOP algorithmic.  The DPMPP2SAncestral sampler calls exactly this 59 times per
-30-step clip; after the timed steps one whole clip (sampler loop + AutoencoderKL decode) is timed as well and
-its frames/s are added to the JSON line (`clip`; `--no-clip` skips it).
+30-step clip.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run builds the model, runs W warm-up steps, times K steps and prints the line.  `--dump-outputs DIR` writes the eps of the
+last timed step (rank 0) as DIR/eps.npy in float32.  `--full` adds everything else, each part measured after the timed steps:
+the HIP-event profiled step behind `roofline` (`--no-profile-step` skips it), one whole clip — sampler loop + AutoencoderKL decode,
+frames/s as `clip` (`--no-clip`) —, the CPU oracle baseline (`--no-cpu-baseline`), the config-3 (TVI2V) step next to the single-GPU
+line (`--no-tvi2v`) and the config-4 objects of the multi-GPU lines (`--no-c4`).
 
 Multi-GPU: `--gpus N` without a launcher environment (WORLD_SIZE unset) re-executes itself under torch.distributed.run with N ranks
 on 127.0.0.1, one per GPU.  `value` at N > 1 is BASELINE.json config 5 — N independent clips, one per GPU ("replicas only", no
-data-path collective; barrier on both sides, MAX time over ranks), `scaling: "weak"`.  The same line carries a `c4` object: config 4,
+data-path collective; barrier on both sides, MAX time over ranks), `scaling: "weak"`.  With `--full` the line carries a `c4` object: config 4,
 ONE clip whose latent rows are sharded over the N ranks (parallel.RowShard: halo rows, all-reduced GroupNorm sums, head-parallel
 spatial attention through all-to-alls; `--shard-mode` selects another decomposition) — strong-scaling ms/step,
 `efficiency_per_gpu` against the single-GPU step measured in the same run, exchanges and bytes per step.  That section runs in CHILD
@@ -257,7 +262,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--clip", action="store_true", help="(default on) time one full 30-step clip + VAE decode (frames/s)")
+    ap.add_argument("--clip", action="store_true", help="(default on with --full) time one full 30-step clip + VAE decode (frames/s)")
     ap.add_argument("--no-clip", action="store_true", help="skip the whole-clip timing (30-step sampler + VAE decode, ~7 s)")
     ap.add_argument("--json-out", type=str, default="", help="also write the JSON line to this file (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -285,7 +290,18 @@ def main():
                     help="row-sharded spatial attention: all-to-all by head (heads) or all-gather of K/V (gather)")
     ap.add_argument("--dump-shapes", type=str, default="", help="write the GEMM launch shape sequence of one step (json)")
     ap.add_argument("--breakdown", action="store_true", help="print per-shape GEMM / attention time of one step to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled step, the clip, the CPU baseline, the config-3 step and config 4 "
+                         "(each can be skipped with its --no-* option); off: only the headline step timing")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the eps of the last timed step (rank 0) to DIR/eps.npy, float32")
     args = ap.parse_args()
+    if not args.full:
+        for flag in ("breakdown", "cpu_full_step", "dump_shapes"):
+            if getattr(args, flag):
+                ap.error(f"--{flag.replace('_', '-')} belongs to a section that only runs with --full")
+        # a plain run is the headline step timing alone: every section after it is off
+        args.no_profile_step = args.no_clip = args.no_cpu_baseline = args.no_tvi2v = args.no_c4 = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started like the single-GPU run (`python bench.py --gpus N`): become the launcher — one rank per GPU over RCCL on 127.0.0.1
@@ -385,6 +401,11 @@ def main():
     assert torch.isfinite(out).all()
     ms_per_step = dt / args.steps * 1e3
     value = (1 if shard else world) * args.steps / dt
+    if rank == 0 and args.dump_outputs:
+        # (copied out now: a replayed graph writes every step into the same output buffer)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "eps.npy"), out.float().cpu().numpy())
 
     # ---- config 4 (ONE clip sharded over the ranks): one instrumented step (bytes, exchange count, device time inside exchanges) and
     # the single-GPU time the per-GPU efficiency is quoted against.  Headline mode (--shard-frames): the unsharded step is timed on
@@ -392,7 +413,7 @@ def main():
     # here, on the same clip on all ranks, and reported as the `c4` object next to the replica `value`. ----
     roof = None
     extra = {}
-    if shard:
+    if shard and args.full:
         info = shard_counters(shards, step, world, dist, wrapper)
         keep, wrapper.frame_shard = wrapper.frame_shard, None
         keep_rows, wrapper.row_shard = wrapper.row_shard, None

@@ -201,11 +201,8 @@ def test_synth_weights_are_name_keyed_and_stable():
 
 
 # ------------------------------------------------------------------------------------------------------
-# the reference's shipped inference yamls, verbatim
+# the reference's shipped inference yamls
 # ------------------------------------------------------------------------------------------------------
-REF_CFG_DIR = "/root/reference/configs/inference_ccedit"
-
-
 def _engine_keys(cfg):
     from ccedit_amd.config import instantiate_from_config
     with torch.device("meta"):
@@ -213,14 +210,35 @@ def _engine_keys(cfg):
     return engine, {k: list(v.shape) for k, v in engine.state_dict().items()}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG_DIR), reason="the reference checkout is not on this machine")
+def _shipped_model_section(name):
+    """The `model:` section of one of the reference's two shipped inference yamls: engine_config() plus the training-time keys
+    the shipped files carry on top of it (CLIP legacy_ucg_value "" and freeze, the hint embedder's ucg_rate; the TVI2V file
+    also use_checkpoint: True in all three networks and a scheduler_config)."""
+    from ccedit_amd.sgm_compat import engine_config
+    tvi2v = name == "keyframe_ref_cp_no2ndca_add_cfca_depthzoe.yaml"
+    m = engine_config(crossframe=tvi2v)
+    emb = m["params"]["conditioner_config"]["params"]["emb_models"]
+    emb[0].update(legacy_ucg_value="", params=dict(freeze=True))
+    emb[1]["ucg_rate"] = 0.0 if tvi2v else 0.01
+    if tvi2v:
+        net = m["params"]["network_config"]["params"]
+        for p in (net, net["controlnet_config"]["params"], net["controlnet_img_config"]["params"]):
+            p["use_checkpoint"] = True
+        m["params"]["scheduler_config"] = dict(target="sgm.lr_scheduler.LambdaLinearScheduler", params=dict(
+            warm_up_steps=[1000], cycle_lengths=[10000000000000], f_start=[1.e-6], f_max=[1.], f_min=[1.]))
+    return m
+
+
 @pytest.mark.parametrize("name,keys,nparams", [("keyframe_no2ndca_depthmidas.yaml", "keys_tv2v.json", 1608747976),
                                                ("keyframe_ref_cp_no2ndca_add_cfca_depthzoe.yaml", "keys_tvi2v.json", 2171449416)])
-def test_shipped_reference_yaml_instantiates_unchanged(golden_dir, name, keys, nparams):
+def test_shipped_reference_yaml_instantiates_unchanged(tmp_path, golden_dir, name, keys, nparams):
     """the two shipped inference configs load UNCHANGED (legacy_ucg_value: "",
     scheduler_config, use_checkpoint: True, ...) and give the reference's network state-dict names and shapes."""
+    import yaml
     from ccedit_amd.config import load_config
-    cfg = load_config(os.path.join(REF_CFG_DIR, name))
+    p = tmp_path / name
+    p.write_text(yaml.safe_dump(dict(model=_shipped_model_section(name)), sort_keys=False))
+    cfg = load_config(str(p))
     engine, mine = _engine_keys(cfg)
     with open(os.path.join(golden_dir, keys)) as f:
         ref = {k: v for k, v in json.load(f).items() if k.startswith("model.")}
