@@ -142,3 +142,14 @@ static inline int cc_launch_status(const char* what) {
     }
     return CCEDIT_OK;
 }
+
+// Pixel I/O launchers (pixel.hip); the exported entry points with their argument checks are in core.cpp
+int cc_pixel_resize_u8(const uint8_t* src, void* dst, uint8_t* tmp, const int32_t* ytab, int32_t yk, const int32_t* xtab, int32_t xk,
+                       int32_t N, int32_t Hs, int32_t Ws, int32_t H, int32_t W, int32_t out_f32, hipStream_t s);
+int cc_pixel_resize_f32(const float* src, float* dst, const int32_t* ytab, const int32_t* xtab, int64_t planes, int32_t Hs, int32_t Ws,
+                        int32_t H, int32_t W, hipStream_t s);
+int cc_pixel_kth_values(const float* x, int32_t B, int64_t n, const int64_t* ranks, int32_t nr, float* out, void* workspace, hipStream_t s);
+int cc_pixel_minmax(const float* x, int32_t B, int64_t n, float* out, hipStream_t s);
+int cc_pixel_depth_hint(const float* depth, float* hint, const float* stats, int32_t stat_stride, int32_t B, int64_t n, int32_t flip,
+                        hipStream_t s);
+int cc_pixel_frames_to_u8(const float* x, uint8_t* out, int32_t B, int64_t P, int32_t mode, int32_t unit_range, hipStream_t s);

@@ -100,3 +100,60 @@ extern "C" const char* ccedit_policy_names(void) {
     }
     return buf;
 }
+
+// ---- pixel I/O (kernels and launchers: pixel.hip).  Everything is checked here, before any HIP call.
+static const int64_t kPixelMax = (int64_t)1 << 31;      // element counts the 32-bit tap arithmetic and the rank counters are sized for
+
+extern "C" int ccedit_resize_u8_pil(const void* src, void* dst, void* tmp, const int32_t* ytab, int32_t yk, const int32_t* xtab, int32_t xk,
+                                    int32_t N, int32_t Hs, int32_t Ws, int32_t H, int32_t W, int32_t out_f32, void* stream) {
+    CC_CHECK_ARG(src && dst && ytab, "ccedit_resize_u8_pil: null pointer (src, dst and ytab are required)");
+    CC_CHECK_ARG(N > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "ccedit_resize_u8_pil: sizes must be positive (N=%d, %dx%d -> %dx%d)", N, Hs, Ws, H, W);
+    CC_CHECK_ARG(yk >= 1 && yk <= 4096 && (!xtab || (xk >= 1 && xk <= 4096)), "ccedit_resize_u8_pil: tap counts yk=%d xk=%d (1 ... 4096)", yk, xk);
+    CC_CHECK_ARG(xtab || Ws == W, "ccedit_resize_u8_pil: xtab may only be null when the width does not change (%d -> %d)", Ws, W);
+    CC_CHECK_ARG(!xtab || tmp, "ccedit_resize_u8_pil: the horizontal pass needs tmp (N x Hs x W x 3 bytes)");
+    CC_CHECK_ARG((int64_t)N * Hs * (Ws > W ? Ws : W) * 3 < kPixelMax && (int64_t)N * H * W * 3 < kPixelMax,
+                 "ccedit_resize_u8_pil: more than 2^31 bytes in one call (N=%d, %dx%d -> %dx%d)", N, Hs, Ws, H, W);
+    return cc_pixel_resize_u8((const uint8_t*)src, dst, (uint8_t*)tmp, ytab, yk, xtab, xk, N, Hs, Ws, H, W, out_f32, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_resize_f32_bicubic(const float* src, float* dst, const int32_t* ytab, const int32_t* xtab, int64_t planes, int32_t Hs,
+                                         int32_t Ws, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(src && dst && ytab && xtab, "ccedit_resize_f32_bicubic: null pointer");
+    CC_CHECK_ARG(planes > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "ccedit_resize_f32_bicubic: sizes must be positive (planes=%lld, %dx%d -> %dx%d)",
+                 (long long)planes, Hs, Ws, H, W);
+    CC_CHECK_ARG(planes < kPixelMax && planes * Hs * Ws < kPixelMax * 4 && planes * H * W < kPixelMax * 4,
+                 "ccedit_resize_f32_bicubic: more than 2^33 elements in one call");
+    return cc_pixel_resize_f32(src, dst, ytab, xtab, planes, Hs, Ws, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_kth_values(const float* x, int32_t B, int64_t n, const int64_t* ranks, int32_t n_ranks, float* out, void* workspace,
+                                 void* stream) {
+    CC_CHECK_ARG(x && ranks && out && workspace, "ccedit_kth_values: null pointer");
+    CC_CHECK_ARG(B > 0 && B <= 65535 && n > 0 && n < kPixelMax, "ccedit_kth_values: B=%d (1 ... 65535), n=%lld (1 ... 2^31 - 1)", B, (long long)n);
+    CC_CHECK_ARG(n_ranks >= 1 && n_ranks <= 4, "ccedit_kth_values: n_ranks=%d (1 ... 4)", n_ranks);
+    for (int r = 0; r < n_ranks; ++r)
+        CC_CHECK_ARG(ranks[r] >= 1 && ranks[r] <= n, "ccedit_kth_values: rank %lld outside 1 ... n=%lld (1-based, as torch.kthvalue)",
+                     (long long)ranks[r], (long long)n);
+    return cc_pixel_kth_values(x, B, n, ranks, n_ranks, out, workspace, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_minmax_f32(const float* x, int32_t B, int64_t n, float* out, void* stream) {
+    CC_CHECK_ARG(x && out, "ccedit_minmax_f32: null pointer");
+    CC_CHECK_ARG(B > 0 && B <= 65535 && n > 0, "ccedit_minmax_f32: B=%d (1 ... 65535), n=%lld (> 0)", B, (long long)n);
+    return cc_pixel_minmax(x, B, n, out, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_depth_hint(const float* depth, float* hint, const float* stats, int32_t stat_stride, int32_t B, int64_t n, int32_t flip,
+                                 void* stream) {
+    CC_CHECK_ARG(depth && hint && stats, "ccedit_depth_hint: null pointer");
+    CC_CHECK_ARG(B > 0 && B <= 65535 && n > 0, "ccedit_depth_hint: B=%d (1 ... 65535), n=%lld (> 0)", B, (long long)n);
+    CC_CHECK_ARG(stat_stride == 0 || stat_stride >= 2, "ccedit_depth_hint: stat_stride=%d (0: one (lo, hi) pair for all clips, else >= 2)", stat_stride);
+    return cc_pixel_depth_hint(depth, hint, stats, stat_stride, B, n, flip, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_frames_to_u8(const float* x, void* out, int32_t B, int64_t P, int32_t mode, int32_t unit_range, void* stream) {
+    CC_CHECK_ARG(x && out, "ccedit_frames_to_u8: null pointer");
+    CC_CHECK_ARG(B > 0 && B <= 65535 && P > 0, "ccedit_frames_to_u8: B=%d (1 ... 65535), P=%lld (> 0)", B, (long long)P);
+    CC_CHECK_ARG(mode == 0 || mode == 1, "ccedit_frames_to_u8: mode=%d (0: truncate 255 v, 1: truncate 255 v + 0.5)", mode);
+    return cc_pixel_frames_to_u8(x, (uint8_t*)out, B, P, mode, unit_range, (hipStream_t)stream);
+}

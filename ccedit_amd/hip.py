@@ -132,7 +132,17 @@ _SIGS = {
     "ccedit_mask_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ccedit_cfg_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]),
     "ccedit_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]),
+    # pixel I/O (csrc/pixel.hip): added within ABI 12, nothing existing changed
+    "ccedit_resize_u8_pil": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_resize_f32_bicubic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_void_p]),
+    "ccedit_kth_values": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ccedit_minmax_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ccedit_depth_hint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "ccedit_frames_to_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
 }
+KTH_WORKSPACE_BYTES_PER_ROW = 4128      # ccedit_kth_values: (prefix, rank) x 4 + 4 x 256 counters, uint32
 
 EXPORTS = tuple(_SIGS)
 

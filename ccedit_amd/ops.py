@@ -744,3 +744,93 @@ def softmax_rows(s: torch.Tensor, cols: int, cols_pad: int, scale: float) -> tor
     hip.check(hip.lib().ccedit_softmax_rows(s.data_ptr(), p.data_ptr(), s.shape[0], cols, cols_pad, s.stride(0), cols_pad,
                                             scale, _stream()), "ccedit_softmax_rows")
     return p
+
+
+# ------------------------------------------------------------------------------------------
+# Pixel I/O (csrc/pixel.hip): uint8 frames <-> the engine's fp32 tensors
+# ------------------------------------------------------------------------------------------
+_TAPS = {}
+
+
+def _taps(kind: str, in_size: int, out_size: int, device) -> torch.Tensor:
+    """Device copy of one axis' tap table (packing.pil_bicubic_taps / aten_bicubic_taps), built once per size and device."""
+    from . import packing
+    key = (kind, in_size, out_size, str(device))
+    if key not in _TAPS:
+        build = packing.pil_bicubic_taps if kind == "pil" else packing.aten_bicubic_taps
+        _TAPS[key] = torch.from_numpy(build(in_size, out_size)).to(device)
+    return _TAPS[key]
+
+
+def resize_u8_pil(frames: torch.Tensor, size, to_float: bool = False) -> torch.Tensor:
+    """Pillow's `Image.resize((W, H), BICUBIC)` of uint8 frames (N, Hs, Ws, 3) on the device, bit for bit.
+    -> uint8 (N, H, W, 3), or with `to_float` fp32 (3, N, H, W) = x / 255 * 2 - 1 (a clip's (1, 3, T, H, W) after [None])."""
+    assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous() and frames.dim() == 4 and frames.shape[3] == 3
+    n, hs, ws, _ = frames.shape
+    h, w = int(size[0]), int(size[1])
+    ytab = _taps("pil", hs, h, frames.device)
+    xtab = _taps("pil", ws, w, frames.device) if ws != w else None        # Pillow skips the pass of an unchanged axis
+    tmp = torch.empty((n, hs, w, 3), dtype=torch.uint8, device=frames.device) if xtab is not None else None
+    out = (torch.empty((3, n, h, w), dtype=torch.float32, device=frames.device) if to_float
+           else torch.empty((n, h, w, 3), dtype=torch.uint8, device=frames.device))
+    hip.check(hip.lib().ccedit_resize_u8_pil(
+        frames.data_ptr(), out.data_ptr(), None if tmp is None else tmp.data_ptr(), ytab.data_ptr(), ytab.shape[1] - 2,
+        None if xtab is None else xtab.data_ptr(), 0 if xtab is None else xtab.shape[1] - 2, n, hs, ws, h, w, int(to_float),
+        _stream()), "ccedit_resize_u8_pil")
+    return out
+
+
+def resize_bicubic(x: torch.Tensor, size) -> torch.Tensor:
+    """`F.interpolate(x, size, mode="bicubic", align_corners=False)` of fp32 (N, C, Hs, Ws) on the device."""
+    assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 4
+    n, c, hs, ws = x.shape
+    h, w = int(size[0]), int(size[1])
+    ytab, xtab = _taps("aten", hs, h, x.device), _taps("aten", ws, w, x.device)
+    out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    hip.check(hip.lib().ccedit_resize_f32_bicubic(x.data_ptr(), out.data_ptr(), ytab.data_ptr(), xtab.data_ptr(), n * c, hs, ws, h, w,
+                                                  _stream()), "ccedit_resize_f32_bicubic")
+    return out
+
+
+def kth_values(x: torch.Tensor, ranks) -> torch.Tensor:
+    """x fp32 (B, n), finite; ranks: up to four 1-based ranks (as torch.kthvalue) -> fp32 (B, len(ranks)) on the device, exact."""
+    assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 2
+    ranks = [int(k) for k in ranks]
+    b, n = x.shape
+    out = torch.empty((b, len(ranks)), dtype=torch.float32, device=x.device)
+    ws = torch.empty(b * hip.KTH_WORKSPACE_BYTES_PER_ROW // 4, dtype=torch.int32, device=x.device)
+    hip.check(hip.lib().ccedit_kth_values(x.data_ptr(), b, n, (C.c_int64 * len(ranks))(*ranks), len(ranks), out.data_ptr(), ws.data_ptr(),
+                                          _stream()), "ccedit_kth_values")
+    return out
+
+
+def minmax(x: torch.Tensor) -> torch.Tensor:
+    """x fp32 (B, n), finite -> fp32 (B, 2) = (min, max) per row, on the device."""
+    assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 2
+    out = torch.empty((x.shape[0], 2), dtype=torch.float32, device=x.device)
+    hip.check(hip.lib().ccedit_minmax_f32(x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), _stream()), "ccedit_minmax_f32")
+    return out
+
+
+def depth_hint(depth: torch.Tensor, stats: torch.Tensor, flip: bool) -> torch.Tensor:
+    """depth fp32 (B, 1, T, H, W); stats fp32 (B, 2) or (1, 2) = (lo, hi) on the device -> (B, 3, T, H, W):
+    clamp((d - lo) / (hi - lo), 0, 1) * 2 - 1, negated with `flip`.  Nothing is read back to the host."""
+    assert depth.dtype == torch.float32 and depth.is_cuda and depth.is_contiguous() and depth.dim() == 5 and depth.shape[1] == 1
+    assert stats.dtype == torch.float32 and stats.is_cuda and stats.is_contiguous() and stats.dim() == 2 and stats.shape[1] == 2
+    b = depth.shape[0]
+    assert stats.shape[0] in (1, b)
+    out = torch.empty((b, 3) + tuple(depth.shape[2:]), dtype=torch.float32, device=depth.device)
+    hip.check(hip.lib().ccedit_depth_hint(depth.data_ptr(), out.data_ptr(), stats.data_ptr(), 2 if stats.shape[0] == b and b > 1 else 0, b,
+                                          depth[0].numel(), int(flip), _stream()), "ccedit_depth_hint")
+    return out
+
+
+def frames_to_u8(x: torch.Tensor, rounding: bool = False, unit_range: bool = False) -> torch.Tensor:
+    """x fp32 (B, 3, T, H, W) in [-1, 1] (`unit_range`: already in [0, 1]) -> uint8 (B, T, H, W, 3):
+    uint8(255 v) of v = clamp((x + 1) / 2, 0, 1), or uint8(min(255 v + 0.5, 255)) with `rounding`."""
+    assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 5 and x.shape[1] == 3
+    b, _, t, h, w = x.shape
+    out = torch.empty((b, t, h, w, 3), dtype=torch.uint8, device=x.device)
+    hip.check(hip.lib().ccedit_frames_to_u8(x.data_ptr(), out.data_ptr(), b, t * h * w, int(rounding), int(unit_range), _stream()),
+              "ccedit_frames_to_u8")
+    return out

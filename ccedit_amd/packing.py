@@ -300,3 +300,115 @@ def pack_ff320_tail(ff: PackedFF320, wo: torch.Tensor, bo: Optional[torch.Tensor
     extra = 2.0 * FF320_DIM * FF320_DIM * (1 if wp is None else 2)
     return PackedFF320(torch.cat(parts).reshape(-1).to(dev), ff.b2p.to(dev), ff.flops_per_row + extra, bop.to(dev),
                        None if bpp is None else bpp.to(dev), ff)
+
+
+# ------------------------------------------------------------------------------------------
+# Resize tap tables (csrc/pixel.hip).  One int32 table per axis, [out][2 + kmax]: first source index, tap count, then the
+# weights (zero padded to kmax) — fixed point for the 8-bit Pillow resize, fp32 bit patterns for the ATen bicubic.  Built once
+# per (in, out) size on the host, in double / fp32 like the libraries they reproduce; a few KB each.
+# ------------------------------------------------------------------------------------------
+PIL_PRECISION_BITS = 32 - 8 - 2          # Pillow's 8-bit resample: weights are rounded to 22-bit fixed point
+
+
+def _pil_bicubic(x: float) -> float:
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+    if x < 2.0:
+        return (((x - 5.0) * x + 8.0) * x - 4.0) * a
+    return 0.0
+
+
+def pil_bicubic_taps(in_size: int, out_size: int):
+    """The coefficients of Pillow's 8-bit `Image.resize(BICUBIC)` along one axis: Keys cubic a = -0.5 stretched by
+    max(in / out, 1) (antialiased when shrinking), window [int(c - s + 0.5), int(c + s + 0.5)) clipped to the image around the
+    centre c = (i + 0.5) in / out, weights normalised to sum 1 in double, then rounded to 22-bit fixed point away from zero by
+    half (`int(w 2^22 +- 0.5)`).  -> int32 [out_size][2 + kmax] (first, count, weights...)."""
+    import numpy as np
+    assert in_size > 0 and out_size > 0
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ss = 1.0 / filterscale
+    rows = []
+    for i in range(out_size):
+        center = (i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size)
+        w = [_pil_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax - xmin)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        rows.append((xmin, [int(-0.5 + v * (1 << PIL_PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PIL_PRECISION_BITS))
+                            for v in w]))
+    kmax = max(len(w) for _, w in rows)
+    tab = np.zeros((out_size, 2 + kmax), dtype=np.int32)
+    for i, (first, w) in enumerate(rows):
+        tab[i, 0], tab[i, 1] = first, len(w)
+        tab[i, 2:2 + len(w)] = w
+    return tab
+
+
+def aten_bicubic_taps(in_size: int, out_size: int):
+    """The four taps per output coordinate of `F.interpolate(mode="bicubic", align_corners=False)` along one axis: source position
+    (i + 0.5) in / out - 0.5 (fp32 scale, the rest of it rounded once), Keys cubic a = -0.75 at the fractional part in fp32; the taps
+    floor - 1 ... floor + 2 are clamped to the border by the kernel.  -> int32 [out_size][6] (first, 4, four fp32 bit patterns)."""
+    import numpy as np
+    f = np.float32
+    a = f(-0.75)
+    scale = f(in_size) / f(out_size)
+    # one rounding, as the fused multiply-add ATen's CPU kernel evaluates this with (the product is exact in double); rounding the product
+    # first moves the position by up to an ulp of the coordinate — 1.6e-5 in the result at 512 -> 768, beyond the 1e-5 the kernel is held to
+    real = (np.float64(scale) * (np.arange(out_size, dtype=np.float64) + 0.5) - 0.5).astype(np.float32)
+    fl = np.floor(real)
+    t = (real - fl).astype(np.float32)
+
+    def c1(x):
+        return ((a + f(2)) * x - (a + f(3))) * x * x + f(1)
+
+    def c2(x):
+        return ((a * x - f(5) * a) * x + f(8) * a) * x - f(4) * a
+    w = np.stack([c2(t + f(1)), c1(t), c1(f(1) - t), c2(f(2) - t)], axis=1).astype(np.float32)
+    tab = np.empty((out_size, 6), dtype=np.int32)
+    tab[:, 0] = fl.astype(np.int64) - 1
+    tab[:, 1] = 4
+    tab[:, 2:] = w.view(np.int32)
+    return tab
+
+
+def apply_pil_taps_reference(img, ytab, xtab):
+    """Plain integer numpy application of two `pil_bicubic_taps` tables to uint8 (..., Hs, Ws, C): horizontal pass, uint8 in
+    between, vertical pass — what csrc/pixel.hip computes, for the CPU tests (never on the product path)."""
+    import numpy as np
+
+    def one(src, tab, axis):
+        src = np.moveaxis(src, axis, 0).astype(np.int64)
+        out = np.empty((tab.shape[0],) + src.shape[1:], dtype=np.uint8)
+        for i, row in enumerate(tab):
+            first, cnt = int(row[0]), int(row[1])
+            acc = np.tensordot(row[2:2 + cnt].astype(np.int64), src[first:first + cnt], axes=(0, 0)) + (1 << (PIL_PRECISION_BITS - 1))
+            out[i] = np.clip(acc >> PIL_PRECISION_BITS, 0, 255)
+        return np.moveaxis(out, 0, axis)
+    img = np.asarray(img)
+    assert img.dtype == np.uint8 and img.ndim >= 3
+    h_ax, w_ax = img.ndim - 3, img.ndim - 2
+    if xtab.shape[0] != img.shape[w_ax] or not _is_identity(xtab):
+        img = one(img, xtab, w_ax)
+    if ytab.shape[0] != img.shape[h_ax] or not _is_identity(ytab):
+        img = one(img, ytab, h_ax)
+    return img
+
+
+def _is_identity(tab) -> bool:
+    import numpy as np
+    idx = np.arange(tab.shape[0])
+    w = tab[:, 2:]
+    pos = idx - tab[:, 0]
+    ok = (pos >= 0) & (pos < tab[:, 1])
+    if not ok.all():
+        return False
+    one = w[idx, pos] == (1 << PIL_PRECISION_BITS)
+    return bool(one.all() and (np.abs(w).sum(axis=1) == (1 << PIL_PRECISION_BITS)).all())

@@ -417,6 +417,47 @@ int ccedit_cfg_denoise(const float* x, const float* eps2, float* den, int64_t n,
                        void* stream);
 int ccedit_axpby(const float* x, const float* z, float* y, int64_t n, float a, float b, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Pixel I/O (added without an ABI bump: six new functions, no struct or signature changed, CCEDIT_ABI_VERSION stays 12).
+ * The host-side arithmetic of the sampling entry points between decoded uint8 frames and the engine's tensors
+ * (scripts/sampling/util.py: load_img, load_video_keyframes, perform_save_locally_video; sampling_tv2v.py: depth_frames;
+ * encoders/modules.py: DepthMidasEncoder / DepthZoeEncoder normalisation).  Kernels: csrc/pixel.hip; tap tables:
+ * ccedit_amd/packing.py (pil_bicubic_taps, aten_bicubic_taps).  All pointers are device pointers except `ranks`.
+ *
+ * Tap table of one axis: int32 [out][2 + k]: first source index, tap count (<= k), k weights (zero padded).
+ *
+ * ccedit_resize_u8_pil: Pillow's 8-bit Image.resize(BICUBIC), bit for bit.  src uint8 [N][Hs][Ws][3] -> horizontal pass with xtab into
+ *   tmp uint8 [N][Hs][W][3] ((2^21 + sum w p) >> 22 clipped to 0 ... 255, weights 22-bit fixed point) -> vertical pass with ytab.
+ *   out_f32 = 0: dst uint8 [N][H][W][3];  out_f32 = 1: dst fp32 [3][N][H][W] = x / 255 * 2 - 1 (true division), i.e. the
+ *   (1, 3, T, H, W) `keyframes` / (N, 3, H, W) `cond_img` (N = 1) tensor of the engine.  xtab = NULL (then Ws == W; tmp unused)
+ *   skips the horizontal pass, as Pillow does for an unchanged axis.  Windows are held inside the image by the kernel.
+ * ccedit_resize_f32_bicubic: F.interpolate(mode="bicubic", align_corners=False) on fp32 [planes][Hs][Ws] -> [planes][H][W]: tables with
+ *   k = 4 and fp32 bit patterns as weights (a = -0.75), first = floor(src position) - 1, taps clamped to the border;
+ *   out = sum_j wy_j (sum_i wx_i src[y_j][x_i]).  Agrees with ATen to fp32 rounding (<= 1e-5 on inputs in [-1, 1]).
+ * ccedit_kth_values: out[b][r] = the ranks[r]-th smallest (1-based, as torch.kthvalue) of the n values of row b of x fp32 [B][n], for
+ *   up to 4 ranks at once (`ranks` is a HOST array).  Exact (radix select, four 8-bit digits of the order-preserving integer image of the
+ *   float).  workspace: B * 4128 bytes of device scratch, 4-byte aligned, contents irrelevant.  Inputs must be FINITE (NaN has no
+ *   place in the order; -0.0 sorts immediately below +0.0).
+ * ccedit_minmax_f32: out[b] = (min, max) of row b, fp32 [B][2]; same input contract.  The MiDaS hint takes ONE min / max over the
+ *   whole batch of frames (encoders/modules.py:1376-1386): call it with B = 1 over all of them.
+ * ccedit_depth_hint: depth fp32 [B][n] (n = T H W) + (lo, hi) = stats[b * stat_stride + {0, 1}] read from device memory (stat_stride 0:
+ *   one pair for all clips) -> hint fp32 [B][3][n]: v = (d - lo) / (hi - lo) (true division), clamped to [0, 1], v * 2 - 1, negated when
+ *   flip != 0 (MiDaS: near = bright), written to the three channels.  hi == lo gives NaN like the reference (0 / 0); it is not trapped.
+ * ccedit_frames_to_u8: x fp32 [B][3][P] (P = T H W; the decoder's output in [-1, 1], or already in [0, 1] with unit_range != 0) ->
+ *   uint8 [B][P][3]: v = clamp((x + 1) / 2, 0, 1), then mode 0: uint8(255 v) (truncation: the frames of the gif / frame files),
+ *   mode 1: uint8(min(255 v + 0.5, 255)) (the grid PNG).  One rounding per reference operation: bit-identical to the numpy expression.
+ */
+int ccedit_resize_u8_pil(const void* src, void* dst, void* tmp, const int32_t* ytab, int32_t yk, const int32_t* xtab, int32_t xk,
+                         int32_t N, int32_t Hs, int32_t Ws, int32_t H, int32_t W, int32_t out_f32, void* stream);
+int ccedit_resize_f32_bicubic(const float* src, float* dst, const int32_t* ytab, const int32_t* xtab, int64_t planes, int32_t Hs,
+                              int32_t Ws, int32_t H, int32_t W, void* stream);
+int ccedit_kth_values(const float* x, int32_t B, int64_t n, const int64_t* ranks, int32_t n_ranks, float* out, void* workspace,
+                      void* stream);
+int ccedit_minmax_f32(const float* x, int32_t B, int64_t n, float* out, void* stream);
+int ccedit_depth_hint(const float* depth, float* hint, const float* stats, int32_t stat_stride, int32_t B, int64_t n, int32_t flip,
+                      void* stream);
+int ccedit_frames_to_u8(const float* x, void* out, int32_t B, int64_t P, int32_t mode, int32_t unit_range, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,9 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="(not in the reference script) draw the samplers' per-step noise from a CPU generator with this seed instead of "
                         "torch.randn_like on the device: the same clip on any GPU / against the CPU oracle (tests)")
     p.add_argument("--disable_check_repeat", action="store_true")
+    p.add_argument("--gpu_io", action="store_true",
+                   help="pixel I/O on the GPU (ccedit_amd/csrc/pixel.hip): frame / depth resize, depth hint normalisation and the uint8 "
+                        "frames of --save_type gif; decoding and file writing stay on the host.  Default off: everything as before")
 
 
 def build_model(args):
@@ -141,15 +144,20 @@ def conditioning_tensors(args, g: torch.Generator, need_frames: bool, need_ref: 
             cond["cond_img"] = torch.rand(1, 3, args.H, args.W, generator=g) * 2 - 1
     if args.video_path:           # sampling_tv2v.py:314-331: keyframes (T,3,H,W) -> (1,3,T,H,W)
         from scripts.sampling.util import load_video_keyframes
-        kf = load_video_keyframes(args.video_path, args.original_fps, args.target_fps, T, (args.H, args.W))
+        kf = load_video_keyframes(args.video_path, args.original_fps, args.target_fps, T, (args.H, args.W), **_io_device(args))
         cond["keyframes"] = kf.permute(1, 0, 2, 3)[None].contiguous()
     if need_ref and getattr(args, "reference_path", ""):
         from scripts.sampling.util import load_img
-        cond["cond_img"] = load_img(args.reference_path, (args.H, args.W))
+        cond["cond_img"] = load_img(args.reference_path, (args.H, args.W), **_io_device(args))
     for k in (["keyframes"] if need_frames else []) + (["cond_img"] if need_ref else []):
         if k not in cond:
             raise SystemExit(f"--cond_path must hold `{k}` for the requested options")
     return cond
+
+
+def _io_device(args) -> dict:
+    """device= of load_img / load_video_keyframes: the current GPU under --gpu_io, else nothing (the host route, unchanged)."""
+    return {"device": torch.device("cuda", torch.cuda.current_device())} if getattr(args, "gpu_io", False) else {}
 
 
 def text_inputs(cond, dev, args=None):
@@ -167,7 +175,9 @@ def text_inputs(cond, dev, args=None):
 def save_result(args, tag, x):
     """sampling_tv2v.py:473-515: clamp to [0,1]; .npy frames (default) or an animated gif + frame grid."""
     from scripts.sampling.util import perform_save_locally_video, save_frames
-    if args.save_type == "gif":
+    if args.save_type == "gif" and getattr(args, "gpu_io", False):
+        perform_save_locally_video(os.path.join(args.save_path, "result"), x, fps=args.target_fps, savetype="gif", gpu_io=True, signed=True)
+    elif args.save_type == "gif":
         perform_save_locally_video(os.path.join(args.save_path, "result"), torch.clamp((x + 1.0) / 2.0, 0.0, 1.0),
                                    fps=args.target_fps, savetype="gif")
     save_frames(args.save_path, tag, x)
@@ -304,7 +314,8 @@ def depth_frames(args, video_path: str, keyframes: torch.Tensor) -> torch.Tensor
     """Raw depth (1, 1, T, H, W) of the clip's keyframes.  The reference's conditioner runs MiDaS dpt_hybrid / ZoeDepth on the RGB
     keyframes (encoders/modules.py:1289-1392); those networks are not part of this build, their output enters as data:
     --depth_root/<video name>.pt or <video_path>.depth.pt holding the depth of ALL frames (N, h, w) — the keyframe index rule and a
-    bicubic resize are applied here like to the frames — or, with --synthetic, the keyframes' luminance."""
+    bicubic resize are applied here like to the frames (the keyframes are selected first, only they are resized) — or, with
+    --synthetic, the keyframes' luminance.  Under --gpu_io the selected raw depth is uploaded and resized by ccedit_resize_f32_bicubic."""
     from scripts.sampling.util import keyframe_indices
     stem = video_path[:-4] if video_path.endswith((".mp4", ".gif")) else video_path.rstrip("/")
     cands = ([os.path.join(args.depth_root, os.path.basename(stem) + ".pt")] if args.depth_root else []) + [stem + ".depth.pt"]
@@ -315,6 +326,9 @@ def depth_frames(args, video_path: str, keyframes: torch.Tensor) -> torch.Tensor
             if d.dim() != 3:
                 raise ValueError(f"{cpath}: expected raw depth (N, h, w) over all frames, got {tuple(d.shape)}")
             d = d[keyframe_indices(d.shape[0], args.original_fps, args.target_fps, T)]
+            if getattr(args, "gpu_io", False):
+                from ccedit_amd import ops
+                return ops.resize_bicubic(d[:, None].contiguous().to(keyframes.device), (H, W))[:, 0][None, None]
             d = torch.nn.functional.interpolate(d[:, None], size=(H, W), mode="bicubic", align_corners=False)[:, 0]
             return d[None, None]
     if args.synthetic:
@@ -323,6 +337,14 @@ def depth_frames(args, video_path: str, keyframes: torch.Tensor) -> torch.Tensor
     raise NotImplementedError(
         f"no depth for {video_path}: the depth annotators (MiDaS dpt_hybrid / ZoeDepth, encoders/modules.py:1289-1392) are not part of "
         f"this build — provide {cands[-1]} (raw depth (N, h, w) of all frames) or --depth_root")
+
+
+def _hint_embedder(model):
+    """The conditioner's depth embedder (input key `control_hint`): its normalize_gpu is the kernel route of the normalisation."""
+    for emb in model.conditioner.embedders:
+        if getattr(emb, "input_key", None) == "control_hint" and hasattr(emb, "normalize_gpu"):
+            return emb
+    raise NotImplementedError("--gpu_io: the config has no depth embedder on `control_hint`")
 
 
 def job_text(args, prompts, dev, context_dim: int):
@@ -411,7 +433,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
             bs = min(len(cprompts), batch_size)
             print(f"\nProgress: {idx} / {len(prompts_chunk)}. ")
             try:
-                kfs = [load_video_keyframes(resolve_video(v), args.original_fps, args.target_fps, T, (H, W)).permute(1, 0, 2, 3)[None]
+                kfs = [load_video_keyframes(resolve_video(v), args.original_fps, args.target_fps, T, (H, W), **_io_device(args)).permute(1, 0, 2, 3)[None]
                        for v in cvideos]
             except Exception as e:                                       # (:312-330: a clip that does not load is reported and skipped)
                 print(f"Error when loading video from  {cvideos}: {type(e).__name__}: {e}")
@@ -419,6 +441,8 @@ def run_jobs(args, with_ref: bool = False) -> None:
             keyframes = torch.cat(kfs, dim=0).to(dev)                    # (bs, 3, T, H, W) in [-1, 1]
             depth = torch.cat([depth_frames(args, v, k) for v, k in zip(cvideos, kfs)], dim=0).to(dev)
             txt, txt_uc = job_text(args, cprompts, dev, args.context_dim)
+            if args.gpu_io:          # raw depth -> finished hint by the kernels; the embedder passes a finished hint through
+                depth = _hint_embedder(model).normalize_gpu(depth)
             batch = {"txt": txt, "control_hint": depth}
             batch_uc = {"txt": txt_uc, "control_hint": depth.clone()}     # uc keeps the SAME hint (:339-344)
             ref = None
@@ -426,7 +450,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 if getattr(args, "auto_ref_editing", False):
                     print("Conduct auto ref editing, args.reference_path is ignored.")
                     raise NotImplementedError                            # as the reference: sampling_tv2v_ref.py:366-369
-                ref = torch.cat([load_img(r, (H, W)) for r in crefs], dim=0).to(dev)
+                ref = torch.cat([load_img(r, (H, W), **_io_device(args)) for r in crefs], dim=0).to(dev)
                 batch["cond_img"], batch_uc["cond_img"] = ref, ref.clone()
             c, uc = model.conditioner.get_unconditional_conditioning(batch, batch_uc=batch_uc)
             for k in c:
@@ -440,11 +464,15 @@ def run_jobs(args, with_ref: bool = False) -> None:
             print(f"chunk {idx}: {bs} clip(s) of {T} frames {H}x{W} in {time.time() - t0:.2f}s")
             to01 = lambda v: (torch.clamp(v.float(), -1.0, 1.0) + 1.0) / 2.0
             save_path = video_save_paths[idx] if video_save_paths else os.path.join(args.save_path, base_tag)
-            perform_save_locally_video(os.path.join(save_path, "original"), to01(keyframes), args.target_fps, args.save_type, save_grid=False)
+            if args.gpu_io and args.save_type == "gif":                   # uint8 frames made on the device: clamp((x + 1) / 2) is in the kernel
+                to01, io = (lambda v: v), dict(gpu_io=True, signed=True)
+            else:                                                         # (.npy keeps fp32 frames: the host route)
+                io = {}
+            perform_save_locally_video(os.path.join(save_path, "original"), to01(keyframes), args.target_fps, args.save_type, save_grid=False, **io)
             keyframes_paths = perform_save_locally_video(os.path.join(save_path, "result"), to01(samples), args.target_fps, args.save_type,
-                                                         return_savepaths=True, save_grid=False)
+                                                         return_savepaths=True, save_grid=False, **io)
             perform_save_locally_video(os.path.join(save_path, "control_hint"), to01(c["control_hint"]), args.target_fps, args.save_type,
-                                       save_grid=False)
+                                       save_grid=False, **io)
             print("Saved samples to {}. Enjoy.".format(save_path))
             log_info["video_paths"] += cvideos
             log_info["keyframes_paths"] += keyframes_paths

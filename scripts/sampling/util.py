@@ -276,8 +276,37 @@ def load_vae_file(model, vae_path: str) -> None:
 # Image files and GIFs go through Pillow; mp4 needs a codec library (decord / cv2 / imageio-ffmpeg) that is not
 # installed here and raises.
 # ------------------------------------------------------------------------------------------
-def load_img(p_cond_img: str, size: tuple = None) -> torch.Tensor:
-    """util.py:360-382: image file -> (1, 3, H, W) in [-1, 1], optional bicubic resize to size = (H, W)."""
+def _decode_rgb_u8(path: str) -> np.ndarray:
+    """Image file -> uint8 (H, W, 3) on the host (the decode is Pillow's on both routes)."""
+    from PIL import Image
+    a = np.array(Image.open(path))
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"{path}: the device route takes 8-bit RGB images, got {a.dtype} {a.shape}")
+    return a
+
+
+def _frames_to_device(frames, size, device) -> torch.Tensor:
+    """uint8 frames (list of (h, w, 3) arrays) -> fp32 (T, 3, H, W) in [-1, 1] on `device`: ONE upload of the uint8 frames and one
+    launch per resize pass for the whole clip when they share a size (else per frame), Pillow's 8-bit bicubic + x / 255 * 2 - 1 in
+    ccedit_amd/csrc/pixel.hip — bit-identical to load_img on the host."""
+    from ccedit_amd import ops
+    if len({f.shape for f in frames}) == 1:
+        groups = [np.stack(frames, axis=0)]
+    else:
+        assert size, "frames of different sizes need a target size"
+        groups = [f[None] for f in frames]
+    out = [ops.resize_u8_pil(torch.from_numpy(np.ascontiguousarray(g)).to(device), size or g.shape[1:3], to_float=True) for g in groups]
+    return (out[0] if len(out) == 1 else torch.cat(out, dim=1)).permute(1, 0, 2, 3)
+
+
+def load_img(p_cond_img: str, size: tuple = None, device=None) -> torch.Tensor:
+    """util.py:360-382: image file -> (1, 3, H, W) in [-1, 1], optional bicubic resize to size = (H, W).
+    device=None: Pillow and torch on the host, as the reference.  With a device the decoded uint8 image is uploaded and resized /
+    scaled there (same values, bit for bit)."""
+    if device is not None:
+        if size:
+            assert len(size) == 2, "size should be (H, W)"
+        return _frames_to_device([_decode_rgb_u8(p_cond_img)], size, device)
     from PIL import Image
     img = Image.open(p_cond_img)
     if size:
@@ -318,16 +347,29 @@ def HWC3(x: np.ndarray) -> np.ndarray:
     return (color * alpha + 255.0 * (1.0 - alpha)).clip(0, 255).astype(np.uint8)
 
 
-def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None) -> torch.Tensor:
-    """util.py:689-762: directory of frame images or a .gif -> keyframes (T, 3, H, W) in [-1, 1]."""
+def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None,
+                         device=None) -> torch.Tensor:
+    """util.py:689-762: directory of frame images or a .gif -> keyframes (T, 3, H, W) in [-1, 1].
+    device=None: everything on the host, as the reference.  With a device, decoding stays on the host (Pillow, uint8); the keyframes
+    are uploaded once as uint8 and resized / scaled by the kernels of ccedit_amd/csrc/pixel.hip: image files exactly as on the
+    host (Pillow's 8-bit bicubic), .gif frames by the fp32 bicubic of F.interpolate (equal to fp32 rounding)."""
+    if device is not None and size:
+        assert len(size) == 2, "size should be (H, W)"
     if os.path.isdir(video_path):
         files = sorted(os.listdir(video_path))
         idx = keyframe_indices(len(files), original_fps, target_fps, num_keyframes)
+        if device is not None:
+            return _frames_to_device([_decode_rgb_u8(os.path.join(video_path, files[i])) for i in idx], size, device)
         return torch.cat([load_img(os.path.join(video_path, files[i]), size) for i in idx], dim=0)
     if video_path.endswith(".gif"):
         from PIL import Image, ImageSequence
         frames = np.stack([HWC3(np.array(fr.convert("RGBA") if fr.mode == "P" and "transparency" in fr.info else fr.convert("RGB")))
                            for fr in ImageSequence.Iterator(Image.open(video_path))], axis=0)
+        if device is not None:
+            from ccedit_amd import ops
+            frames = frames[keyframe_indices(frames.shape[0], original_fps, target_fps, num_keyframes)]
+            x = _frames_to_device(list(frames), None, device).contiguous()                # uint8 -> x / 255 * 2 - 1, (T, 3, h, w)
+            return ops.resize_bicubic(x, size) if size else x
         frames = torch.from_numpy(frames).permute(0, 3, 1, 2).float() / 255.0
         frames = frames[keyframe_indices(frames.shape[0], original_fps, target_fps, num_keyframes)]
         frames = torch.clamp(frames * 2.0 - 1.0, -1.0, 1.0)
@@ -342,14 +384,26 @@ def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, nu
 
 
 def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, savetype: str = "gif",
-                               return_savepaths: bool = False, save_grid: bool = True):
+                               return_savepaths: bool = False, save_grid: bool = True, gpu_io: bool = False, signed: bool = False):
     """util.py:288-352: samples (B, 3, T, H, W) in [0, 1] -> <save_path>/gif/animation-XXXX.gif (+ grid/grid-XXXX.png:
-    the T frames side by side).  savetype='mp4' needs a codec library and raises."""
+    the T frames side by side).  savetype='mp4' needs a codec library and raises.
+    gpu_io (savetype='gif', device tensor): the uint8 frames are made on the device (ccedit_frames_to_u8) and 3 bytes per pixel
+    instead of 12 come to the host; the files are byte-identical.  `signed` (with gpu_io only): samples are the decoder's output in
+    [-1, 1] and clamp((x + 1) / 2, 0, 1) is part of the same kernel."""
     from PIL import Image
     assert samples.dim() == 5, "Expected samples to have shape (B, C, T, H, W)"
     assert savetype in ["gif", "mp4", "npy"]
+    assert gpu_io or not signed, "signed samples are only taken on the gpu_io route"
     if savetype == "mp4":
         raise NotImplementedError("mp4 encoding needs imageio-ffmpeg / cv2, not installed here: use savetype='gif'")
+    u8 = u8_grid = None
+    if gpu_io:
+        from ccedit_amd import ops
+        if savetype != "gif" or not samples.is_cuda:
+            raise ValueError("gpu_io saves uint8 frames (savetype='gif') of a device tensor")
+        x = samples.detach().float().contiguous()
+        u8 = ops.frames_to_u8(x, rounding=False, unit_range=not signed).cpu().numpy()                  # (B, T, H, W, 3)
+        u8_grid = ops.frames_to_u8(x, rounding=True, unit_range=not signed).cpu().numpy() if save_grid else None
     if savetype == "npy":          # (not in the reference) the frames themselves: <save_path>/npy/frames-XXXX.npy, (T, H, W, C) float32 in [0, 1]
         os.makedirs(os.path.join(save_path, "npy"), exist_ok=True)
         count = len(os.listdir(os.path.join(save_path, "npy")))
@@ -366,14 +420,15 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
         os.makedirs(os.path.join(save_path, "grid"), exist_ok=True)
         count_grid = len(os.listdir(os.path.join(save_path, "grid")))
     savepaths = []
-    for sample in samples:
-        frames_f = sample.detach().float().cpu().permute(1, 2, 3, 0).numpy()              # (T, H, W, C)
+    for b, sample in enumerate(samples):
+        if u8 is None:
+            frames_f = sample.detach().float().cpu().permute(1, 2, 3, 0).numpy()          # (T, H, W, C)
         if save_grid:
             # torchvision.utils.save_image(normalize=False, padding=0): x * 255 + 0.5, clamp, uint8
-            grid = np.concatenate(list(np.clip(frames_f * 255.0 + 0.5, 0, 255).astype(np.uint8)), axis=1)
+            grid = np.concatenate(list(np.clip(frames_f * 255.0 + 0.5, 0, 255).astype(np.uint8) if u8 is None else u8_grid[b]), axis=1)
             Image.fromarray(grid).save(os.path.join(save_path, "grid", f"grid-{count_grid:04}.png"))
             count_grid += 1
-        frames = [Image.fromarray(f) for f in (255.0 * frames_f).astype(np.uint8)]
+        frames = [Image.fromarray(f) for f in ((255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b])]
         savepath = os.path.join(save_path, "gif", f"animation-{count:04}.gif")
         frames[0].save(savepath, save_all=True, append_images=frames[1:], duration=int(round(1000.0 / fps)), loop=0)
         count += 1

@@ -142,6 +142,15 @@ class DepthMidasEncoder(_Precomputed):
         d = -(torch.clamp(d, 0, 1) * 2 - 1)
         return d.repeat(1, 3, 1, 1, 1).to(depth.dtype)
 
+    @staticmethod
+    def normalize_gpu(depth: torch.Tensor) -> torch.Tensor:
+        """`normalize` for a device tensor on the kernels of ccedit_amd/csrc/pixel.hip (one min / max over the whole batch, kept on
+        the device; same operations in the same order).  Chosen by the entry points under --gpu_io; forward() keeps `normalize`.
+        Constant depth gives NaN here as there (0 / 0)."""
+        from ccedit_amd import ops
+        d = depth.float().contiguous()
+        return ops.depth_hint(d, ops.minmax(d.view(1, -1)), flip=True).to(depth.dtype)
+
     def forward(self, x):
         if torch.is_tensor(x) and x.dim() == 5 and x.shape[1] == 1:
             return self.normalize(x)
@@ -174,6 +183,15 @@ class DepthZoeEncoder(DepthMidasEncoder):
         d /= (vmax - vmin)[:, None, None, None, None]
         d = torch.clamp(d, 0, 1) * 2 - 1
         return d.repeat(1, 3, 1, 1, 1).to(depth.dtype)
+
+    @staticmethod
+    def normalize_gpu(depth: torch.Tensor) -> torch.Tensor:
+        """`normalize` for a device tensor: both order statistics of every clip by one exact radix select (ccedit_kth_values), read by
+        the hint kernel from device memory.  vmax == vmin gives NaN / inf here as there."""
+        from ccedit_amd import ops
+        d = depth.float().contiguous()
+        n = d[0].numel()
+        return ops.depth_hint(d, ops.kth_values(d.view(d.shape[0], -1), [int(0.02 * n), int(0.85 * n)]), flip=False).to(depth.dtype)
 
 
 class VAEEmbedder(AbstractEmbModel):
