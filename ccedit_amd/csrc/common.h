@@ -153,3 +153,11 @@ int cc_pixel_minmax(const float* x, int32_t B, int64_t n, float* out, hipStream_
 int cc_pixel_depth_hint(const float* depth, float* hint, const float* stats, int32_t stat_stride, int32_t B, int64_t n, int32_t flip,
                         hipStream_t s);
 int cc_pixel_frames_to_u8(const float* x, uint8_t* out, int32_t B, int64_t P, int32_t mode, int32_t unit_range, hipStream_t s);
+
+// Edit-mask launchers (mask.hip); entry points and argument checks in core.cpp
+int cc_mask_resize_nearest(const uint8_t* src, uint8_t* dst, const int32_t* ytab, const int32_t* xtab, int32_t N, int32_t Hs, int32_t Ws,
+                           int32_t H, int32_t W, hipStream_t s);
+int cc_mask_latent(const uint8_t* mask_px, uint8_t* mask_lat, int64_t N, int32_t H, int32_t W, hipStream_t s);
+int cc_mask_inpaint_blend(const float* x, const float* x0, const float* noise, const uint8_t* mask, float* y, int32_t B, int32_t C, int64_t P,
+                          float sigma, float s, hipStream_t st);
+int cc_mask_composite(const float* result, const float* original, const uint8_t* mask_px, float* out, int32_t B, int64_t P, hipStream_t st);

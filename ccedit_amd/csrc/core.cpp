@@ -157,3 +157,39 @@ extern "C" int ccedit_frames_to_u8(const float* x, void* out, int32_t B, int64_t
     CC_CHECK_ARG(mode == 0 || mode == 1, "ccedit_frames_to_u8: mode=%d (0: truncate 255 v, 1: truncate 255 v + 0.5)", mode);
     return cc_pixel_frames_to_u8(x, (uint8_t*)out, B, P, mode, unit_range, (hipStream_t)stream);
 }
+
+// ---- edit masks (kernels and launchers: mask.hip).  Everything is checked here, before any HIP call.
+extern "C" int ccedit_mask_resize_nearest(const void* src, void* dst, const int32_t* ytab, const int32_t* xtab, int32_t N, int32_t Hs, int32_t Ws,
+                                          int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(src && dst && ytab && xtab, "ccedit_mask_resize_nearest: null pointer");
+    CC_CHECK_ARG(N > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "ccedit_mask_resize_nearest: sizes must be positive (N=%d, %dx%d -> %dx%d)", N, Hs, Ws,
+                 H, W);
+    CC_CHECK_ARG((int64_t)N * Hs * Ws < kPixelMax && (int64_t)N * H * W < kPixelMax,
+                 "ccedit_mask_resize_nearest: more than 2^31 bytes in one call (N=%d, %dx%d -> %dx%d)", N, Hs, Ws, H, W);
+    return cc_mask_resize_nearest((const uint8_t*)src, (uint8_t*)dst, ytab, xtab, N, Hs, Ws, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_mask_latent(const void* mask_px, void* mask_lat, int64_t N, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(mask_px && mask_lat, "ccedit_mask_latent: null pointer");
+    CC_CHECK_ARG(N > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "ccedit_mask_latent: N=%lld frames of %dx%d (positive, H and W multiples of 8)",
+                 (long long)N, H, W);
+    CC_CHECK_ARG(N < kPixelMax && N * H * W < kPixelMax * 4, "ccedit_mask_latent: more than 2^33 pixels in one call");
+    CC_CHECK_ARG(((uintptr_t)mask_px & 7) == 0, "ccedit_mask_latent: the pixel mask must be 8-byte aligned (a row of a cell is one 8-byte load)");
+    return cc_mask_latent((const uint8_t*)mask_px, (uint8_t*)mask_lat, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_inpaint_blend(const float* x, const float* x0, const float* noise, const void* mask, float* y, int32_t B, int32_t C, int64_t P,
+                                    float sigma, float s, void* stream) {
+    CC_CHECK_ARG(x && x0 && noise && mask && y, "ccedit_inpaint_blend: null pointer");
+    CC_CHECK_ARG(B > 0 && C > 0 && P > 0 && P < kPixelMax * 4 && (int64_t)B * C * P < kPixelMax * 4,
+                 "ccedit_inpaint_blend: B=%d C=%d P=%lld (positive, at most 2^33 elements)", B, C, (long long)P);
+    CC_CHECK_ARG(s > 0.0f, "ccedit_inpaint_blend: s=%g must be positive (s = sqrt(1 + sigma^2))", (double)s);
+    return cc_mask_inpaint_blend(x, x0, noise, (const uint8_t*)mask, y, B, C, P, sigma, s, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_mask_composite(const float* result, const float* original, const void* mask_px, float* out, int32_t B, int64_t P, void* stream) {
+    CC_CHECK_ARG(result && original && mask_px && out, "ccedit_mask_composite: null pointer");
+    CC_CHECK_ARG(B > 0 && P > 0 && P < kPixelMax * 4 && (int64_t)B * 3 * P < kPixelMax * 4,
+                 "ccedit_mask_composite: B=%d P=%lld (positive, at most 2^33 elements)", B, (long long)P);
+    return cc_mask_composite(result, original, (const uint8_t*)mask_px, out, B, P, (hipStream_t)stream);
+}

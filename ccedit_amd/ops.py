@@ -834,3 +834,72 @@ def frames_to_u8(x: torch.Tensor, rounding: bool = False, unit_range: bool = Fal
     hip.check(hip.lib().ccedit_frames_to_u8(x.data_ptr(), out.data_ptr(), b, t * h * w, int(rounding), int(unit_range), _stream()),
               "ccedit_frames_to_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# Edit masks (csrc/mask.hip): set = edit, clear = keep.  Pixel masks: byte >= 128 is set; latent masks: byte != 0
+# ------------------------------------------------------------------------------------------
+_NEAREST = {}
+
+
+def mask_resize_nearest(mask: torch.Tensor, size) -> torch.Tensor:
+    """Pillow's `Image.resize((W, H), NEAREST)` of uint8 masks (N, Hs, Ws) on the device, byte for byte -> uint8 (N, H, W)."""
+    from . import packing
+    assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.dim() == 3
+    n, hs, ws = mask.shape
+    h, w = int(size[0]), int(size[1])
+    tabs = []
+    for a, b in ((hs, h), (ws, w)):
+        key = (a, b, str(mask.device))
+        if key not in _NEAREST:
+            _NEAREST[key] = torch.from_numpy(packing.pil_nearest_index(a, b)).to(mask.device)
+        tabs.append(_NEAREST[key])
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=mask.device)
+    hip.check(hip.lib().ccedit_mask_resize_nearest(mask.data_ptr(), out.data_ptr(), tabs[0].data_ptr(), tabs[1].data_ptr(), n, hs, ws, h, w,
+                                                   _stream()), "ccedit_mask_resize_nearest")
+    return out
+
+
+def mask_latent(mask_px: torch.Tensor) -> torch.Tensor:
+    """Pixel mask uint8 (B, T, H, W) (>= 128 = edit) -> latent mask uint8 (B, T, H / 8, W / 8): 1 where more than 32 of the 64 pixels of
+    the cell are set — clamp(round(F.interpolate(mask, (T, H // 8, W // 8), mode="area")), 0, 1) of the binary mask."""
+    assert mask_px.dtype == torch.uint8 and mask_px.is_cuda and mask_px.is_contiguous() and mask_px.dim() == 4
+    b, t, h, w = mask_px.shape
+    assert h % 8 == 0 and w % 8 == 0, f"mask of {h}x{w}: H and W must be multiples of 8"
+    out = torch.empty((b, t, h // 8, w // 8), dtype=torch.uint8, device=mask_px.device)
+    hip.check(hip.lib().ccedit_mask_latent(mask_px.data_ptr(), out.data_ptr(), b * t, h, w, _stream()), "ccedit_mask_latent")
+    return out
+
+
+def inpaint_blend(x: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, mask: torch.Tensor, sigma: float, s: float,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The known-region re-injection of an inpainting step in one pass: y = mask ? x : (x0 + noise * sigma) / s over fp32 (B, C, T, h, w)
+    with the uint8 latent mask (B, T, h, w) broadcast over C (sampling.py:150-153, 213-216; s = sqrt(1 + sigma^2) from the host).
+    `out` may be `x`."""
+    for tns in (x, x0, noise):
+        assert tns.dtype == torch.float32 and tns.is_cuda and tns.is_contiguous() and tns.shape == x.shape and tns.dim() == 5
+    b, c, t, h, w = x.shape
+    assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and tuple(mask.shape) == (b, t, h, w), \
+        f"latent mask {tuple(mask.shape)} {mask.dtype} for a latent {tuple(x.shape)}: expected uint8 {(b, t, h, w)}"
+    y = torch.empty_like(x) if out is None else out
+    assert y.dtype == torch.float32 and y.is_contiguous() and y.shape == x.shape
+    n = x.numel()
+    _launch_mem("inpaint_blend", 16.0 * n + mask.numel(), lambda: hip.check(hip.lib().ccedit_inpaint_blend(
+        x.data_ptr(), x0.data_ptr(), noise.data_ptr(), mask.data_ptr(), y.data_ptr(), b, c, t * h * w, float(sigma), float(s), _stream()),
+        "ccedit_inpaint_blend"), (b, c, t, h, w))
+    return y
+
+
+def mask_composite(result: torch.Tensor, original: torch.Tensor, mask_px: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = mask ? result : original over fp32 frames (B, 3, T, H, W) with the uint8 pixel mask (B, T, H, W) (>= 128 = edit) broadcast
+    over the channels: the untouched pixels put back after the VAE round trip.  `out` may be `result`."""
+    for tns in (result, original):
+        assert tns.dtype == torch.float32 and tns.is_cuda and tns.is_contiguous() and tns.shape == result.shape and tns.dim() == 5
+    b, c, t, h, w = result.shape
+    assert c == 3 and mask_px.dtype == torch.uint8 and mask_px.is_cuda and mask_px.is_contiguous() and tuple(mask_px.shape) == (b, t, h, w), \
+        f"pixel mask {tuple(mask_px.shape)} {mask_px.dtype} for frames {tuple(result.shape)}: expected uint8 {(b, t, h, w)}"
+    y = torch.empty_like(result) if out is None else out
+    assert y.dtype == torch.float32 and y.is_contiguous() and y.shape == result.shape
+    hip.check(hip.lib().ccedit_mask_composite(result.data_ptr(), original.data_ptr(), mask_px.data_ptr(), y.data_ptr(), b, t * h * w, _stream()),
+              "ccedit_mask_composite")
+    return y

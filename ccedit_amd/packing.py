@@ -306,6 +306,7 @@ def pack_ff320_tail(ff: PackedFF320, wo: torch.Tensor, bo: Optional[torch.Tensor
 # Resize tap tables (csrc/pixel.hip).  One int32 table per axis, [out][2 + kmax]: first source index, tap count, then the
 # weights (zero padded to kmax) — fixed point for the 8-bit Pillow resize, fp32 bit patterns for the ATen bicubic.  Built once
 # per (in, out) size on the host, in double / fp32 like the libraries they reproduce; a few KB each.
+# pil_nearest_index: the gather table of the mask resize (csrc/mask.hip), int32 [out].
 # ------------------------------------------------------------------------------------------
 PIL_PRECISION_BITS = 32 - 8 - 2          # Pillow's 8-bit resample: weights are rounded to 22-bit fixed point
 
@@ -377,6 +378,23 @@ def aten_bicubic_taps(in_size: int, out_size: int):
     tab[:, 1] = 4
     tab[:, 2:] = w.view(np.int32)
     return tab
+
+
+def pil_nearest_index(in_size: int, out_size: int):
+    """The source index per output coordinate of Pillow's `Image.resize(NEAREST)` along one axis (the gather table of
+    ccedit_mask_resize_nearest): src = floor((dst + 0.5) * in / out).  Pillow steps the position by repeated addition in double
+    (0.5 * scale, then + scale per pixel: ImagingScaleAffine), so a position that is an integer in exact arithmetic may land on
+    either side of it; the same running sum is formed here — the product form differs from Pillow for one size pair in five.
+    -> int32 [out_size]."""
+    import numpy as np
+    assert in_size > 0 and out_size > 0
+    scale = in_size / out_size
+    pos = 0.5 * scale
+    idx = np.empty(out_size, dtype=np.int32)
+    for i in range(out_size):
+        idx[i] = min(int(pos), in_size - 1)
+        pos += scale
+    return idx
 
 
 def apply_pil_taps_reference(img, ytab, xtab):

@@ -366,6 +366,11 @@ class SingleStepDiffusionSampler(BaseDiffusionSampler):
         return ops.axpby(x0.float().contiguous(), noise, inv, float(sigma_i) * inv)
 
     def _inpaint_blend(self, x, x0, mask, sigma_i):
+        if mask.dtype == torch.uint8:
+            # a latent mask (B, T, h, w) from ops.mask_latent: one pass, the mask broadcast over the channels in the kernel, the reference's
+            # multiply / add / divide with sigma_i and sqrt(1 + sigma_i^2) as it computes them.  A fresh tensor: no CFG twin mark is touched
+            noise = self.noise_sampler(x0).float().contiguous()
+            return ops.inpaint_blend(x, x0.float().contiguous(), noise, mask, float(sigma_i), float(torch.sqrt(1.0 + sigma_i ** 2)))
         return ops.mask_blend(x, self._noised_original(x0, sigma_i), mask.float().expand_as(x).contiguous())
 
 

@@ -458,6 +458,31 @@ int ccedit_depth_hint(const float* depth, float* hint, const float* stats, int32
                       void* stream);
 int ccedit_frames_to_u8(const float* x, void* out, int32_t B, int64_t P, int32_t mode, int32_t unit_range, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Edit masks (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  What lies between a user's mask and the
+ * samplers' inpainting loops (`--inpainting_mode`; the reference's sampling_tv2v.py:385-407 leaves the mask to the user).  Kernels:
+ * csrc/mask.hip.  Convention: set = edit (generated), clear = keep the original — x = x * mask + img_orig * (1 - mask).  A byte of a
+ * PIXEL mask is set when it is >= 128, a byte of a LATENT mask when it is not 0.  All pointers are device pointers.
+ *
+ * ccedit_mask_resize_nearest: dst[n][y][x] = src[n][ytab[y]][xtab[x]], uint8 [N][Hs][Ws] -> [N][H][W]; the int32 index tables
+ *   (ccedit_amd/packing.py: pil_nearest_index, Pillow's NEAREST: floor((i + 0.5) * in / out)) are clamped into the source by the kernel.
+ * ccedit_mask_latent: pixel mask uint8 [N][H][W] (N = B T frames, H % 8 == W % 8 == 0, 8-byte aligned) -> latent mask uint8
+ *   [N][H/8][W/8]: 1 where MORE than 32 of the 64 pixels of the 8 x 8 cell are set, else 0 — round(area mean) with the tie 32/64
+ *   rounded to even, i.e. clamp(round(F.interpolate(mask, (T, H/8, W/8), mode="area")), 0, 1) of a binary mask, in integers.
+ * ccedit_inpaint_blend: y = m ? x : (x0 + noise * sigma) / s over fp32 [B][C][P] (P = T h w) with the latent mask uint8 [B][P] broadcast
+ *   over C; sigma and s = sqrt(1 + sigma^2) are computed by the host as the reference does.  One fp32 multiply, one add, one correctly
+ *   rounded divide, not contracted: for a binary mask bit-equal to x * m + ((x0 + noise * sigma) / s) * (1 - m) in fp32 (up to the sign
+ *   of a zero).  y may alias x.
+ * ccedit_mask_composite: out = m ? result : original over fp32 [B][3][P] (P = T H W) with the pixel mask uint8 [B][P] broadcast over the
+ *   three channels.  out may alias result.
+ */
+int ccedit_mask_resize_nearest(const void* src, void* dst, const int32_t* ytab, const int32_t* xtab, int32_t N, int32_t Hs, int32_t Ws,
+                               int32_t H, int32_t W, void* stream);
+int ccedit_mask_latent(const void* mask_px, void* mask_lat, int64_t N, int32_t H, int32_t W, void* stream);
+int ccedit_inpaint_blend(const float* x, const float* x0, const float* noise, const void* mask, float* y, int32_t B, int32_t C, int64_t P,
+                         float sigma, float s, void* stream);
+int ccedit_mask_composite(const float* result, const float* original, const void* mask_px, float* out, int32_t B, int64_t P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

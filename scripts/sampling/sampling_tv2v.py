@@ -19,6 +19,10 @@ Job mode (round 6) — the reference script's own surface (sampling_tv2v.py:45-7
 unless --disable_check_repeat).  What the reference computes with networks that are not part of this build enters as data: the depth
 of a clip from `<video>.depth.pt` / `--depth_root/<name>.pt` (raw depth (N,h,w) of ALL frames; normalised by the conditioner's
 MiDaS / Zoe recipe), prompts through `--tokenizer_path`; `--synthetic` substitutes the frames' luminance and prompt-seeded token ids.
+`--inpainting_mode` (a stub in the reference: "mask should be provided by the user", :385-407) works here with a user's mask —
+`--mask_path`, `--mask_root/<video name>.{png,gif}` | `<video name>/`, or `<video stem>.mask.png | .mask.gif | .mask/`; white = edit, black = keep —
+through the samplers' sample_inpainting and the kernels of ccedit_amd/csrc/mask.hip; `--mask_composite` puts the original pixels back
+outside the mask after decoding; the mask as applied is saved under <save_path>/<basemodel>/mask/.
 Launched under torch.distributed (RANK / WORLD_SIZE), the chunks are dealt round-robin to the ranks (BASELINE.json config 5:
 independent clips, one per GPU, no collective — ccedit_amd.parallel.shard_clips).
 """
@@ -83,7 +87,17 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--prior_coefficient_x", type=float, default=0.0)
     p.add_argument("--prior_coefficient_noise", type=float, default=1.0)
     p.add_argument("--sdedit_denoise_strength", type=float, default=0.0)
-    p.add_argument("--inpainting_mode", action="store_true", help="inpainting mode")
+    p.add_argument("--inpainting_mode", action="store_true",
+                   help="region-restricted editing: only where the clip's mask is white is generated, the rest is re-injected from the "
+                        "original before every sampler step (the samplers' sample_inpainting).  Needs a mask: --mask_path, --mask_root "
+                        "or <video stem>.mask.png / .mask.gif / .mask/ next to the video")
+    p.add_argument("--mask_path", type=str, default="",
+                   help="(not in the reference script, which leaves the mask to the user) the edit mask of a single-clip invocation: one "
+                        "image for all frames, or a directory of images / a .gif with one mask per frame of the video.  White = edit, black = keep")
+    p.add_argument("--mask_root", type=str, default="",
+                   help="directory of masks of a multi-clip invocation: <video name>.png, <video name>.gif or <video name>/")
+    p.add_argument("--mask_composite", action="store_true",
+                   help="with --inpainting_mode: put the original pixels back outside the mask after decoding (the VAE round trip is lossy)")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(not in the reference script) draw the samplers' per-step noise from a CPU generator with this seed instead of "
@@ -92,6 +106,25 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--gpu_io", action="store_true",
                    help="pixel I/O on the GPU (ccedit_amd/csrc/pixel.hip): frame / depth resize, depth hint normalisation and the uint8 "
                         "frames of --save_type gif; decoding and file writing stay on the host.  Default off: everything as before")
+
+
+def make_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser()
+    add_common_args(p)
+    return p
+
+
+def check_args(p: argparse.ArgumentParser, args) -> None:
+    """Combinations argparse cannot express: an error exit of the parser itself."""
+    if args.mask_composite and not args.inpainting_mode:
+        p.error("--mask_composite puts the original back outside the mask of --inpainting_mode: give both")
+
+
+def parse_args(argv=None):
+    p = make_parser()
+    args = p.parse_args(argv)
+    check_args(p, args)
+    return args
 
 
 def build_model(args):
@@ -192,17 +225,69 @@ def _cpu_noise(sampler, args) -> None:
         sampler.noise_sampler = lambda x: torch.randn(x.shape, generator=gen).to(x.device)
 
 
-def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video"):
-    """sampling_tv2v.py:361-470 for one clip."""
+# ------------------------------------------------------------------------------------------
+# Edit masks of --inpainting_mode (white = edit, black = keep the original)
+# ------------------------------------------------------------------------------------------
+NO_MASK = ("--inpainting_mode needs an edit mask (the reference script stops here too: \"mask should be provided by the user\", "
+           "sampling_tv2v.py:385-387).  Looked for: (1) --mask_path, (2) --mask_root/<video name>.png, .gif or --mask_root/<video name>/, "
+           "(3) <video stem>.mask.png, <video stem>.mask.gif or <video stem>.mask/ next to the video")
+
+
+def find_mask(args, video_path: str):
+    """The mask of one clip, looked up like its depth (depth_frames): --mask_path, else --mask_root/<video name>.{png,gif} or
+    --mask_root/<video name>/, else <video stem>.mask.png | .mask.gif | .mask/.  -> path, or None."""
+    if getattr(args, "mask_path", ""):
+        return args.mask_path
+    if not video_path:
+        return None
+    stem = video_path[:-4] if video_path.endswith((".mp4", ".gif")) else video_path.rstrip("/")
+    cands = [(stem + ".mask.png", os.path.isfile), (stem + ".mask.gif", os.path.isfile), (stem + ".mask", os.path.isdir)]
+    if getattr(args, "mask_root", ""):
+        base = os.path.join(args.mask_root, os.path.basename(stem))
+        cands = [(base + ".png", os.path.isfile), (base + ".gif", os.path.isfile), (base, os.path.isdir)] + cands
+    for cpath, present in cands:
+        if present(cpath):
+            return cpath
+    return None
+
+
+def clip_masks(args, video_paths, dev):
+    """The pixel masks of a chunk: uint8 (bs, T, H, W) on `dev`, 0 = keep / 255 = edit, resized like the frames' geometry (nearest).
+    A clip without a mask is an error (NotImplementedError, as the flag alone always was)."""
+    from scripts.sampling.util import count_video_frames, load_video_mask
+    out = []
+    for v in video_paths:
+        mpath = find_mask(args, v)
+        if mpath is None:
+            raise NotImplementedError(f"no mask for {v or 'the clip'}: {NO_MASK}")
+        video = resolve_video(v) if v else ""
+        n_all = count_video_frames(video) if video and (os.path.isdir(video) or video.endswith(".gif")) else None
+        out.append(load_video_mask(mpath, args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all, **_io_device(args)))
+    return torch.stack([m.to(dev) for m in out], dim=0).contiguous()
+
+
+def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None):
+    """sampling_tv2v.py:361-468 for one chunk: the sampled latent.  `mask`: the uint8 LATENT mask (bs, T, H / 8, W / 8) of
+    --inpainting_mode (ops.mask_latent of the pixel masks; 1 = edit)."""
     from scripts.sampling.util import init_sampling, prior_latent, sdedit_start
 
     def denoiser(inp, sigma, cc):
         return model.denoiser(model.model, inp, sigma, cc)
 
-    if getattr(args, "inpainting_mode", False):
-        # the reference script raises here too (sampling_tv2v.py:385-386, 444-445: the mask is not a user input yet);
-        # the loop itself is available as sampler.sample_inpainting(denoiser, x, c, x0=z, mask=mask, uc=uc)
-        raise NotImplementedError
+    inpaint = getattr(args, "inpainting_mode", False)
+    if inpaint and mask is None:
+        raise NotImplementedError(NO_MASK)
+
+    def run(sampler, start):
+        """What the reference's commented-out branch does with a user's mask (sampling_tv2v.py:395-407, 454-466): the known latent is the
+        encoded clip, the loop is the sampler's sample_inpainting (uc['control_hint'] already equals c['control_hint'] here)."""
+        if not inpaint:
+            return sampler(denoiser, start, c, uc=uc)
+        if not hasattr(sampler, "sample_inpainting"):
+            raise NotImplementedError(f"{args.sampler_name} has no inpainting loop (the reference has one for the EDM and the ancestral samplers)")
+        z = model.encode_first_stage(keyframes)
+        return sampler.sample_inpainting(denoiser, start, c, uc=uc, x0=z, mask=mask)
+
     if args.sdedit_denoise_strength == 0.0:
         if args.prior_coefficient_x != 0.0:
             randn = prior_latent(model, randn, args.prior_coefficient_x, args.prior_coefficient_noise, keyframes, ref, prior_type)
@@ -210,7 +295,7 @@ def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_t
                                 discretization_name=args.discretization_name, guider_config_target=GUIDER,
                                 cfg_scale=args.cfg_scale)
         _cpu_noise(sampler, args)
-        samples = sampler(denoiser, randn, c, uc=uc)
+        return run(sampler, randn)
     else:
         assert 0.0 < args.sdedit_denoise_strength <= 1.0, "sdedit_denoise_strength should be in (0, 1]"
         assert args.prior_coefficient_x == 0, "prior_coefficient_x should be 0 when using sdedit_denoise_strength"
@@ -218,8 +303,18 @@ def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_t
                                 discretization_name=args.discretization_name, guider_config_target=GUIDER,
                                 cfg_scale=args.cfg_scale, img2img_strength=args.sdedit_denoise_strength)
         _cpu_noise(sampler, args)
-        samples = sampler(denoiser, sdedit_start(model, sampler, keyframes), cond=c, uc=uc)
-    return model.decode_first_stage(samples)
+        return run(sampler, sdedit_start(model, sampler, keyframes))
+
+
+def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, mask_px=None):
+    """sampling_tv2v.py:361-470 for one chunk: sample, decode and — with --mask_composite and the pixel masks `mask_px` — put the
+    original pixels back outside the mask (ccedit_mask_composite)."""
+    z = sample_latent(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=prior_type, mask=mask)
+    samples = model.decode_first_stage(z)
+    if getattr(args, "mask_composite", False) and mask_px is not None:
+        from ccedit_amd import ops
+        samples = ops.mask_composite(samples.float().contiguous(), keyframes.float().contiguous(), mask_px)
+    return samples
 
 
 # ------------------------------------------------------------------------------------------
@@ -457,9 +552,14 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 if isinstance(c[k], torch.Tensor):
                     c[k], uc[k] = c[k][:bs].to(dev), uc[k][:bs].to(dev)
             randn = torch.randn(bs, 4, T, H // 8, W // 8, generator=g).to(dev)
+            mask_px = mask_lat = None
+            if args.inpainting_mode:                                      # (no mask: NotImplementedError, as the flag alone always was)
+                from ccedit_amd import ops
+                mask_px = clip_masks(args, cvideos, dev)
+                mask_lat = ops.mask_latent(mask_px)
             t0 = time.time()
             samples = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref,
-                                 prior_type=getattr(args, "prior_type", "video"))
+                                 prior_type=getattr(args, "prior_type", "video"), mask=mask_lat, mask_px=mask_px)
             torch.cuda.synchronize()
             print(f"chunk {idx}: {bs} clip(s) of {T} frames {H}x{W} in {time.time() - t0:.2f}s")
             to01 = lambda v: (torch.clamp(v.float(), -1.0, 1.0) + 1.0) / 2.0
@@ -473,6 +573,10 @@ def run_jobs(args, with_ref: bool = False) -> None:
                                                          return_savepaths=True, save_grid=False, **io)
             perform_save_locally_video(os.path.join(save_path, "control_hint"), to01(c["control_hint"]), args.target_fps, args.save_type,
                                        save_grid=False, **io)
+            if mask_px is not None:                                       # the mask as it was applied, same naming as control_hint/
+                m01 = (mask_px >= 128).float()[:, None].expand(-1, 3, -1, -1, -1).contiguous()
+                perform_save_locally_video(os.path.join(save_path, "mask"), m01 * 2.0 - 1.0 if io else m01, args.target_fps, args.save_type,
+                                           save_grid=False, **io)
             print("Saved samples to {}. Enjoy.".format(save_path))
             log_info["video_paths"] += cvideos
             log_info["keyframes_paths"] += keyframes_paths
@@ -486,14 +590,21 @@ def run_jobs(args, with_ref: bool = False) -> None:
             model, dev = build_model(args_nobase)                        # (:517-520: the checkpoint is loaded again before the next base model)
 
 
+def single_clip_masks(args, dev) -> dict:
+    """mask= / mask_px= of sample_one for the single-clip (tensor) mode: {} without --inpainting_mode."""
+    if not args.inpainting_mode:
+        return {}
+    from ccedit_amd import ops
+    mask_px = clip_masks(args, [args.video_path], dev)
+    return dict(mask=ops.mask_latent(mask_px), mask_px=mask_px)
+
+
 def job_mode(args) -> bool:
     return bool(args.prompt_listpath or args.videos_directory or args.json_path or (args.prompt and args.video_path))
 
 
 def main():
-    p = argparse.ArgumentParser()
-    add_common_args(p)
-    args = p.parse_args()
+    args = parse_args()
     torch.manual_seed(args.seed)
     torch.set_grad_enabled(False)
     if job_mode(args):
@@ -502,7 +613,8 @@ def main():
     model, dev = build_model(args)
     T, h, w = args.num_keyframes, args.H // 8, args.W // 8
     g = torch.Generator().manual_seed(args.seed)
-    need_frames = args.prior_coefficient_x != 0.0 or args.sdedit_denoise_strength != 0.0
+    need_frames = args.prior_coefficient_x != 0.0 or args.sdedit_denoise_strength != 0.0 or args.inpainting_mode
+    masks = single_clip_masks(args, dev)
     cond = conditioning_tensors(args, g, need_frames)
     hint = cond["control_hint"].to(dev)
     txt, txt_uc = text_inputs(cond, dev, args)
@@ -517,7 +629,7 @@ def main():
             continue
         randn = torch.randn(1, 4, T, h, w, generator=g).to(dev)                           # CPU generator, like :363
         t0 = time.time()
-        x = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes)
+        x = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes, **masks)
         torch.cuda.synchronize()
         save_result(args, tag, x)
         print(f"{tag}: {T} frames {args.H}x{args.W} in {time.time() - t0:.2f}s")

@@ -20,18 +20,29 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from scripts.sampling.sampling_tv2v import (add_common_args, build_model, conditioning_tensors, job_mode, run_jobs, sample_one,  # noqa: E402
-                                            save_result, text_inputs)
+from scripts.sampling.sampling_tv2v import (add_common_args, build_model, check_args, conditioning_tensors, job_mode, run_jobs,  # noqa: E402
+                                            sample_one, save_result, single_clip_masks, text_inputs)
 
 
-def main():
+def make_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     add_common_args(p)
     p.add_argument("--prior_type", type=str, default="ref", choices=["video", "ref", "video_ref"])
     p.add_argument("--reference_path", type=str, default="", help="edited centre frame (image file) -> cond_img")
     p.add_argument("--reference_root", type=str, default="", help="path to the root of reference videos")
     p.add_argument("--auto_ref_editing", action="store_true", help="auto center editing")
-    args = p.parse_args()
+    return p
+
+
+def parse_args(argv=None):
+    p = make_parser()
+    args = p.parse_args(argv)
+    check_args(p, args)
+    return args
+
+
+def main():
+    args = parse_args()
     torch.manual_seed(args.seed)
     torch.set_grad_enabled(False)
     if job_mode(args):        # the reference script's list / directory / BalanceCC-json surface (sampling_tv2v_ref.py:124-194, 340-400)
@@ -43,7 +54,8 @@ def main():
     model, dev = build_model(args)
     T, h, w = args.num_keyframes, args.H // 8, args.W // 8
     g = torch.Generator().manual_seed(args.seed)
-    need_frames = (args.prior_coefficient_x != 0.0 and args.prior_type != "ref") or args.sdedit_denoise_strength != 0.0
+    need_frames = (args.prior_coefficient_x != 0.0 and args.prior_type != "ref") or args.sdedit_denoise_strength != 0.0 or args.inpainting_mode
+    masks = single_clip_masks(args, dev)
     cond = conditioning_tensors(args, g, need_frames, need_ref=True)
     hint, ref = cond["control_hint"].to(dev), cond["cond_img"].to(dev)
     txt, txt_uc = text_inputs(cond, dev)
@@ -58,7 +70,7 @@ def main():
             continue
         randn = torch.randn(1, 4, T, h, w, generator=g).to(dev)
         t0 = time.time()
-        x = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=args.prior_type)
+        x = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=args.prior_type, **masks)
         torch.cuda.synchronize()
         save_result(args, tag, x)
         print(f"{tag}: {T} frames {args.H}x{args.W} in {time.time() - t0:.2f}s")

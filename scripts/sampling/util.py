@@ -383,6 +383,67 @@ def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, nu
     raise ValueError("Unsupported video format. Only support dirctory, .mp4 and .gif.")
 
 
+def count_video_frames(video_path: str) -> int:
+    """Number of frames of what load_video_keyframes reads: files of a directory, frames of a .gif."""
+    if os.path.isdir(video_path):
+        return len(os.listdir(video_path))
+    if video_path.endswith(".gif"):
+        from PIL import Image
+        return int(getattr(Image.open(video_path), "n_frames", 1))
+    raise ValueError("Unsupported video format. Only support dirctory, .mp4 and .gif.")
+
+
+_MASK_IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".tif", ".tiff")
+
+
+def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None, num_allframes: int = None,
+                    device=None) -> torch.Tensor:
+    """The edit mask of a clip -> uint8 (T, H, W) holding 0 (keep the original) or 255 (edit): the reference's
+    x = x * mask + img_orig * (1 - mask) with white = 1.  (The reference leaves the mask to the user: sampling_tv2v.py:385-407.)
+    mask_path: what load_video_keyframes accepts — a directory of images or a .gif, one mask per frame of the VIDEO: `num_allframes`
+    (None: not checked) must equal its frame count, the keyframes are selected by the same `keyframe_indices` rule as the frames — or
+    ONE image file, used for every keyframe.  Any image mode is taken through its luminance (`convert("L")`); a value >= 128 is white.
+    Resize to size = (H, W) is nearest-neighbour on the binarised mask, src = floor((dst + 0.5) * in / out) (Pillow's NEAREST, its
+    running sum in double included: ccedit_amd/packing.py pil_nearest_index).  device=None: Pillow on the host.  With a device the
+    binarised keyframe masks are uploaded once and gathered there (ccedit_mask_resize_nearest): identical bytes."""
+    from PIL import Image, ImageSequence
+    if size:
+        assert len(size) == 2, "size should be (H, W)"
+
+    def lum(img):
+        a = np.array(img.convert("L"))
+        return np.where(a >= 128, 255, 0).astype(np.uint8)
+
+    if os.path.isdir(mask_path):
+        files = sorted(os.listdir(mask_path))
+        n, pick = len(files), lambda i: lum(Image.open(os.path.join(mask_path, files[i])))
+    elif mask_path.endswith(".gif"):
+        frames = [lum(fr) for fr in ImageSequence.Iterator(Image.open(mask_path))]
+        n, pick = len(frames), lambda i: frames[i]
+    elif mask_path.lower().endswith(_MASK_IMAGE_EXT):
+        one = lum(Image.open(mask_path))
+        n, pick = None, lambda i: one
+    else:
+        raise ValueError(f"Unsupported mask format: {mask_path}. Only support directory, .gif and one image file {_MASK_IMAGE_EXT}.")
+    if n is None:
+        masks = [pick(0)] * num_keyframes
+    else:
+        if num_allframes is not None and n != num_allframes:
+            raise ValueError(f"mask {mask_path} has {n} frames, the video has {num_allframes}: a mask sequence needs one mask per frame "
+                             "(or give one image for all frames)")
+        masks = [pick(int(i)) for i in keyframe_indices(n, original_fps, target_fps, num_keyframes)]
+    if len({m.shape for m in masks}) != 1:
+        raise ValueError(f"mask {mask_path}: frames of different sizes {sorted({m.shape for m in masks})}")
+    if device is not None:
+        from ccedit_amd import ops
+        m = torch.from_numpy(np.ascontiguousarray(np.stack(masks, axis=0))).to(device)
+        return ops.mask_resize_nearest(m, size) if size and tuple(size) != tuple(m.shape[1:]) else m
+    if size and tuple(size) != masks[0].shape:
+        h, w = size
+        masks = [np.array(Image.fromarray(m).resize((w, h), Image.NEAREST)) for m in masks]
+    return torch.from_numpy(np.ascontiguousarray(np.stack(masks, axis=0)))
+
+
 def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, savetype: str = "gif",
                                return_savepaths: bool = False, save_grid: bool = True, gpu_io: bool = False, signed: bool = False):
     """util.py:288-352: samples (B, 3, T, H, W) in [0, 1] -> <save_path>/gif/animation-XXXX.gif (+ grid/grid-XXXX.png:
