@@ -161,3 +161,8 @@ int cc_mask_latent(const uint8_t* mask_px, uint8_t* mask_lat, int64_t N, int32_t
 int cc_mask_inpaint_blend(const float* x, const float* x0, const float* noise, const uint8_t* mask, float* y, int32_t B, int32_t C, int64_t P,
                           float sigma, float s, hipStream_t st);
 int cc_mask_composite(const float* result, const float* original, const uint8_t* mask_px, float* out, int32_t B, int64_t P, hipStream_t st);
+
+// Window launchers (window.hip); entry points and argument checks in core.cpp
+int cc_window_gather(const float* x, float* xw, const int32_t* starts, int32_t W, int32_t BC, int32_t N, int32_t T, int64_t P, hipStream_t s);
+int cc_window_fuse(const float* const* yw, float* out, const int32_t* starts, const float* coef, int32_t W, int32_t BC, int32_t N, int32_t T,
+                   int64_t P, hipStream_t s);

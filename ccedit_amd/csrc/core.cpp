@@ -193,3 +193,28 @@ extern "C" int ccedit_mask_composite(const float* result, const float* original,
                  "ccedit_mask_composite: B=%d P=%lld (positive, at most 2^33 elements)", B, (long long)P);
     return cc_mask_composite(result, original, (const uint8_t*)mask_px, out, B, P, (hipStream_t)stream);
 }
+
+// ---- windows of a long clip (kernels and launchers: window.hip).  Everything the host can see is checked here, before any HIP call;
+// the device tables (starts, coef, the pointer table) are held inside their tensors by the kernels themselves.
+static int window_shape_ok(const char* fn, int32_t W, int32_t B, int32_t C, int32_t N, int32_t T, int64_t P) {
+    CC_CHECK_ARG(W >= 1 && W <= 4096 && B > 0 && C > 0 && T >= 1 && N >= T && P > 0,
+                 "%s: W=%d (1 ... 4096) windows of T=%d frames over N=%d (N >= T >= 1), B=%d C=%d P=%lld (positive)", fn, W, T, N, B, C, (long long)P);
+    CC_CHECK_ARG((int64_t)B * C < kPixelMax && P < kPixelMax * 4 && (int64_t)B * C * N * P < kPixelMax * 4 && (int64_t)W * B * C * T * P < kPixelMax * 4,
+                 "%s: more than 2^33 elements in one call (W=%d B=%d C=%d N=%d T=%d P=%lld)", fn, W, B, C, N, T, (long long)P);
+    return CCEDIT_OK;
+}
+
+extern "C" int ccedit_window_gather(const float* x, float* xw, const int32_t* starts, int32_t W, int32_t B, int32_t C, int32_t N, int32_t T,
+                                    int64_t P, void* stream) {
+    CC_CHECK_ARG(x && xw && starts, "ccedit_window_gather: null pointer");
+    if (int rc = window_shape_ok("ccedit_window_gather", W, B, C, N, T, P)) return rc;
+    return cc_window_gather(x, xw, starts, W, B * C, N, T, P, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_window_fuse(const void* yw, float* out, const int32_t* starts, const float* coef, int32_t W, int32_t B, int32_t C,
+                                  int32_t N, int32_t T, int64_t P, void* stream) {
+    CC_CHECK_ARG(yw && out && starts && coef, "ccedit_window_fuse: null pointer");
+    CC_CHECK_ARG(((uintptr_t)yw & 7) == 0, "ccedit_window_fuse: the table of window pointers must be 8-byte aligned");
+    if (int rc = window_shape_ok("ccedit_window_fuse", W, B, C, N, T, P)) return rc;
+    return cc_window_fuse((const float* const*)yw, out, starts, coef, W, B * C, N, T, P, (hipStream_t)stream);
+}

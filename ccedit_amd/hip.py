@@ -148,6 +148,11 @@ _SIGS = {
     "ccedit_inpaint_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float,
                                        C.c_float, C.c_void_p]),
     "ccedit_mask_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    # windows of a long clip (csrc/window.hip): added within ABI 12, nothing existing changed
+    "ccedit_window_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                       C.c_void_p]),
+    "ccedit_window_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int64, C.c_void_p]),
 }
 KTH_WORKSPACE_BYTES_PER_ROW = 4128      # ccedit_kth_values: (prefix, rank) x 4 + 4 x 256 counters, uint32
 

@@ -1271,7 +1271,7 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
         # host sync, remembered with the tensor's identity + version like the caches above; never decided while capturing a graph).
         dup = False
         if self.dedup_hint and hint5d.shape[0] % 2 == 0:
-            if not isinstance(self._hint_dup, dict) or len(self._hint_dup) >= 8:
+            if not isinstance(self._hint_dup, dict) or len(self._hint_dup) >= 2 * self._hint_slots:
                 self._hint_dup = {}
             ent = self._hint_dup.get(key[:-1])
             if ent is None and not torch.cuda.is_current_stream_capturing():
@@ -1286,7 +1286,7 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
         if dup and not half:
             g = torch.cat([g, g])
         if self.cache_hint_stem:
-            if not isinstance(self._hint_val, dict) or len(self._hint_val) >= 4:     # one entry per CFG half (+ shards)
+            if not isinstance(self._hint_val, dict) or len(self._hint_val) >= self._hint_slots:     # one entry per CFG half (+ shards)
                 self._hint_val = {}
             self._hint_val[key] = (hint5d, g)
         return g
@@ -1355,6 +1355,29 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
     _graphs = None
     _graph_failed = False
 
+    # A long clip (ccedit_amd/windows.py) evaluates W windows in turn at every sampler evaluation: W conditioning keys alive at once.
+    # With the limits of a plain clip (2 graphs, 4 stem outputs) three or more windows evict, each time, the entry the next window
+    # needs — nothing would ever be replayed.  reserve_windows(W) sizes the per-clip caches for W windows and gives the W graphs ONE
+    # memory pool: they replay strictly one after another on one stream and every replay's output is cloned before the next (see
+    # _forward_graphed), so the activations of one evaluation are held once, not W times.  Without the call nothing changes.
+    _graph_slots = 2
+    _hint_slots = 4
+    _graph_pool = None
+    graph_counts = None         # {"eager", "capture", "replay"}: evaluations of _forward_graphed by kind since reserve_windows / first use
+
+    def reserve_windows(self, windows: int) -> None:
+        """Size the per-clip caches for `windows` conditioning keys evaluated in turn (0 or 1: back to a plain clip's limits)."""
+        w = max(int(windows), 1)
+        self._graph_slots = max(2, w)
+        self._hint_slots = max(4, 2 * w)           # per window: one stem output per kind of evaluation (shared CFG prefix or not)
+        self._graph_pool = torch.cuda.graph_pool_handle() if w > 1 and torch.cuda.is_available() else None
+        self.graph_counts = dict(eager=0, capture=0, replay=0)
+
+    def _count(self, kind: str) -> None:
+        if self.graph_counts is None:
+            self.graph_counts = dict(eager=0, capture=0, replay=0)
+        self.graph_counts[kind] += 1
+
     def forward(self, x: torch.Tensor, t: torch.Tensor, c: Dict[str, torch.Tensor], **kwargs) -> torch.Tensor:
         # row-sharded evaluations are captured too when their exchanges are stream operations (RCCL; the host-staged gloo transport of the
         # CPU / one-GPU tests is not): the launch count per rank is the single-GPU one while every kernel is N times shorter
@@ -1377,10 +1400,11 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
             self._graphs = {}
         ent = self._graphs.get(key)
         if ent is None:
-            while len(self._graphs) >= 2:                       # a clip uses one key; keep the previous clip's until it is replaced
+            while len(self._graphs) >= self._graph_slots:       # a clip uses one key (W with windows); keep the previous clip's until it is replaced
                 self._graphs.pop(next(iter(self._graphs)))
             # the conditioning tensors are pinned while the entry lives: a key match always means the same bytes (see _guided_hint)
             self._graphs[key] = dict(pins=[v for v in c.values() if torch.is_tensor(v)])
+            self._count("eager")
             return self._forward_eager(x, t, c, _twins=twins)
         if "graph" not in ent:
             ok = True
@@ -1389,7 +1413,7 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
                 g = torch.cuda.CUDAGraph()
                 # thread_local: calls from OTHER threads (the process group's watchdog polling its events when torch.distributed is
                 # initialised — bench.py --gpus N) must not invalidate the capture
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode="thread_local"):
                     # scratch arenas used while capturing must live in this graph's pool, and nothing outside the capture may go on
                     # using them: their zero fills are only RECORDED, and after a failed capture never run at all — the eager
                     # fallback would accumulate statistics onto uninitialised memory and wait on garbage split-K counters
@@ -1401,6 +1425,7 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
                     finally:
                         ops.reset_stream_scratch()
                 ent["graph"] = g
+                self._count("capture")
                 ent["pins"].append(dict(self._hint_val) if isinstance(self._hint_val, dict) else None)   # the cached stem output it reads
                 ent["pins"].append(dict(self._tkv_val) if isinstance(self._tkv_val, dict) else None)     # ... and the cached text K / V
             except Exception as e:                              # capture is an optimisation: report once, keep evaluating eagerly
@@ -1421,6 +1446,7 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
         else:
             ent["x"].copy_(x)
             ent["t"].copy_(t)
+            self._count("replay")
         ent["graph"].replay()
         return ent["out"].clone()
 

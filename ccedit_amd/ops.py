@@ -903,3 +903,46 @@ def mask_composite(result: torch.Tensor, original: torch.Tensor, mask_px: torch.
     hip.check(hip.lib().ccedit_mask_composite(result.data_ptr(), original.data_ptr(), mask_px.data_ptr(), y.data_ptr(), b, t * h * w, _stream()),
               "ccedit_mask_composite")
     return y
+
+
+# ------------------------------------------------------------------------------------------
+# Windows of a long clip (csrc/window.hip): gather W windows of T frames, cross-fade their outputs back (ccedit_amd/windows.py)
+# ------------------------------------------------------------------------------------------
+def _chk_latent(t: torch.Tensor, name: str):
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 5:
+        raise ValueError(f"{name}: expected a contiguous cuda fp32 (B, C, frames, h, w) tensor, got {t.dtype} {t.device} {tuple(t.shape)} "
+                         f"contiguous={t.is_contiguous()}")
+
+
+def window_gather(x: torch.Tensor, starts: torch.Tensor, frames: int) -> torch.Tensor:
+    """(B, C, N, h, w) fp32 -> (W, B, C, T, h, w): window i is x[:, :, starts[i]:starts[i] + T], all windows in one launch, a bit copy.
+    `starts`: int32 (W,) on the device (windows.plan); the result's [i] are contiguous (B, C, T, h, w) tensors."""
+    _chk_latent(x, "window_gather")
+    assert starts.dtype == torch.int32 and starts.is_cuda and starts.is_contiguous() and starts.dim() == 1
+    b, c, n, h, w = x.shape
+    nw, t = starts.shape[0], int(frames)
+    xw = torch.empty((nw, b, c, t, h, w), dtype=torch.float32, device=x.device)
+    _launch_mem("window_gather", 8.0 * xw.numel(), lambda: hip.check(hip.lib().ccedit_window_gather(
+        x.data_ptr(), xw.data_ptr(), starts.data_ptr(), nw, b, c, n, t, h * w, _stream()), "ccedit_window_gather"), (nw, b, c, t, h, w))
+    return xw
+
+
+def window_fuse(ys, starts: torch.Tensor, coef: torch.Tensor, frames: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The W windows' outputs `ys` (each (B, C, T, h, w) fp32, read in place through a device table of their addresses) -> (B, C, N, h, w):
+    out[:, :, f] = sum over the windows covering f, ascending, of coef[i, f - starts[i]] * ys[i][:, :, f - starts[i]] — product first,
+    then multiply and add per further term, bit-equal to that loop in numpy float32.  `coef`: fp32 (W, T) on the device (windows.plan)."""
+    nw, n = len(ys), int(frames)
+    assert nw >= 1 and starts.dtype == torch.int32 and starts.is_cuda and starts.is_contiguous() and tuple(starts.shape) == (nw,)
+    for y in ys:
+        _chk_latent(y, "window_fuse")
+        assert y.shape == ys[0].shape and y.device == ys[0].device
+    b, c, t, h, w = ys[0].shape
+    assert coef.dtype == torch.float32 and coef.is_cuda and coef.is_contiguous() and tuple(coef.shape) == (nw, t)
+    y = torch.empty((b, c, n, h, w), dtype=torch.float32, device=ys[0].device) if out is None else out
+    assert y.dtype == torch.float32 and y.is_contiguous() and tuple(y.shape) == (b, c, n, h, w)
+    # the W addresses change with every evaluation: 8 W bytes through pinned memory, not blocking (see Denoiser.__call__)
+    table = torch.tensor([v.data_ptr() for v in ys], dtype=torch.int64).pin_memory().to(y.device, non_blocking=True)
+    _launch_mem("window_fuse", 4.0 * (nw * ys[0].numel() + y.numel()), lambda: hip.check(hip.lib().ccedit_window_fuse(
+        table.data_ptr(), y.data_ptr(), starts.data_ptr(), coef.data_ptr(), nw, b, c, n, t, h * w, _stream()), "ccedit_window_fuse"),
+        (nw, b, c, n, h, w))
+    return y

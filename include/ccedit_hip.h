@@ -483,6 +483,28 @@ int ccedit_inpaint_blend(const float* x, const float* x0, const float* noise, co
                          float sigma, float s, void* stream);
 int ccedit_mask_composite(const float* result, const float* original, const void* mask_px, float* out, int32_t B, int64_t P, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Windows (added without an ABI bump: two new functions, CCEDIT_ABI_VERSION stays 12).  A clip of N > T keyframes is covered by W
+ * overlapping windows of T frames; at every network evaluation each window goes through the network at its usual shape and the
+ * windows' denoised latents are cross-faded into one latent of N frames (ccedit_amd/windows.py: plan, WindowedDenoiser;
+ * `--window_frames`).  Kernels: csrc/window.hip.  Latents are fp32 [B][C][frames][P], P = h w.  `starts` (int32 [W], ascending, each
+ * 0 ... N - T) and `coef` (fp32 [W][T], per frame summing to 1 over the windows that cover it) are device tables uploaded once per
+ * clip; the kernels clamp a start into 0 ... N - T and write 0 for a frame no window covers, so no table can take an access outside
+ * its tensor.  All pointers are device pointers.
+ *
+ * ccedit_window_gather: xw[w][b][c][j][p] = x[b][c][starts[w] + j][p]; x is [B][C][N][P], xw [W][B][C][T][P] (window w is the contiguous
+ *   tensor xw + w B C T P); all W windows in one launch, a bit copy.
+ * ccedit_window_fuse: out[b][c][f][p] = sum, over the windows covering f in ascending w, of coef[w][f - starts[w]] *
+ *   y_w[b][c][f - starts[w]][p]; out is [B][C][N][P], y_w [B][C][T][P] at yw[w].  `yw` is a DEVICE table of W pointers (8-byte aligned):
+ *   the windows' outputs are read where the network left them, nothing is staged into one buffer first.  The first term is the
+ *   product alone, every further term one multiply then one add, never an fma: bit-equal to the same loop in numpy float32, and a
+ *   frame covered by one window (coefficient 1.0f) is a bit copy.  One launch, every output element written once, no atomics.
+ */
+int ccedit_window_gather(const float* x, float* xw, const int32_t* starts, int32_t W, int32_t B, int32_t C, int32_t N, int32_t T, int64_t P,
+                         void* stream);
+int ccedit_window_fuse(const void* yw, float* out, const int32_t* starts, const float* coef, int32_t W, int32_t B, int32_t C, int32_t N,
+                       int32_t T, int64_t P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

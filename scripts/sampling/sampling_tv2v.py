@@ -23,6 +23,10 @@ MiDaS / Zoe recipe), prompts through `--tokenizer_path`; `--synthetic` substitut
 `--mask_path`, `--mask_root/<video name>.{png,gif}` | `<video name>/`, or `<video stem>.mask.png | .mask.gif | .mask/`; white = edit, black = keep —
 through the samplers' sample_inpainting and the kernels of ccedit_amd/csrc/mask.hip; `--mask_composite` puts the original pixels back
 outside the mask after decoding; the mask as applied is saved under <save_path>/<basemodel>/mask/.
+`--window_frames T` (with `--window_overlap O`, default T // 2) lifts the limit of one window of keyframes: with `--num_keyframes N` > T the
+clip is covered by overlapping windows of T frames, each evaluated by the unchanged network at every sampler evaluation and fused into
+one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everything else — inpainting, SDEdit, the prior mix,
+--noise_seed, --gpu_io — runs on the long latent as on a short one, first-stage encode / decode in groups of at most T frames.
 Launched under torch.distributed (RANK / WORLD_SIZE), the chunks are dealt round-robin to the ranks (BASELINE.json config 5:
 independent clips, one per GPU, no collective — ccedit_amd.parallel.shard_clips).
 """
@@ -98,6 +102,12 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="directory of masks of a multi-clip invocation: <video name>.png, <video name>.gif or <video name>/")
     p.add_argument("--mask_composite", action="store_true",
                    help="with --inpainting_mode: put the original pixels back outside the mask after decoding (the VAE round trip is lossy)")
+    p.add_argument("--window_frames", type=int, default=0,
+                   help="(not in the reference script) keyframes per network evaluation; with --num_keyframes above it the clip is covered "
+                        "by overlapping windows of this many frames whose denoised latents are fused at every sampler evaluation "
+                        "(17 for the shipped checkpoints).  0 = off: one window of --num_keyframes frames, as before")
+    p.add_argument("--window_overlap", type=int, default=None,
+                   help="(not in the reference script) frames shared by consecutive windows, 0 ... window_frames - 1 (default: window_frames // 2)")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(not in the reference script) draw the samplers' per-step noise from a CPU generator with this seed instead of "
@@ -118,6 +128,30 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
     """Combinations argparse cannot express: an error exit of the parser itself."""
     if args.mask_composite and not args.inpainting_mode:
         p.error("--mask_composite puts the original back outside the mask of --inpainting_mode: give both")
+    if args.window_frames < 0:
+        p.error("--window_frames must be positive (0 = off)")
+    if args.window_overlap is not None and not args.window_frames:
+        p.error("--window_overlap is the overlap of the windows of --window_frames: give both")
+    if args.window_frames and args.window_overlap is not None and not 0 <= args.window_overlap < args.window_frames:
+        p.error("--window_overlap must be in 0 ... window_frames - 1")
+
+
+def windowing(args) -> bool:
+    """Windows are active when the clip has more keyframes than one window holds; otherwise the plain path runs untouched."""
+    return getattr(args, "window_frames", 0) > 0 and args.num_keyframes > args.window_frames
+
+
+def check_windowing(args, with_ref: bool = False) -> None:
+    """Before any GPU work: windows cover the TV2V path only (NotImplementedError otherwise)."""
+    if not windowing(args):
+        return
+    if with_ref:
+        raise NotImplementedError("--window_frames is not available with a reference image (sampling_tv2v_ref.py): one reference image "
+                                  "belongs to the centre frame of one window")
+    if args.config_path and os.path.exists(args.config_path):
+        from ccedit_amd.windows import check_supported
+        with open(args.config_path, "r") as f:
+            check_supported(config=f.read())
 
 
 def parse_args(argv=None):
@@ -274,6 +308,14 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
     def denoiser(inp, sigma, cc):
         return model.denoiser(model.model, inp, sigma, cc)
 
+    if windowing(args):          # N frames through windows of --window_frames: the sampler sees the same closure over the long latent
+        from ccedit_amd.windows import GroupedFirstStage, WindowedDenoiser, check_supported
+        if ref is not None:
+            raise NotImplementedError("--window_frames is not available with a reference image: it belongs to the centre frame of one window")
+        check_supported(cond=c)
+        denoiser = WindowedDenoiser(denoiser, args.window_frames, args.window_overlap, wrapper=model.model)
+        model = GroupedFirstStage(model, args.window_frames)      # (the closure above keeps the engine itself)
+
     inpaint = getattr(args, "inpainting_mode", False)
     if inpaint and mask is None:
         raise NotImplementedError(NO_MASK)
@@ -310,6 +352,9 @@ def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_t
     """sampling_tv2v.py:361-470 for one chunk: sample, decode and — with --mask_composite and the pixel masks `mask_px` — put the
     original pixels back outside the mask (ccedit_mask_composite)."""
     z = sample_latent(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=prior_type, mask=mask)
+    if windowing(args):
+        from ccedit_amd.windows import GroupedFirstStage
+        model = GroupedFirstStage(model, args.window_frames)
     samples = model.decode_first_stage(z)
     if getattr(args, "mask_composite", False) and mask_px is not None:
         from ccedit_amd import ops
@@ -471,6 +516,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
     for every chunk: keyframes, conditioning, one CFG-doubled batch through the sampler, decode, original / result / control_hint +
     log_info.json."""
     import json
+    check_windowing(args, with_ref)
     from ccedit_amd.parallel import shard_clips
     from scripts.sampling.util import chunk, load_img, load_video_keyframes, model_load_ckpt, perform_save_locally_video
     prompts, video_paths, video_save_paths, ref_paths = expand_jobs(args, with_ref)
@@ -609,6 +655,7 @@ def main():
     torch.set_grad_enabled(False)
     if job_mode(args):
         return run_jobs(args)
+    check_windowing(args)
     from scripts.sampling.util import ResumeLog, save_frames
     model, dev = build_model(args)
     T, h, w = args.num_keyframes, args.H // 8, args.W // 8
