@@ -166,3 +166,12 @@ int cc_mask_composite(const float* result, const float* original, const uint8_t*
 int cc_window_gather(const float* x, float* xw, const int32_t* starts, int32_t W, int32_t BC, int32_t N, int32_t T, int64_t P, hipStream_t s);
 int cc_window_fuse(const float* const* yw, float* out, const int32_t* starts, const float* coef, int32_t W, int32_t BC, int32_t N, int32_t T,
                    int64_t P, hipStream_t s);
+
+// Propagation launchers (propagate.hip); entry points and argument checks in core.cpp
+int cc_prop_pyramid(const uint8_t* rgb, uint8_t* pyr, int32_t F, int32_t H, int32_t W, hipStream_t s);
+int cc_prop_match(const uint8_t* lum, const int32_t* pairs, const int32_t* rank, const int32_t* parent, int32_t* out, int32_t P, int32_t F,
+                  int32_t h, int32_t w, int32_t R, hipStream_t s);
+int cc_prop_warp(const uint8_t* src, const int32_t* vec, const int32_t* pairs, int32_t col, uint8_t* out, int32_t P, int32_t Fsrc, int32_t H,
+                 int32_t W, int32_t C, hipStream_t s);
+int cc_prop_blend(const uint8_t* wE, const uint8_t* wY, const uint8_t* lum, const int32_t* pairs, const int32_t* gtab, const uint8_t* rgb,
+                  const uint8_t* mask, uint8_t* out, int32_t NF, int32_t F, int32_t H, int32_t W, hipStream_t s);

@@ -218,3 +218,55 @@ extern "C" int ccedit_window_fuse(const void* yw, float* out, const int32_t* sta
     if (int rc = window_shape_ok("ccedit_window_fuse", W, B, C, N, T, P)) return rc;
     return cc_window_fuse((const float* const*)yw, out, starts, coef, W, B * C, N, T, P, (hipStream_t)stream);
 }
+
+// ---- propagation of edited keyframes to every source frame (kernels and launchers: propagate.hip).  Everything the host can see is
+// checked here, before any HIP call; the device tables (pairs, rank, g, the block vectors) are held in range by the kernels themselves.
+static int prop_shape_ok(const char* fn, int32_t P, int32_t F, int32_t H, int32_t W) {
+    CC_CHECK_ARG(P >= 1 && P <= 65534 && F >= 1 && F <= 65535, "%s: P=%d pairs (1 ... 65534) over F=%d frames (1 ... 65535)", fn, P, F);
+    CC_CHECK_ARG(H >= 64 && W >= 64 && H % 64 == 0 && W % 64 == 0 && H <= 8192 && W <= 8192,
+                 "%s: frames of %dx%d (H and W multiples of 64, 64 ... 8192: four pyramid levels of 8 x 8 blocks)", fn, H, W);
+    CC_CHECK_ARG((int64_t)F * H * W * 3 < kPixelMax * 4 && (int64_t)P * H * W * 3 < kPixelMax * 4, "%s: more than 2^33 bytes in one call (P=%d F=%d %dx%d)",
+                 fn, P, F, H, W);
+    return CCEDIT_OK;
+}
+
+extern "C" int ccedit_prop_pyramid(const void* rgb, void* pyr, int32_t F, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(rgb && pyr, "ccedit_prop_pyramid: null pointer");
+    if (int rc = prop_shape_ok("ccedit_prop_pyramid", 1, F, H, W)) return rc;
+    CC_CHECK_ARG(((uintptr_t)rgb & 3) == 0 && ((uintptr_t)pyr & 7) == 0, "ccedit_prop_pyramid: rgb must be 4-byte and pyr 8-byte aligned");
+    return cc_prop_pyramid((const uint8_t*)rgb, (uint8_t*)pyr, F, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_prop_match(const void* pyr, const int32_t* pairs, const int32_t* rank, const int32_t* vec_parent, int32_t* vec_out, int32_t P,
+                                 int32_t F, int32_t H, int32_t W, int32_t level, int32_t radius, void* stream) {
+    CC_CHECK_ARG(pyr && pairs && rank && vec_out, "ccedit_prop_match: null pointer (vec_parent alone may be null: prediction zero)");
+    if (int rc = prop_shape_ok("ccedit_prop_match", P, F, H, W)) return rc;
+    CC_CHECK_ARG(level >= 0 && level <= 3, "ccedit_prop_match: level=%d (0 ... 3)", level);
+    CC_CHECK_ARG(radius >= 1 && radius <= 4, "ccedit_prop_match: radius=%d (1 ... 4)", radius);
+    CC_CHECK_ARG(!vec_parent || level <= 2, "ccedit_prop_match: level 3 is the coarsest, it has no parent vectors");
+    int64_t off = 0;
+    for (int l = 0; l < level; ++l) off += (int64_t)F * (H >> l) * (W >> l);
+    return cc_prop_match((const uint8_t*)pyr + off, pairs, rank, vec_parent, vec_out, P, F, H >> level, W >> level, radius, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_prop_warp(const void* src, const int32_t* vec, const int32_t* pairs, int32_t col, void* out, int32_t P, int32_t Fsrc, int32_t H,
+                                int32_t W, int32_t C, void* stream) {
+    CC_CHECK_ARG(src && vec && pairs && out, "ccedit_prop_warp: null pointer");
+    if (int rc = prop_shape_ok("ccedit_prop_warp", P, Fsrc, H, W)) return rc;
+    CC_CHECK_ARG(C == 1 || C == 3, "ccedit_prop_warp: C=%d channels (1: luma, 3: RGB)", C);
+    CC_CHECK_ARG(col == 1 || col == 2, "ccedit_prop_warp: col=%d (the column of a pair row that names the source frame: 1 or 2)", col);
+    CC_CHECK_ARG(((uintptr_t)out & 3) == 0, "ccedit_prop_warp: out must be 4-byte aligned");
+    return cc_prop_warp((const uint8_t*)src, vec, pairs, col, (uint8_t*)out, P, Fsrc, H, W, C, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_prop_blend(const void* warped_rgb, const void* warped_luma, const void* pyr, const int32_t* pairs, const int32_t* gtab,
+                                 const void* rgb, const void* mask, void* out, int32_t NF, int32_t F, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(warped_rgb && warped_luma && pyr && pairs && gtab && out, "ccedit_prop_blend: null pointer");
+    CC_CHECK_ARG((rgb == nullptr) == (mask == nullptr), "ccedit_prop_blend: rgb and mask come together (the source is put back where the mask is clear)");
+    CC_CHECK_ARG(NF >= 1 && NF <= 32767, "ccedit_prop_blend: NF=%d in-between frames (1 ... 32767)", NF);
+    if (int rc = prop_shape_ok("ccedit_prop_blend", 2 * NF, F, H, W)) return rc;
+    CC_CHECK_ARG((((uintptr_t)warped_rgb | (uintptr_t)out | (uintptr_t)rgb | (uintptr_t)mask) & 3) == 0,
+                 "ccedit_prop_blend: warped_rgb, out, rgb and mask must be 4-byte aligned");
+    return cc_prop_blend((const uint8_t*)warped_rgb, (const uint8_t*)warped_luma, (const uint8_t*)pyr, pairs, gtab, (const uint8_t*)rgb,
+                         (const uint8_t*)mask, (uint8_t*)out, NF, F, H, W, (hipStream_t)stream);
+}

@@ -153,6 +153,14 @@ _SIGS = {
                                        C.c_void_p]),
     "ccedit_window_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int64, C.c_void_p]),
+    # propagation of edited keyframes (csrc/propagate.hip): added within ABI 12, nothing existing changed
+    "ccedit_prop_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_prop_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_prop_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_void_p]),
+    "ccedit_prop_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }
 KTH_WORKSPACE_BYTES_PER_ROW = 4128      # ccedit_kth_values: (prefix, rank) x 4 + 4 x 256 counters, uint32
 

@@ -946,3 +946,98 @@ def window_fuse(ys, starts: torch.Tensor, coef: torch.Tensor, frames: int, out: 
         table.data_ptr(), y.data_ptr(), starts.data_ptr(), coef.data_ptr(), nw, b, c, n, t, h * w, _stream()), "ccedit_window_fuse"),
         (nw, b, c, n, h, w))
     return y
+
+
+# ------------------------------------------------------------------------------------------
+# Propagation of edited keyframes to every source frame (csrc/propagate.hip; plan, tables and the clip loop: ccedit_amd/propagate.py)
+# ------------------------------------------------------------------------------------------
+def _chk_u8(t: torch.Tensor, name: str, dims: int):
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.dim() != dims:
+        raise ValueError(f"{name}: expected a contiguous cuda uint8 tensor of {dims} dimensions, got {t.dtype} {t.device} {tuple(t.shape)} "
+                         f"contiguous={t.is_contiguous()}")
+
+
+def _chk_i32(t: torch.Tensor, name: str, shape):
+    if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected a contiguous cuda int32 tensor {tuple(shape)}, got {t.dtype} {t.device} {tuple(t.shape)}")
+
+
+def prop_pyramid_bytes(f: int, h: int, w: int) -> int:
+    return f * h * w * 85 // 64
+
+
+def prop_level(pyr: torch.Tensor, f: int, h: int, w: int, level: int) -> torch.Tensor:
+    """Level `level` of a pyramid written by prop_pyramid, as a (F, H >> level, W >> level) view."""
+    off = sum(f * (h >> l) * (w >> l) for l in range(level))
+    return pyr[off:off + f * (h >> level) * (w >> level)].view(f, h >> level, w >> level)
+
+
+def prop_pyramid(rgb: torch.Tensor) -> torch.Tensor:
+    """uint8 frames (F, H, W, 3) -> the four luma levels of all frames in one uint8 buffer (prop_level gives the views)."""
+    _chk_u8(rgb, "prop_pyramid", 4)
+    f, h, w, c = rgb.shape
+    assert c == 3, f"prop_pyramid: RGB frames (F, H, W, 3), got {tuple(rgb.shape)}"
+    pyr = torch.empty(prop_pyramid_bytes(f, h, w), dtype=torch.uint8, device=rgb.device)
+    hip.check(hip.lib().ccedit_prop_pyramid(rgb.data_ptr(), pyr.data_ptr(), f, h, w, _stream()), "ccedit_prop_pyramid")
+    return pyr
+
+
+def prop_match(pyr: torch.Tensor, pairs: torch.Tensor, rank: torch.Tensor, parent: Optional[torch.Tensor], frames: int, h: int, w: int,
+               level: int, radius: int) -> torch.Tensor:
+    """One level of the block matching for all pairs (P, 4) of the call -> int32 vectors (P, (h >> level) / 8, (w >> level) / 8, 2)."""
+    _chk_u8(pyr, "prop_match", 1)
+    assert pyr.numel() == prop_pyramid_bytes(frames, h, w), f"prop_match: a pyramid of {frames} frames {h}x{w} has {prop_pyramid_bytes(frames, h, w)} bytes"
+    p = pairs.shape[0]
+    _chk_i32(pairs, "prop_match: pairs", (p, 4))
+    _chk_i32(rank, "prop_match: rank", ((2 * radius + 1) ** 2,))
+    nby, nbx = (h >> level) // 8, (w >> level) // 8
+    if parent is not None:
+        _chk_i32(parent, "prop_match: parent", (p, nby // 2, nbx // 2, 2))
+    out = torch.empty((p, nby, nbx, 2), dtype=torch.int32, device=pyr.device)
+    hip.check(hip.lib().ccedit_prop_match(pyr.data_ptr(), pairs.data_ptr(), rank.data_ptr(), None if parent is None else parent.data_ptr(),
+                                          out.data_ptr(), p, frames, h, w, level, radius, _stream()), "ccedit_prop_match")
+    return out
+
+
+def prop_warp(src: torch.Tensor, vec: torch.Tensor, pairs: torch.Tensor, col: int) -> torch.Tensor:
+    """src uint8 (Fsrc, H, W, 3) or (Fsrc, H, W) warped along the level-0 block vectors `vec` (P, H / 8, W / 8, 2), the source frame of
+    pair p taken from column `col` of its row -> uint8 (P, H, W[, 3])."""
+    if src.dim() not in (3, 4) or (src.dim() == 4 and src.shape[3] != 3):
+        raise ValueError(f"prop_warp: frames (F, H, W, 3) or (F, H, W), got {tuple(src.shape)}")
+    _chk_u8(src, "prop_warp", src.dim())
+    fs, h, w = src.shape[:3]
+    p = pairs.shape[0]
+    _chk_i32(pairs, "prop_warp: pairs", (p, 4))
+    _chk_i32(vec, "prop_warp: vec", (p, h // 8, w // 8, 2))
+    out = torch.empty((p,) + tuple(src.shape[1:]), dtype=torch.uint8, device=src.device)
+    hip.check(hip.lib().ccedit_prop_warp(src.data_ptr(), vec.data_ptr(), pairs.data_ptr(), int(col), out.data_ptr(), p, fs, h, w,
+                                         3 if src.dim() == 4 else 1, _stream()), "ccedit_prop_warp")
+    return out
+
+
+def prop_blend(warped_rgb: torch.Tensor, warped_luma: torch.Tensor, pyr: torch.Tensor, pairs: torch.Tensor, gtab: torch.Tensor, frames: int,
+               rgb: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The two warped keyframes (2 NF, H, W, 3) of every in-between frame, weighted by distance and by the confidence of the warped source
+    lumas (2 NF, H, W) against the frame's own luma (level 0 of `pyr`) -> uint8 (NF, H, W, 3).  With `rgb` (F, H, W, 3) and `mask`
+    (F, H, W): the source pixel where the frame's own mask is clear (< 128)."""
+    _chk_u8(warped_rgb, "prop_blend: warped_rgb", 4)
+    p, h, w, _ = warped_rgb.shape
+    assert p % 2 == 0 and warped_rgb.shape[3] == 3, f"prop_blend: two warped keyframes per frame, got {tuple(warped_rgb.shape)}"
+    _chk_u8(warped_luma, "prop_blend: warped_luma", 3)
+    assert tuple(warped_luma.shape) == (p, h, w), f"prop_blend: warped_luma {tuple(warped_luma.shape)} for warped_rgb {tuple(warped_rgb.shape)}"
+    _chk_u8(pyr, "prop_blend: pyr", 1)
+    assert pyr.numel() == prop_pyramid_bytes(frames, h, w)
+    _chk_i32(pairs, "prop_blend: pairs", (p, 4))
+    _chk_i32(gtab, "prop_blend: gtab", (256,))
+    if (rgb is None) != (mask is None):
+        raise ValueError("prop_blend: rgb and mask come together")
+    if rgb is not None:
+        _chk_u8(rgb, "prop_blend: rgb", 4)
+        _chk_u8(mask, "prop_blend: mask", 3)
+        assert tuple(rgb.shape) == (frames, h, w, 3) and tuple(mask.shape) == (frames, h, w), \
+            f"prop_blend: rgb {tuple(rgb.shape)} / mask {tuple(mask.shape)} for {frames} frames {h}x{w}"
+    out = torch.empty((p // 2, h, w, 3), dtype=torch.uint8, device=warped_rgb.device)
+    hip.check(hip.lib().ccedit_prop_blend(warped_rgb.data_ptr(), warped_luma.data_ptr(), pyr.data_ptr(), pairs.data_ptr(), gtab.data_ptr(),
+                                          None if rgb is None else rgb.data_ptr(), None if mask is None else mask.data_ptr(), out.data_ptr(),
+                                          p // 2, frames, h, w, _stream()), "ccedit_prop_blend")
+    return out

@@ -505,6 +505,41 @@ int ccedit_window_gather(const float* x, float* xw, const int32_t* starts, int32
 int ccedit_window_fuse(const void* yw, float* out, const int32_t* starts, const float* coef, int32_t W, int32_t B, int32_t C, int32_t N,
                        int32_t T, int64_t P, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Propagation (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  Full-frame-rate output: the edited
+ * keyframes are carried to every source frame between them along motion estimated on the source frames (ccedit_amd/propagate.py:
+ * plan, tables, propagate_clip; `--propagate`).  Kernels: csrc/propagate.hip.  Everything is integer arithmetic on bytes and equals
+ * tests/_propagate_numpy.py bit for bit.  Frames are uint8 [frames][H][W][3] (RGB) or [frames][H][W] (luma, masks), H and W multiples of
+ * 64.  A PAIR is a row of four int32 on the device: (f, k, e, dist) — the frame that is produced, the keyframe it is matched against
+ * (both numbers of source frames), the ordinal of that keyframe among the edited keyframes, and the weight of this side in the blend
+ * (the distance to the OTHER keyframe).  The pairs of in-between frame j are rows 2 j (towards the earlier keyframe) and 2 j + 1.
+ * Indices read from a pair are clamped into their tensor, `dist` into 1 ... 255, table entries into their range, block vectors into
+ * +-32 (as a parent) / +-4096 (in the warp): no device table can take an access outside a tensor.
+ *
+ * ccedit_prop_pyramid: rgb [F][H][W][3] -> pyr: luma (77 R + 150 G + 29 B + 128) >> 8 as level 0 [F][H][W], then levels 1 ... 3, each the
+ *   rounded mean (p00 + p01 + p10 + p11 + 2) >> 2 of the level before, [F][H >> l][W >> l], one after the other: F H W 85 / 64 bytes.
+ *   rgb 4-byte, pyr 8-byte aligned.
+ * ccedit_prop_match: one level, all P pairs in one launch.  Blocks are 8 x 8, the compared patch 16 x 16 (a 4-pixel apron, coordinates
+ *   clamped).  Candidates (dy, dx) in +-radius (1 ... 4) around twice the vector of the parent block (by >> 1, bx >> 1) of vec_parent
+ *   (null: around zero); the minimum of SAD * 256 + rank[(dy + radius) (2 radius + 1) + dx + radius] wins.  vec_out / vec_parent: int32
+ *   [P][(H >> level) / 8][(W >> level) / 8][2] = (dy, dx), prediction included.
+ * ccedit_prop_warp: out[p] = src[pair p, column col] sampled at 16 (y, x) + flow, clamped, bilinear with 4-bit fractions,
+ *   (sum w p + 128) >> 8; flow (1/16 pixel) = the fixed-point bilinear interpolation of the level-0 block vectors `vec` around the
+ *   block centres (t = 2 x - 7, blocks t >> 4 and its successor clamped, weights 16 - (t & 15) and t & 15, (sum + 8) >> 4).
+ *   src [Fsrc][H][W][C], out [P][H][W][C], C = 3 or 1; col = 1 (source frames) or 2 (edited keyframes).  out 4-byte aligned.
+ * ccedit_prop_blend: for in-between frame j: e = min(255, (5 x 5 edge-replicated box sum of |warped_luma[2 j + s] - luma of frame f| +
+ *   12) / 25) per side s, w_s = dist_s gtab[e_s] (gtab: int32 [256], entries 1 ... 4096), out[j] = (w_0 A + w_1 B + (w_0 + w_1) / 2) /
+ *   (w_0 + w_1) per channel of warped_rgb[2 j], [2 j + 1].  With rgb [F][H][W][3] and mask [F][H][W] (both or neither): the source pixel
+ *   where frame f's mask byte is < 128.  warped_rgb [2 NF][H][W][3], warped_luma [2 NF][H][W], pyr as written by ccedit_prop_pyramid.
+ */
+int ccedit_prop_pyramid(const void* rgb, void* pyr, int32_t F, int32_t H, int32_t W, void* stream);
+int ccedit_prop_match(const void* pyr, const int32_t* pairs, const int32_t* rank, const int32_t* vec_parent, int32_t* vec_out, int32_t P, int32_t F,
+                      int32_t H, int32_t W, int32_t level, int32_t radius, void* stream);
+int ccedit_prop_warp(const void* src, const int32_t* vec, const int32_t* pairs, int32_t col, void* out, int32_t P, int32_t Fsrc, int32_t H, int32_t W,
+                     int32_t C, void* stream);
+int ccedit_prop_blend(const void* warped_rgb, const void* warped_luma, const void* pyr, const int32_t* pairs, const int32_t* gtab, const void* rgb,
+                      const void* mask, void* out, int32_t NF, int32_t F, int32_t H, int32_t W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

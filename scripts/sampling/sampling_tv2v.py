@@ -29,6 +29,9 @@ one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everyt
 --noise_seed, --gpu_io — runs on the long latent as on a short one, first-stage encode / decode in groups of at most T frames.
 Launched under torch.distributed (RANK / WORLD_SIZE), the chunks are dealt round-robin to the ranks (BASELINE.json config 5:
 independent clips, one per GPU, no collective — ccedit_amd.parallel.shard_clips).
+`--propagate` (job mode, --save_type gif) adds the frames BETWEEN the keyframes: every source frame from the first to the last keyframe
+gets an edited frame, the two neighbouring edited keyframes carried along motion estimated on the source (ccedit_amd/propagate.py,
+csrc/propagate.hip), written to <save_path>/<basemodel>/result_full/gif/ at --original_fps; log_info.json gains `fullrate_paths`.
 """
 from __future__ import annotations
 
@@ -108,6 +111,11 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                         "(17 for the shipped checkpoints).  0 = off: one window of --num_keyframes frames, as before")
     p.add_argument("--window_overlap", type=int, default=None,
                    help="(not in the reference script) frames shared by consecutive windows, 0 ... window_frames - 1 (default: window_frames // 2)")
+    p.add_argument("--propagate", action="store_true",
+                   help="(not in the reference script) full-frame-rate output: after a clip's keyframes are saved, every source frame from the "
+                        "first to the last keyframe gets an edited frame — the two neighbouring edited keyframes carried along the source's "
+                        "motion (ccedit_amd/propagate.py, csrc/propagate.hip) — written to <save_path>/result_full/ at --original_fps.  "
+                        "Needs a video source (job mode) and --save_type gif")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(not in the reference script) draw the samplers' per-step noise from a CPU generator with this seed instead of "
@@ -134,6 +142,12 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--window_overlap is the overlap of the windows of --window_frames: give both")
     if args.window_frames and args.window_overlap is not None and not 0 <= args.window_overlap < args.window_frames:
         p.error("--window_overlap must be in 0 ... window_frames - 1")
+    if getattr(args, "propagate", False):
+        if not job_mode(args):
+            p.error("--propagate carries the edit to the frames between the keyframes of a video: give --prompt with --video_path "
+                    "(or --prompt_listpath / --videos_directory / --json_path)")
+        if args.save_type != "gif":
+            p.error(f"--propagate writes result_full/ as gif: add --save_type gif (got {args.save_type})")
 
 
 def windowing(args) -> bool:
@@ -152,6 +166,46 @@ def check_windowing(args, with_ref: bool = False) -> None:
         from ccedit_amd.windows import check_supported
         with open(args.config_path, "r") as f:
             check_supported(config=f.read())
+
+
+def check_propagate(args, video_paths) -> None:
+    """Before any GPU work: --propagate needs strictly increasing keyframe indices on every clip (ValueError from ccedit_amd.propagate.plan —
+    keyframe_indices' linspace fallback on a video that is too short repeats frames).  Clips that cannot be counted here (no decoder)
+    are reported where they fail to load, as always."""
+    if not getattr(args, "propagate", False):
+        return
+    from ccedit_amd.propagate import plan
+    from scripts.sampling.util import count_video_frames, keyframe_indices
+    for v in dict.fromkeys(video_paths):
+        video = resolve_video(v)
+        if os.path.isdir(video) or (video.endswith(".gif") and os.path.exists(video)):
+            n = count_video_frames(video)
+            try:
+                plan(keyframe_indices(n, args.original_fps, args.target_fps, args.num_keyframes), n)
+            except ValueError as e:
+                raise ValueError(f"--propagate: {video}: {e}") from e
+
+
+def propagate_chunk(args, cvideos, samples, dev, save_path):
+    """--propagate for one chunk: per clip all source frames on the device, the edited keyframes as the uint8 frames result/ holds
+    (frames_to_u8 without rounding of the decoder output), propagate_clip, <save_path>/result_full/gif/animation-XXXX.gif at
+    --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
+    from ccedit_amd import ops
+    from ccedit_amd.propagate import propagate_clip
+    from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask, save_gif_u8
+    edited = ops.frames_to_u8(samples.float().contiguous(), rounding=False, unit_range=False)           # (bs, T, H, W, 3)
+    paths = []
+    for b, v in enumerate(cvideos):
+        source = load_video_frames_u8(resolve_video(v), (args.H, args.W), dev)
+        n_all = source.shape[0]
+        masks = None
+        if args.inpainting_mode and args.mask_composite:
+            masks = load_video_mask(find_mask(args, v), args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all,
+                                    device=dev, all_frames=True).contiguous()
+        idx = keyframe_indices(n_all, args.original_fps, args.target_fps, args.num_keyframes)
+        full = propagate_clip(source, idx, edited[b], masks=masks)
+        paths.append(save_gif_u8(os.path.join(save_path, "result_full"), full.cpu().numpy(), args.original_fps))
+    return paths
 
 
 def parse_args(argv=None):
@@ -521,6 +575,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
     from scripts.sampling.util import chunk, load_img, load_video_keyframes, model_load_ckpt, perform_save_locally_video
     prompts, video_paths, video_save_paths, ref_paths = expand_jobs(args, with_ref)
     num_samples, batch_size = args.num_samples, args.batch_size
+    check_propagate(args, video_paths)
     print("\nNumber of prompts: {}".format(len(prompts)))
     print("Generate {} samples for each prompt".format(num_samples))
     rep = lambda lst: [item for item in lst for _ in range(num_samples)]
@@ -623,6 +678,9 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 m01 = (mask_px >= 128).float()[:, None].expand(-1, 3, -1, -1, -1).contiguous()
                 perform_save_locally_video(os.path.join(save_path, "mask"), m01 * 2.0 - 1.0 if io else m01, args.target_fps, args.save_type,
                                            save_grid=False, **io)
+            if args.propagate:
+                log_info.setdefault("fullrate_paths", [])
+                log_info["fullrate_paths"] += propagate_chunk(args, cvideos, samples, dev, save_path)
             print("Saved samples to {}. Enjoy.".format(save_path))
             log_info["video_paths"] += cvideos
             log_info["keyframes_paths"] += keyframes_paths

@@ -347,6 +347,46 @@ def HWC3(x: np.ndarray) -> np.ndarray:
     return (color * alpha + 255.0 * (1.0 - alpha)).clip(0, 255).astype(np.uint8)
 
 
+def _decode_gif_u8(video_path: str) -> np.ndarray:
+    """All frames of a .gif -> uint8 (N, h, w, 3) on the host (transparency blended on white, as HWC3)."""
+    from PIL import Image, ImageSequence
+    return np.stack([HWC3(np.array(fr.convert("RGBA") if fr.mode == "P" and "transparency" in fr.info else fr.convert("RGB")))
+                     for fr in ImageSequence.Iterator(Image.open(video_path))], axis=0)
+
+
+def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
+    """(not in the reference) ALL frames of what load_video_keyframes reads -> uint8 (F, H, W, 3) on `device` at size = (H, W): the
+    source side of --propagate.  Decoding stays on the host (Pillow); the frames reach the output size by the routes of the keyframes —
+    image files by Pillow's 8-bit bicubic (ops.resize_u8_pil), .gif frames by the fp32 bicubic of F.interpolate and then the nearest
+    byte (ops.resize_bicubic, ops.frames_to_u8 with rounding)."""
+    from ccedit_amd import ops
+    assert device is not None and size and len(size) == 2, "load_video_frames_u8 works on a device, size should be (H, W)"
+    if os.path.isdir(video_path):
+        frames = [_decode_rgb_u8(os.path.join(video_path, f)) for f in sorted(os.listdir(video_path))]
+        groups = [np.stack(frames, axis=0)] if len({f.shape for f in frames}) == 1 else [f[None] for f in frames]
+        out = [ops.resize_u8_pil(torch.from_numpy(np.ascontiguousarray(g)).to(device), size) for g in groups]
+        return out[0] if len(out) == 1 else torch.cat(out, dim=0)
+    if video_path.endswith(".gif"):
+        x = _frames_to_device(list(_decode_gif_u8(video_path)), None, device).contiguous()       # (F, 3, h, w) in [-1, 1]
+        x = ops.resize_bicubic(x, size)
+        return ops.frames_to_u8(x.permute(1, 0, 2, 3)[None].contiguous(), rounding=True)[0]
+    if video_path.endswith(".mp4"):
+        raise NotImplementedError("mp4 decoding needs decord / cv2 / imageio-ffmpeg, none of which is installed; "
+                                  "extract the frames to a directory of images (or a .gif) instead")
+    raise ValueError("Unsupported video format. Only support dirctory, .mp4 and .gif.")
+
+
+def save_gif_u8(save_path: str, frames: np.ndarray, fps: int) -> str:
+    """uint8 frames (T, H, W, 3) -> <save_path>/gif/animation-XXXX.gif, numbered and written like perform_save_locally_video's."""
+    from PIL import Image
+    os.makedirs(os.path.join(save_path, "gif"), exist_ok=True)
+    count = len(os.listdir(os.path.join(save_path, "gif")))
+    imgs = [Image.fromarray(f) for f in frames]
+    savepath = os.path.join(save_path, "gif", f"animation-{count:04}.gif")
+    imgs[0].save(savepath, save_all=True, append_images=imgs[1:], duration=int(round(1000.0 / fps)), loop=0)
+    return savepath
+
+
 def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None,
                          device=None) -> torch.Tensor:
     """util.py:689-762: directory of frame images or a .gif -> keyframes (T, 3, H, W) in [-1, 1].
@@ -362,9 +402,7 @@ def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, nu
             return _frames_to_device([_decode_rgb_u8(os.path.join(video_path, files[i])) for i in idx], size, device)
         return torch.cat([load_img(os.path.join(video_path, files[i]), size) for i in idx], dim=0)
     if video_path.endswith(".gif"):
-        from PIL import Image, ImageSequence
-        frames = np.stack([HWC3(np.array(fr.convert("RGBA") if fr.mode == "P" and "transparency" in fr.info else fr.convert("RGB")))
-                           for fr in ImageSequence.Iterator(Image.open(video_path))], axis=0)
+        frames = _decode_gif_u8(video_path)
         if device is not None:
             from ccedit_amd import ops
             frames = frames[keyframe_indices(frames.shape[0], original_fps, target_fps, num_keyframes)]
@@ -397,7 +435,7 @@ _MASK_IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".tif", ".tiff")
 
 
 def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None, num_allframes: int = None,
-                    device=None) -> torch.Tensor:
+                    device=None, all_frames: bool = False) -> torch.Tensor:
     """The edit mask of a clip -> uint8 (T, H, W) holding 0 (keep the original) or 255 (edit): the reference's
     x = x * mask + img_orig * (1 - mask) with white = 1.  (The reference leaves the mask to the user: sampling_tv2v.py:385-407.)
     mask_path: what load_video_keyframes accepts — a directory of images or a .gif, one mask per frame of the VIDEO: `num_allframes`
@@ -405,7 +443,9 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
     ONE image file, used for every keyframe.  Any image mode is taken through its luminance (`convert("L")`); a value >= 128 is white.
     Resize to size = (H, W) is nearest-neighbour on the binarised mask, src = floor((dst + 0.5) * in / out) (Pillow's NEAREST, its
     running sum in double included: ccedit_amd/packing.py pil_nearest_index).  device=None: Pillow on the host.  With a device the
-    binarised keyframe masks are uploaded once and gathered there (ccedit_mask_resize_nearest): identical bytes."""
+    binarised keyframe masks are uploaded once and gathered there (ccedit_mask_resize_nearest): identical bytes.
+    all_frames (--propagate): the masks of ALL frames of the video, (num_allframes, H, W), instead of the keyframes'; one image file is
+    repeated num_allframes times (which must then be given)."""
     from PIL import Image, ImageSequence
     if size:
         assert len(size) == 2, "size should be (H, W)"
@@ -425,8 +465,15 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
         n, pick = None, lambda i: one
     else:
         raise ValueError(f"Unsupported mask format: {mask_path}. Only support directory, .gif and one image file {_MASK_IMAGE_EXT}.")
+    if all_frames and n is None and num_allframes is None:
+        raise ValueError("load_video_mask(all_frames=True) of one image needs num_allframes")
     if n is None:
-        masks = [pick(0)] * num_keyframes
+        masks = [pick(0)] * (num_allframes if all_frames else num_keyframes)
+    elif all_frames:
+        if num_allframes is not None and n != num_allframes:
+            raise ValueError(f"mask {mask_path} has {n} frames, the video has {num_allframes}: a mask sequence needs one mask per frame "
+                             "(or give one image for all frames)")
+        masks = [pick(i) for i in range(n)]
     else:
         if num_allframes is not None and n != num_allframes:
             raise ValueError(f"mask {mask_path} has {n} frames, the video has {num_allframes}: a mask sequence needs one mask per frame "
