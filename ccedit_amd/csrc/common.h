@@ -175,3 +175,11 @@ int cc_prop_warp(const uint8_t* src, const int32_t* vec, const int32_t* pairs, i
                  int32_t W, int32_t C, hipStream_t s);
 int cc_prop_blend(const uint8_t* wE, const uint8_t* wY, const uint8_t* lum, const int32_t* pairs, const int32_t* gtab, const uint8_t* rgb,
                   const uint8_t* mask, uint8_t* out, int32_t NF, int32_t F, int32_t H, int32_t W, hipStream_t s);
+
+// Motion-JPEG launchers (mjpeg.hip); entry points and argument checks in core.cpp
+int64_t cc_mjpeg_segment_bytes(int32_t W);
+int cc_mjpeg_transform(const uint8_t* frames, const int32_t* tab, int16_t* coef, int32_t N, int32_t H, int32_t W, int32_t quality, hipStream_t s);
+int cc_mjpeg_entropy(const int16_t* coef, const int32_t* tab, uint8_t* scratch, int32_t* seg_len, int32_t N, int32_t H, int32_t W, hipStream_t s);
+int cc_mjpeg_pack_scan(const int32_t* seg_len, int64_t* seg_off, int32_t* frame_bytes, int32_t N, int32_t H, int32_t W, int32_t hdr_len, hipStream_t s);
+int cc_mjpeg_pack(const uint8_t* scratch, const int32_t* seg_len, const int64_t* seg_off, const uint8_t* header, uint8_t* out, int32_t N, int32_t H,
+                  int32_t W, int32_t hdr_len, int64_t out_bytes, hipStream_t s);

@@ -270,3 +270,63 @@ extern "C" int ccedit_prop_blend(const void* warped_rgb, const void* warped_luma
     return cc_prop_blend((const uint8_t*)warped_rgb, (const uint8_t*)warped_luma, (const uint8_t*)pyr, pairs, gtab, (const uint8_t*)rgb,
                          (const uint8_t*)mask, (uint8_t*)out, NF, F, H, W, (hipStream_t)stream);
 }
+
+// ---- Motion-JPEG (kernels and launchers: mjpeg.hip).  Everything the host can see is checked here, before any HIP call; the device
+// tables (constants, segment lengths and offsets) are held in range by the kernels themselves.
+static int mjpeg_shape_ok(const char* fn, int32_t N, int32_t H, int32_t W) {
+    CC_CHECK_ARG(N >= 1, "%s: N=%d frames (N >= 1)", fn, N);
+    CC_CHECK_ARG(H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0 && H <= 65520 && W <= 65520,
+                 "%s: frames of %dx%d (H and W multiples of 16, 16 ... 65520: 4:2:0 MCUs)", fn, H, W);
+    CC_CHECK_ARG((int64_t)N * (H / 16) * ((W / 16 + 3) / 4) < kPixelMax && (int64_t)N * H * W * 3 < kPixelMax * 4,
+                 "%s: N=%d frames of %dx%d are more than one call takes (2^33 bytes, 2^31 strips of four MCUs)", fn, N, H, W);
+    return CCEDIT_OK;
+}
+
+extern "C" int64_t ccedit_mjpeg_segment_bytes(int32_t W) {
+    if (W < 16 || W % 16 != 0 || W > 65520) {
+        cc_set_error("ccedit_mjpeg_segment_bytes: W=%d (a multiple of 16, 16 ... 65520)", W);
+        return CCEDIT_EINVAL;
+    }
+    return cc_mjpeg_segment_bytes(W);
+}
+
+extern "C" int ccedit_mjpeg_transform(const void* frames, const int32_t* tables, void* coef, int32_t N, int32_t H, int32_t W, int32_t quality,
+                                      void* stream) {
+    CC_CHECK_ARG(frames && tables && coef, "ccedit_mjpeg_transform: null pointer (frames, tables and coef are required)");
+    if (int rc = mjpeg_shape_ok("ccedit_mjpeg_transform", N, H, W)) return rc;
+    CC_CHECK_ARG(quality >= 1 && quality <= 100, "ccedit_mjpeg_transform: quality=%d (1 ... 100)", quality);
+    CC_CHECK_ARG((((uintptr_t)frames | (uintptr_t)coef) & 15) == 0 && ((uintptr_t)tables & 3) == 0,
+                 "ccedit_mjpeg_transform: frames and coef must be 16-byte aligned, tables 4-byte");
+    return cc_mjpeg_transform((const uint8_t*)frames, tables, (int16_t*)coef, N, H, W, quality, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_mjpeg_entropy(const void* coef, const int32_t* tables, void* segments, int32_t* seg_len, int32_t N, int32_t H, int32_t W,
+                                    void* stream) {
+    CC_CHECK_ARG(coef && tables && segments && seg_len, "ccedit_mjpeg_entropy: null pointer");
+    if (int rc = mjpeg_shape_ok("ccedit_mjpeg_entropy", N, H, W)) return rc;
+    CC_CHECK_ARG(((uintptr_t)coef & 15) == 0 && (((uintptr_t)tables | (uintptr_t)seg_len) & 3) == 0,
+                 "ccedit_mjpeg_entropy: coef must be 16-byte aligned, tables and seg_len 4-byte");
+    return cc_mjpeg_entropy((const int16_t*)coef, tables, (uint8_t*)segments, seg_len, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_mjpeg_pack_scan(const int32_t* seg_len, int64_t* seg_off, int32_t* frame_bytes, int32_t N, int32_t H, int32_t W,
+                                      int32_t hdr_len, void* stream) {
+    CC_CHECK_ARG(seg_len && seg_off && frame_bytes, "ccedit_mjpeg_pack_scan: null pointer");
+    if (int rc = mjpeg_shape_ok("ccedit_mjpeg_pack_scan", N, H, W)) return rc;
+    CC_CHECK_ARG(hdr_len >= 2 && hdr_len <= 65536, "ccedit_mjpeg_pack_scan: hdr_len=%d bytes of frame header (2 ... 65536)", hdr_len);
+    CC_CHECK_ARG((((uintptr_t)seg_len | (uintptr_t)frame_bytes) & 3) == 0 && ((uintptr_t)seg_off & 7) == 0,
+                 "ccedit_mjpeg_pack_scan: seg_len and frame_bytes must be 4-byte aligned, seg_off 8-byte");
+    return cc_mjpeg_pack_scan(seg_len, seg_off, frame_bytes, N, H, W, hdr_len, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_mjpeg_pack(const void* segments, const int32_t* seg_len, const int64_t* seg_off, const void* header, void* out, int32_t N,
+                                 int32_t H, int32_t W, int32_t hdr_len, int64_t out_bytes, void* stream) {
+    CC_CHECK_ARG(segments && seg_len && seg_off && header && out, "ccedit_mjpeg_pack: null pointer");
+    if (int rc = mjpeg_shape_ok("ccedit_mjpeg_pack", N, H, W)) return rc;
+    CC_CHECK_ARG(hdr_len >= 2 && hdr_len <= 65536, "ccedit_mjpeg_pack: hdr_len=%d bytes of frame header (2 ... 65536)", hdr_len);
+    CC_CHECK_ARG(out_bytes >= (int64_t)N * (hdr_len + 2 * (int64_t)(H / 16)), "ccedit_mjpeg_pack: out_bytes=%lld is less than the headers and markers "
+                 "of N=%d frames take", (long long)out_bytes, N);
+    CC_CHECK_ARG(((uintptr_t)seg_len & 3) == 0 && ((uintptr_t)seg_off & 7) == 0, "ccedit_mjpeg_pack: seg_len must be 4-byte aligned, seg_off 8-byte");
+    return cc_mjpeg_pack((const uint8_t*)segments, seg_len, seg_off, (const uint8_t*)header, (uint8_t*)out, N, H, W, hdr_len, out_bytes,
+                         (hipStream_t)stream);
+}

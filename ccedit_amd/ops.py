@@ -1041,3 +1041,64 @@ def prop_blend(warped_rgb: torch.Tensor, warped_luma: torch.Tensor, pyr: torch.T
                                           None if rgb is None else rgb.data_ptr(), None if mask is None else mask.data_ptr(), out.data_ptr(),
                                           p // 2, frames, h, w, _stream()), "ccedit_prop_blend")
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# Motion-JPEG output (csrc/mjpeg.hip; constants, header, container and the frame loop: ccedit_amd/mjpeg.py)
+# ------------------------------------------------------------------------------------------
+def mjpeg_segment_bytes(w: int) -> int:
+    n = int(hip.lib().ccedit_mjpeg_segment_bytes(int(w)))
+    if n < 0:
+        hip.check(n, "ccedit_mjpeg_segment_bytes")
+    return n
+
+
+def mjpeg_transform(frames: torch.Tensor, tables: torch.Tensor, quality: int) -> torch.Tensor:
+    """uint8 frames (N, H, W, 3) -> quantised coefficients int16 (N, H / 16, W / 16, 6, 64): per MCU Y00 Y01 Y10 Y11 Cb Cr, zigzag order."""
+    _chk_u8(frames, "mjpeg_transform", 4)
+    n, h, w, c = frames.shape
+    assert c == 3, f"mjpeg_transform: RGB frames (N, H, W, 3), got {tuple(frames.shape)}"
+    _chk_i32(tables, "mjpeg_transform: tables", (816,))
+    coef = torch.empty((n, h // 16, w // 16, 6, 64), dtype=torch.int16, device=frames.device)
+    hip.check(hip.lib().ccedit_mjpeg_transform(frames.data_ptr(), tables.data_ptr(), coef.data_ptr(), n, h, w, int(quality), _stream()),
+              "ccedit_mjpeg_transform")
+    return coef
+
+
+def mjpeg_entropy(coef: torch.Tensor, tables: torch.Tensor):
+    """coefficients (N, MR, MC, 6, 64) -> (segments uint8 (N * MR, segment_bytes), seg_len int32 (N * MR,)): one restart interval per
+    MCU row, stuffed and padded."""
+    if coef.dtype != torch.int16 or not coef.is_cuda or not coef.is_contiguous() or coef.dim() != 5 or tuple(coef.shape[3:]) != (6, 64):
+        raise ValueError(f"mjpeg_entropy: expected contiguous cuda int16 coefficients (N, H / 16, W / 16, 6, 64), got {coef.dtype} {tuple(coef.shape)}")
+    _chk_i32(tables, "mjpeg_entropy: tables", (816,))
+    n, mr, mc = coef.shape[:3]
+    segments = torch.empty((n * mr, mjpeg_segment_bytes(mc * 16)), dtype=torch.uint8, device=coef.device)
+    seg_len = torch.empty((n * mr,), dtype=torch.int32, device=coef.device)
+    hip.check(hip.lib().ccedit_mjpeg_entropy(coef.data_ptr(), tables.data_ptr(), segments.data_ptr(), seg_len.data_ptr(), n, mr * 16, mc * 16,
+                                             _stream()), "ccedit_mjpeg_entropy")
+    return segments, seg_len
+
+
+def mjpeg_pack_scan(seg_len: torch.Tensor, frames: int, h: int, w: int, hdr_len: int):
+    """-> (seg_off int64 (N * MR,), frame_bytes int32 (N,)): where every segment starts in the packed output, and each frame's size."""
+    _chk_i32(seg_len, "mjpeg_pack_scan: seg_len", (frames * (h // 16),))
+    seg_off = torch.empty((frames * (h // 16),), dtype=torch.int64, device=seg_len.device)
+    frame_bytes = torch.empty((frames,), dtype=torch.int32, device=seg_len.device)
+    hip.check(hip.lib().ccedit_mjpeg_pack_scan(seg_len.data_ptr(), seg_off.data_ptr(), frame_bytes.data_ptr(), frames, h, w, int(hdr_len), _stream()),
+              "ccedit_mjpeg_pack_scan")
+    return seg_off, frame_bytes
+
+
+def mjpeg_pack(segments: torch.Tensor, seg_len: torch.Tensor, seg_off: torch.Tensor, header: torch.Tensor, frames: int, h: int, w: int,
+               out_bytes: int) -> torch.Tensor:
+    """-> uint8 (out_bytes,): the frames back to back, each header + segments separated by RSTn + EOI."""
+    _chk_u8(segments, "mjpeg_pack: segments", 2)
+    _chk_u8(header, "mjpeg_pack: header", 1)
+    assert tuple(segments.shape) == (frames * (h // 16), mjpeg_segment_bytes(w)), f"mjpeg_pack: segments {tuple(segments.shape)}"
+    _chk_i32(seg_len, "mjpeg_pack: seg_len", (frames * (h // 16),))
+    if seg_off.dtype != torch.int64 or not seg_off.is_cuda or not seg_off.is_contiguous() or tuple(seg_off.shape) != tuple(seg_len.shape):
+        raise ValueError(f"mjpeg_pack: seg_off: expected a contiguous cuda int64 tensor {tuple(seg_len.shape)}, got {seg_off.dtype} {tuple(seg_off.shape)}")
+    out = torch.empty((int(out_bytes),), dtype=torch.uint8, device=segments.device)
+    hip.check(hip.lib().ccedit_mjpeg_pack(segments.data_ptr(), seg_len.data_ptr(), seg_off.data_ptr(), header.data_ptr(), out.data_ptr(), frames, h, w,
+                                          header.numel(), int(out_bytes), _stream()), "ccedit_mjpeg_pack")
+    return out

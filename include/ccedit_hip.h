@@ -540,6 +540,36 @@ int ccedit_prop_warp(const void* src, const int32_t* vec, const int32_t* pairs, 
 int ccedit_prop_blend(const void* warped_rgb, const void* warped_luma, const void* pyr, const int32_t* pairs, const int32_t* gtab, const void* rgb,
                       const void* mask, void* out, int32_t NF, int32_t F, int32_t H, int32_t W, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Motion-JPEG (added without an ABI bump: five new functions, CCEDIT_ABI_VERSION stays 12).  `--save_type mjpeg`: uint8 frames
+ * [N][H][W][3] on the device (what ccedit_frames_to_u8 writes) -> one baseline JPEG per frame (ITU-T T.81: sequential DCT, 8 bit,
+ * YCbCr 4:2:0, MCU 16 x 16, restart interval = one MCU row = one SEGMENT), ccedit_amd/mjpeg.py: constants, header, container.
+ * Kernels: csrc/mjpeg.hip.  Everything is integer arithmetic and equals tests/_mjpeg_numpy.py byte for byte.  H and W are multiples
+ * of 16, 16 ... 65520.  `tables`: int32 [816] from ccedit_amd/mjpeg.py (table_array: [0] base quantisation tables 2 x 64 row-major,
+ * [128] zigzag, [192] FDCT matrix 8 x 8 at 13 bits, [256] nine colour factors at 16 bits, [272] DC codes 2 x 16 by size, [304] AC codes
+ * 2 x 256 by run << 4 | size; a code is code << 8 | length).  Values read from it are held in range by the kernels (indices masked,
+ * quantisers 1 ... 255, lengths <= 16), as are the segment lengths and offsets the pack functions read: no device table can take an
+ * access outside a buffer.  A block codes to at most 63 x 26 + 27 bits whatever the tables hold; nothing is ever truncated.
+ *
+ * ccedit_mjpeg_segment_bytes: bytes of one segment's slot in `segments` (all its blocks at that bound, every byte stuffed), a
+ *   multiple of 16; -1 for a W that is no multiple of 16.
+ * ccedit_mjpeg_transform: frames -> coef int16 [N][H / 16][W / 16][6][64]: per MCU the blocks Y00 Y01 Y10 Y11 Cb Cr, each in zigzag
+ *   order, quantised by the base tables scaled to `quality` (1 ... 100): q = sign(F) ((|F| + (Q << 17)) >> 18) / Q, AC clamped to
+ *   +-1023.  frames and coef 16-byte aligned.
+ * ccedit_mjpeg_entropy: coef -> the stuffed, padded entropy-coded bytes of segment i at segments + i * segment_bytes, its length in
+ *   seg_len[i] (int32 [N * H / 16]).  DC predictors start at 0 in every segment; DC differences are clamped to +-2047.
+ * ccedit_mjpeg_pack_scan: seg_len -> seg_off (int64 [N * H / 16]: where each segment starts in the packed output, the frames back to
+ *   back, each `hdr_len` header bytes, its segments separated by RSTn, EOI) and frame_bytes (int32 [N]).
+ * ccedit_mjpeg_pack: copies header, segments and markers into out (out_bytes = the sum of frame_bytes).
+ */
+int64_t ccedit_mjpeg_segment_bytes(int32_t W);
+int ccedit_mjpeg_transform(const void* frames, const int32_t* tables, void* coef, int32_t N, int32_t H, int32_t W, int32_t quality, void* stream);
+int ccedit_mjpeg_entropy(const void* coef, const int32_t* tables, void* segments, int32_t* seg_len, int32_t N, int32_t H, int32_t W, void* stream);
+int ccedit_mjpeg_pack_scan(const int32_t* seg_len, int64_t* seg_off, int32_t* frame_bytes, int32_t N, int32_t H, int32_t W, int32_t hdr_len,
+                           void* stream);
+int ccedit_mjpeg_pack(const void* segments, const int32_t* seg_len, const int64_t* seg_off, const void* header, void* out, int32_t N, int32_t H,
+                      int32_t W, int32_t hdr_len, int64_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

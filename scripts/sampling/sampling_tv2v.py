@@ -29,9 +29,11 @@ one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everyt
 --noise_seed, --gpu_io — runs on the long latent as on a short one, first-stage encode / decode in groups of at most T frames.
 Launched under torch.distributed (RANK / WORLD_SIZE), the chunks are dealt round-robin to the ranks (BASELINE.json config 5:
 independent clips, one per GPU, no collective — ccedit_amd.parallel.shard_clips).
-`--propagate` (job mode, --save_type gif) adds the frames BETWEEN the keyframes: every source frame from the first to the last keyframe
+`--propagate` (job mode, --save_type gif or mjpeg) adds the frames BETWEEN the keyframes: every source frame from the first to the last keyframe
 gets an edited frame, the two neighbouring edited keyframes carried along motion estimated on the source (ccedit_amd/propagate.py,
-csrc/propagate.hip), written to <save_path>/<basemodel>/result_full/gif/ at --original_fps; log_info.json gains `fullrate_paths`.
+csrc/propagate.hip), written to <save_path>/<basemodel>/result_full/gif/ (or mjpeg/) at --original_fps; log_info.json gains `fullrate_paths`.
+`--save_type mjpeg` writes true-colour video: Motion-JPEG in an .avi, every frame encoded on the GPU (ccedit_amd/mjpeg.py, csrc/mjpeg.hip) at
+--video_quality; such an .avi is also a video SOURCE wherever a .gif is.
 """
 from __future__ import annotations
 
@@ -61,7 +63,7 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--vae_path", type=str, default="")
     p.add_argument("--cond_path", type=str, default="", help="precomputed conditioning tensors (see module docstring)")
     p.add_argument("--synthetic", action="store_true", help="seeded random conditioning + name-keyed synthetic weights")
-    p.add_argument("--video_path", type=str, default="", help="directory of frame images or .gif: source of `keyframes`")
+    p.add_argument("--video_path", type=str, default="", help="directory of frame images, .gif or Motion-JPEG .avi: source of `keyframes`")
     p.add_argument("--prompt_listpath", type=str, default="")
     p.add_argument("--video_listpath", type=str, default="")
     p.add_argument("--videos_directory", type=str, default="", help="directory containing videos to be processed")
@@ -74,8 +76,12 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--batch_size", type=int, default=4)
     p.add_argument("--original_fps", type=int, default=20)
     p.add_argument("--target_fps", type=int, default=3)
-    p.add_argument("--save_type", type=str, default="npy", choices=["npy", "gif", "mp4"],
-                   help="reference: gif | mp4 (default mp4).  mp4 needs a codec library (none offline: raises, as decoding does); npy = raw frames")
+    p.add_argument("--save_type", type=str, default="npy", choices=["npy", "gif", "mp4", "mjpeg"],
+                   help="reference: gif | mp4 (default mp4).  mp4 needs a codec library (none offline: raises, as decoding does); npy = raw frames; "
+                        "mjpeg (not in the reference script) = true-colour Motion-JPEG in an .avi, baseline JPEG frames encoded on the GPU "
+                        "(ccedit_amd/mjpeg.py, csrc/mjpeg.hip) at --video_quality; H and W must be multiples of 16")
+    p.add_argument("--video_quality", type=int, default=90,
+                   help="(not in the reference script) JPEG quality of --save_type mjpeg, 1 ... 100: the Annex K tables scaled by the usual rule")
     p.add_argument("--save_path", type=str, default="outputs/demo/tv2v")
     p.add_argument("--H", type=int, default=256)
     p.add_argument("--W", type=int, default=384)
@@ -115,7 +121,7 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="(not in the reference script) full-frame-rate output: after a clip's keyframes are saved, every source frame from the "
                         "first to the last keyframe gets an edited frame — the two neighbouring edited keyframes carried along the source's "
                         "motion (ccedit_amd/propagate.py, csrc/propagate.hip) — written to <save_path>/result_full/ at --original_fps.  "
-                        "Needs a video source (job mode) and --save_type gif")
+                        "Needs a video source (job mode) and --save_type gif or --save_type mjpeg")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(not in the reference script) draw the samplers' per-step noise from a CPU generator with this seed instead of "
@@ -146,8 +152,12 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         if not job_mode(args):
             p.error("--propagate carries the edit to the frames between the keyframes of a video: give --prompt with --video_path "
                     "(or --prompt_listpath / --videos_directory / --json_path)")
-        if args.save_type != "gif":
-            p.error(f"--propagate writes result_full/ as gif: add --save_type gif (got {args.save_type})")
+        if args.save_type not in ("gif", "mjpeg"):
+            p.error(f"--propagate writes result_full/ as gif or as Motion-JPEG: add --save_type gif or --save_type mjpeg (got {args.save_type})")
+    if not 1 <= getattr(args, "video_quality", 90) <= 100:
+        p.error(f"--video_quality must be in 1 ... 100 (got {args.video_quality})")
+    if args.save_type == "mjpeg" and (args.H % 16 or args.W % 16):
+        p.error(f"--save_type mjpeg codes 16 x 16 MCUs: --H and --W must be multiples of 16 (got {args.H}x{args.W})")
 
 
 def windowing(args) -> bool:
@@ -178,7 +188,7 @@ def check_propagate(args, video_paths) -> None:
     from scripts.sampling.util import count_video_frames, keyframe_indices
     for v in dict.fromkeys(video_paths):
         video = resolve_video(v)
-        if os.path.isdir(video) or (video.endswith(".gif") and os.path.exists(video)):
+        if os.path.isdir(video) or (video.endswith((".gif", ".avi")) and os.path.exists(video)):
             n = count_video_frames(video)
             try:
                 plan(keyframe_indices(n, args.original_fps, args.target_fps, args.num_keyframes), n)
@@ -188,11 +198,11 @@ def check_propagate(args, video_paths) -> None:
 
 def propagate_chunk(args, cvideos, samples, dev, save_path):
     """--propagate for one chunk: per clip all source frames on the device, the edited keyframes as the uint8 frames result/ holds
-    (frames_to_u8 without rounding of the decoder output), propagate_clip, <save_path>/result_full/gif/animation-XXXX.gif at
-    --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
+    (frames_to_u8 without rounding of the decoder output), propagate_clip, <save_path>/result_full/gif/animation-XXXX.gif (--save_type
+    mjpeg: result_full/mjpeg/animation-XXXX.avi, encoded from the frames where they are, on the device) at --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
     from ccedit_amd import ops
     from ccedit_amd.propagate import propagate_clip
-    from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask, save_gif_u8
+    from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask, save_avi_u8, save_gif_u8
     edited = ops.frames_to_u8(samples.float().contiguous(), rounding=False, unit_range=False)           # (bs, T, H, W, 3)
     paths = []
     for b, v in enumerate(cvideos):
@@ -204,7 +214,10 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
                                     device=dev, all_frames=True).contiguous()
         idx = keyframe_indices(n_all, args.original_fps, args.target_fps, args.num_keyframes)
         full = propagate_clip(source, idx, edited[b], masks=masks)
-        paths.append(save_gif_u8(os.path.join(save_path, "result_full"), full.cpu().numpy(), args.original_fps))
+        if args.save_type == "mjpeg":
+            paths.append(save_avi_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps, args.video_quality))
+        else:
+            paths.append(save_gif_u8(os.path.join(save_path, "result_full"), full.cpu().numpy(), args.original_fps))
     return paths
 
 
@@ -294,13 +307,15 @@ def text_inputs(cond, dev, args=None):
 
 
 def save_result(args, tag, x):
-    """sampling_tv2v.py:473-515: clamp to [0,1]; .npy frames (default) or an animated gif + frame grid."""
+    """sampling_tv2v.py:473-515: clamp to [0,1]; .npy frames (default) or an animated gif / a Motion-JPEG .avi + frame grid."""
     from scripts.sampling.util import perform_save_locally_video, save_frames
-    if args.save_type == "gif" and getattr(args, "gpu_io", False):
-        perform_save_locally_video(os.path.join(args.save_path, "result"), x, fps=args.target_fps, savetype="gif", gpu_io=True, signed=True)
-    elif args.save_type == "gif":
+    quality = dict(video_quality=args.video_quality) if args.save_type == "mjpeg" else {}
+    if args.save_type in ("gif", "mjpeg") and getattr(args, "gpu_io", False):
+        perform_save_locally_video(os.path.join(args.save_path, "result"), x, fps=args.target_fps, savetype=args.save_type, gpu_io=True, signed=True,
+                                   **quality)
+    elif args.save_type in ("gif", "mjpeg"):
         perform_save_locally_video(os.path.join(args.save_path, "result"), torch.clamp((x + 1.0) / 2.0, 0.0, 1.0),
-                                   fps=args.target_fps, savetype="gif")
+                                   fps=args.target_fps, savetype=args.save_type, **quality)
     save_frames(args.save_path, tag, x)
 
 
@@ -328,7 +343,7 @@ def find_mask(args, video_path: str):
         return args.mask_path
     if not video_path:
         return None
-    stem = video_path[:-4] if video_path.endswith((".mp4", ".gif")) else video_path.rstrip("/")
+    stem = video_path[:-4] if video_path.endswith((".mp4", ".gif", ".avi")) else video_path.rstrip("/")
     cands = [(stem + ".mask.png", os.path.isfile), (stem + ".mask.gif", os.path.isfile), (stem + ".mask", os.path.isdir)]
     if getattr(args, "mask_root", ""):
         base = os.path.join(args.mask_root, os.path.basename(stem))
@@ -349,7 +364,7 @@ def clip_masks(args, video_paths, dev):
         if mpath is None:
             raise NotImplementedError(f"no mask for {v or 'the clip'}: {NO_MASK}")
         video = resolve_video(v) if v else ""
-        n_all = count_video_frames(video) if video and (os.path.isdir(video) or video.endswith(".gif")) else None
+        n_all = count_video_frames(video) if video and (os.path.isdir(video) or video.endswith((".gif", ".avi"))) else None
         out.append(load_video_mask(mpath, args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all, **_io_device(args)))
     return torch.stack([m.to(dev) for m in out], dim=0).contiguous()
 
@@ -494,13 +509,15 @@ def basemodel_list(args):
 
 def resolve_video(video_path: str) -> str:
     """The json layout names <Video Name>.mp4; without a codec library (none offline) the same clip as a directory of frames
-    <Video Name>/ or as <Video Name>.gif is taken instead.  Nothing else is rewritten."""
+    <Video Name>/, as <Video Name>.gif or as <Video Name>.avi (Motion-JPEG) is taken instead.  Nothing else is rewritten."""
     if video_path.endswith(".mp4"):
         stem = video_path[:-4]
         if os.path.isdir(stem):
             return stem
         if os.path.exists(stem + ".gif"):
             return stem + ".gif"
+        if os.path.exists(stem + ".avi"):
+            return stem + ".avi"
     return video_path
 
 
@@ -511,7 +528,7 @@ def depth_frames(args, video_path: str, keyframes: torch.Tensor) -> torch.Tensor
     bicubic resize are applied here like to the frames (the keyframes are selected first, only they are resized) — or, with
     --synthetic, the keyframes' luminance.  Under --gpu_io the selected raw depth is uploaded and resized by ccedit_resize_f32_bicubic."""
     from scripts.sampling.util import keyframe_indices
-    stem = video_path[:-4] if video_path.endswith((".mp4", ".gif")) else video_path.rstrip("/")
+    stem = video_path[:-4] if video_path.endswith((".mp4", ".gif", ".avi")) else video_path.rstrip("/")
     cands = ([os.path.join(args.depth_root, os.path.basename(stem) + ".pt")] if args.depth_root else []) + [stem + ".depth.pt"]
     T, H, W = keyframes.shape[2], keyframes.shape[3], keyframes.shape[4]
     for cpath in cands:
@@ -665,10 +682,12 @@ def run_jobs(args, with_ref: bool = False) -> None:
             print(f"chunk {idx}: {bs} clip(s) of {T} frames {H}x{W} in {time.time() - t0:.2f}s")
             to01 = lambda v: (torch.clamp(v.float(), -1.0, 1.0) + 1.0) / 2.0
             save_path = video_save_paths[idx] if video_save_paths else os.path.join(args.save_path, base_tag)
-            if args.gpu_io and args.save_type == "gif":                   # uint8 frames made on the device: clamp((x + 1) / 2) is in the kernel
+            if args.gpu_io and args.save_type in ("gif", "mjpeg"):       # uint8 frames made on the device: clamp((x + 1) / 2) is in the kernel
                 to01, io = (lambda v: v), dict(gpu_io=True, signed=True)
             else:                                                         # (.npy keeps fp32 frames: the host route)
                 io = {}
+            if args.save_type == "mjpeg":
+                io["video_quality"] = args.video_quality
             perform_save_locally_video(os.path.join(save_path, "original"), to01(keyframes), args.target_fps, args.save_type, save_grid=False, **io)
             keyframes_paths = perform_save_locally_video(os.path.join(save_path, "result"), to01(samples), args.target_fps, args.save_type,
                                                          return_savepaths=True, save_grid=False, **io)
@@ -676,7 +695,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
                                        save_grid=False, **io)
             if mask_px is not None:                                       # the mask as it was applied, same naming as control_hint/
                 m01 = (mask_px >= 128).float()[:, None].expand(-1, 3, -1, -1, -1).contiguous()
-                perform_save_locally_video(os.path.join(save_path, "mask"), m01 * 2.0 - 1.0 if io else m01, args.target_fps, args.save_type,
+                perform_save_locally_video(os.path.join(save_path, "mask"), m01 * 2.0 - 1.0 if io.get("signed") else m01, args.target_fps, args.save_type,
                                            save_grid=False, **io)
             if args.propagate:
                 log_info.setdefault("fullrate_paths", [])

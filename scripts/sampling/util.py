@@ -273,8 +273,8 @@ def load_vae_file(model, vae_path: str) -> None:
 
 # ------------------------------------------------------------------------------------------
 # frame / video I/O: reference scripts/sampling/util.py:288-382, 689-762
-# Image files and GIFs go through Pillow; mp4 needs a codec library (decord / cv2 / imageio-ffmpeg) that is not
-# installed here and raises.
+# Image files, GIFs and the JPEG frames of a Motion-JPEG .avi (ccedit_amd/mjpeg.py: read_avi walks the container) go through Pillow;
+# mp4 needs a codec library (decord / cv2 / imageio-ffmpeg) that is not installed here and raises.
 # ------------------------------------------------------------------------------------------
 def _decode_rgb_u8(path: str) -> np.ndarray:
     """Image file -> uint8 (H, W, 3) on the host (the decode is Pillow's on both routes)."""
@@ -354,6 +354,20 @@ def _decode_gif_u8(video_path: str) -> np.ndarray:
                      for fr in ImageSequence.Iterator(Image.open(video_path))], axis=0)
 
 
+def _is_frame_file(video_path: str) -> bool:
+    """A video held in ONE file whose frames Pillow decodes: an animated .gif or a Motion-JPEG .avi."""
+    return video_path.endswith((".gif", ".avi"))
+
+
+def _decode_video_u8(video_path: str) -> np.ndarray:
+    """All frames of a .gif or an MJPG .avi -> uint8 (N, h, w, 3) on the host; from here on both are treated alike.  An .avi that is
+    missing, truncated or holds another codec is a ValueError that says so (ccedit_amd.mjpeg.read_avi)."""
+    if video_path.endswith(".avi"):
+        from ccedit_amd.mjpeg import decode_avi_u8
+        return decode_avi_u8(video_path)
+    return _decode_gif_u8(video_path)
+
+
 def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
     """(not in the reference) ALL frames of what load_video_keyframes reads -> uint8 (F, H, W, 3) on `device` at size = (H, W): the
     source side of --propagate.  Decoding stays on the host (Pillow); the frames reach the output size by the routes of the keyframes —
@@ -366,14 +380,14 @@ def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
         groups = [np.stack(frames, axis=0)] if len({f.shape for f in frames}) == 1 else [f[None] for f in frames]
         out = [ops.resize_u8_pil(torch.from_numpy(np.ascontiguousarray(g)).to(device), size) for g in groups]
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
-    if video_path.endswith(".gif"):
-        x = _frames_to_device(list(_decode_gif_u8(video_path)), None, device).contiguous()       # (F, 3, h, w) in [-1, 1]
+    if _is_frame_file(video_path):
+        x = _frames_to_device(list(_decode_video_u8(video_path)), None, device).contiguous()     # (F, 3, h, w) in [-1, 1]
         x = ops.resize_bicubic(x, size)
         return ops.frames_to_u8(x.permute(1, 0, 2, 3)[None].contiguous(), rounding=True)[0]
     if video_path.endswith(".mp4"):
         raise NotImplementedError("mp4 decoding needs decord / cv2 / imageio-ffmpeg, none of which is installed; "
                                   "extract the frames to a directory of images (or a .gif) instead")
-    raise ValueError("Unsupported video format. Only support dirctory, .mp4 and .gif.")
+    raise ValueError("Unsupported video format. Only support dirctory, .mp4, .gif and .avi (Motion-JPEG).")
 
 
 def save_gif_u8(save_path: str, frames: np.ndarray, fps: int) -> str:
@@ -387,9 +401,23 @@ def save_gif_u8(save_path: str, frames: np.ndarray, fps: int) -> str:
     return savepath
 
 
+def save_avi_u8(save_path: str, frames, fps: int, quality: int = 90) -> str:
+    """uint8 frames (T, H, W, 3), on the device or on the host (then uploaded) -> <save_path>/mjpeg/animation-XXXX.avi, numbered like
+    save_gif_u8's files: Motion-JPEG, every frame encoded on the device (ccedit_amd/mjpeg.py), only the compressed bytes come back."""
+    from ccedit_amd import mjpeg
+    if not torch.is_tensor(frames):
+        frames = torch.from_numpy(np.ascontiguousarray(frames))
+    if not frames.is_cuda:
+        frames = frames.to(torch.device("cuda", torch.cuda.current_device()))
+    os.makedirs(os.path.join(save_path, "mjpeg"), exist_ok=True)
+    count = len(os.listdir(os.path.join(save_path, "mjpeg")))
+    savepath = os.path.join(save_path, "mjpeg", f"animation-{count:04}.avi")
+    return mjpeg.write_avi(savepath, mjpeg.encode_frames(frames, quality), fps, frames.shape[1], frames.shape[2])
+
+
 def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None,
                          device=None) -> torch.Tensor:
-    """util.py:689-762: directory of frame images or a .gif -> keyframes (T, 3, H, W) in [-1, 1].
+    """util.py:689-762: directory of frame images, a .gif or a Motion-JPEG .avi -> keyframes (T, 3, H, W) in [-1, 1].
     device=None: everything on the host, as the reference.  With a device, decoding stays on the host (Pillow, uint8); the keyframes
     are uploaded once as uint8 and resized / scaled by the kernels of ccedit_amd/csrc/pixel.hip: image files exactly as on the
     host (Pillow's 8-bit bicubic), .gif frames by the fp32 bicubic of F.interpolate (equal to fp32 rounding)."""
@@ -401,8 +429,8 @@ def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, nu
         if device is not None:
             return _frames_to_device([_decode_rgb_u8(os.path.join(video_path, files[i])) for i in idx], size, device)
         return torch.cat([load_img(os.path.join(video_path, files[i]), size) for i in idx], dim=0)
-    if video_path.endswith(".gif"):
-        frames = _decode_gif_u8(video_path)
+    if _is_frame_file(video_path):
+        frames = _decode_video_u8(video_path)
         if device is not None:
             from ccedit_amd import ops
             frames = frames[keyframe_indices(frames.shape[0], original_fps, target_fps, num_keyframes)]
@@ -418,17 +446,20 @@ def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, nu
     if video_path.endswith(".mp4"):
         raise NotImplementedError("mp4 decoding needs decord / cv2 / imageio-ffmpeg, none of which is installed; "
                                   "extract the frames to a directory of images (or a .gif) instead")
-    raise ValueError("Unsupported video format. Only support dirctory, .mp4 and .gif.")
+    raise ValueError("Unsupported video format. Only support dirctory, .mp4, .gif and .avi (Motion-JPEG).")
 
 
 def count_video_frames(video_path: str) -> int:
-    """Number of frames of what load_video_keyframes reads: files of a directory, frames of a .gif."""
+    """Number of frames of what load_video_keyframes reads: files of a directory, frames of a .gif or of a Motion-JPEG .avi."""
     if os.path.isdir(video_path):
         return len(os.listdir(video_path))
     if video_path.endswith(".gif"):
         from PIL import Image
         return int(getattr(Image.open(video_path), "n_frames", 1))
-    raise ValueError("Unsupported video format. Only support dirctory, .mp4 and .gif.")
+    if video_path.endswith(".avi"):
+        from ccedit_amd.mjpeg import read_avi
+        return len(read_avi(video_path)[0])
+    raise ValueError("Unsupported video format. Only support dirctory, .mp4, .gif and .avi (Motion-JPEG).")
 
 
 _MASK_IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".tif", ".tiff")
@@ -438,7 +469,7 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
                     device=None, all_frames: bool = False) -> torch.Tensor:
     """The edit mask of a clip -> uint8 (T, H, W) holding 0 (keep the original) or 255 (edit): the reference's
     x = x * mask + img_orig * (1 - mask) with white = 1.  (The reference leaves the mask to the user: sampling_tv2v.py:385-407.)
-    mask_path: what load_video_keyframes accepts — a directory of images or a .gif, one mask per frame of the VIDEO: `num_allframes`
+    mask_path: what load_video_keyframes accepts — a directory of images, a .gif or a Motion-JPEG .avi, one mask per frame of the VIDEO: `num_allframes`
     (None: not checked) must equal its frame count, the keyframes are selected by the same `keyframe_indices` rule as the frames — or
     ONE image file, used for every keyframe.  Any image mode is taken through its luminance (`convert("L")`); a value >= 128 is white.
     Resize to size = (H, W) is nearest-neighbour on the binarised mask, src = floor((dst + 0.5) * in / out) (Pillow's NEAREST, its
@@ -460,11 +491,15 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
     elif mask_path.endswith(".gif"):
         frames = [lum(fr) for fr in ImageSequence.Iterator(Image.open(mask_path))]
         n, pick = len(frames), lambda i: frames[i]
+    elif mask_path.endswith(".avi"):
+        from ccedit_amd.mjpeg import decode_avi_u8
+        frames = [lum(Image.fromarray(fr)) for fr in decode_avi_u8(mask_path)]
+        n, pick = len(frames), lambda i: frames[i]
     elif mask_path.lower().endswith(_MASK_IMAGE_EXT):
         one = lum(Image.open(mask_path))
         n, pick = None, lambda i: one
     else:
-        raise ValueError(f"Unsupported mask format: {mask_path}. Only support directory, .gif and one image file {_MASK_IMAGE_EXT}.")
+        raise ValueError(f"Unsupported mask format: {mask_path}. Only support directory, .gif, .avi (Motion-JPEG) and one image file {_MASK_IMAGE_EXT}.")
     if all_frames and n is None and num_allframes is None:
         raise ValueError("load_video_mask(all_frames=True) of one image needs num_allframes")
     if n is None:
@@ -492,25 +527,30 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
 
 
 def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, savetype: str = "gif",
-                               return_savepaths: bool = False, save_grid: bool = True, gpu_io: bool = False, signed: bool = False):
+                               return_savepaths: bool = False, save_grid: bool = True, gpu_io: bool = False, signed: bool = False,
+                               video_quality: int = 90):
     """util.py:288-352: samples (B, 3, T, H, W) in [0, 1] -> <save_path>/gif/animation-XXXX.gif (+ grid/grid-XXXX.png:
     the T frames side by side).  savetype='mp4' needs a codec library and raises.
-    gpu_io (savetype='gif', device tensor): the uint8 frames are made on the device (ccedit_frames_to_u8) and 3 bytes per pixel
+    savetype='mjpeg' (not in the reference): <save_path>/mjpeg/animation-XXXX.avi, Motion-JPEG at `video_quality` (1 ... 100), numbered and
+    returned like the gifs; the uint8 frames are the gif branch's — made on the host and uploaded, or on the device with gpu_io: the same
+    bytes either way — and every frame is encoded on the device (ccedit_amd/mjpeg.py, csrc/mjpeg.hip).
+    gpu_io (savetype='gif' or 'mjpeg', device tensor): the uint8 frames are made on the device (ccedit_frames_to_u8) and 3 bytes per pixel
     instead of 12 come to the host; the files are byte-identical.  `signed` (with gpu_io only): samples are the decoder's output in
     [-1, 1] and clamp((x + 1) / 2, 0, 1) is part of the same kernel."""
     from PIL import Image
     assert samples.dim() == 5, "Expected samples to have shape (B, C, T, H, W)"
-    assert savetype in ["gif", "mp4", "npy"]
+    assert savetype in ["gif", "mp4", "npy", "mjpeg"]
     assert gpu_io or not signed, "signed samples are only taken on the gpu_io route"
     if savetype == "mp4":
         raise NotImplementedError("mp4 encoding needs imageio-ffmpeg / cv2, not installed here: use savetype='gif'")
     u8 = u8_grid = None
     if gpu_io:
         from ccedit_amd import ops
-        if savetype != "gif" or not samples.is_cuda:
+        if savetype not in ("gif", "mjpeg") or not samples.is_cuda:
             raise ValueError("gpu_io saves uint8 frames (savetype='gif') of a device tensor")
         x = samples.detach().float().contiguous()
-        u8 = ops.frames_to_u8(x, rounding=False, unit_range=not signed).cpu().numpy()                  # (B, T, H, W, 3)
+        u8 = ops.frames_to_u8(x, rounding=False, unit_range=not signed)                                # (B, T, H, W, 3)
+        u8 = u8 if savetype == "mjpeg" else u8.cpu().numpy()                                           # (mjpeg: the frames stay on the device)
         u8_grid = ops.frames_to_u8(x, rounding=True, unit_range=not signed).cpu().numpy() if save_grid else None
     if savetype == "npy":          # (not in the reference) the frames themselves: <save_path>/npy/frames-XXXX.npy, (T, H, W, C) float32 in [0, 1]
         os.makedirs(os.path.join(save_path, "npy"), exist_ok=True)
@@ -536,6 +576,11 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
             grid = np.concatenate(list(np.clip(frames_f * 255.0 + 0.5, 0, 255).astype(np.uint8) if u8 is None else u8_grid[b]), axis=1)
             Image.fromarray(grid).save(os.path.join(save_path, "grid", f"grid-{count_grid:04}.png"))
             count_grid += 1
+        if savetype == "mjpeg":
+            savepath = save_avi_u8(save_path, (255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b], fps, video_quality)
+            count += 1
+            savepaths.append(savepath)
+            continue
         frames = [Image.fromarray(f) for f in ((255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b])]
         savepath = os.path.join(save_path, "gif", f"animation-{count:04}.gif")
         frames[0].save(savepath, save_all=True, append_images=frames[1:], duration=int(round(1000.0 / fps)), loop=0)
