@@ -20,12 +20,14 @@ Anything else raises NotImplementedError at construction.
 from __future__ import annotations
 
 import os
+import warnings
 from typing import Dict, List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
 from . import ops, policy
+from .caches import GraphEntry, PinnedCache, tensor_key
 from .hip import ACT_SILU
 from .layers import PACK_GENERATION, Conv, Linear, Norm, Slot, pack_tree
 from .packing import pack_concat
@@ -1219,9 +1221,6 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
     # result is kept while the SAME hint tensor (storage, shape, version) is passed again — results are
     # unchanged.  bench.py's per-step metric runs with the cache OFF (every step does the full work).
     cache_hint_stem = True
-    _hint_val = None
-    _hint_slices = None
-    _hint_dup = None
     dedup_hint = policy.on("hint_dedup")      # 0: evaluate the hint stem on both CFG halves (A/B)
     frame_shard = None          # parallel.FrameShard: split the T keyframes of each clip over the ranks (config 4)
     row_shard = None            # parallel.RowShard: split the latent ROWS of every frame over the ranks (config 4, balanced)
@@ -1237,48 +1236,51 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
     # the two files that had the form without the SLP vectoriser and refuses it in any object (check_isa), which restored
     # run-to-run bit-equality with the side stream on; CCEDIT_OVERLAP_CONTROLNET=0 keeps everything on one stream.
     overlap_controlnet = policy.on("overlap_controlnet")
-    _side_stream = None
+    _side_stream = {}           # main stream handle -> the side stream that serves it (process-wide, like _half_stream)
     _half_stream = None
-
-    @staticmethod
-    def _tensor_key(tns: torch.Tensor):
-        return (tns.data_ptr(), tuple(tns.shape), tuple(tns.stride()), tns._version, tns.dtype)
-
     _fail_capture_for_test = False      # tests/test_network_gpu.py: make the next capture raise after its launches were recorded
+
+    def __init__(self, diffusion_model, compile_model: bool = False):
+        super().__init__(diffusion_model, compile_model)
+        # the per-clip caches (caches.PinnedCache: a key match always means the same bytes); two limits follow reserve_windows
+        self._hint_val = PinnedCache(lambda: self._hint_slots)          # hint-stem outputs: one per CFG half (+ shards)
+        self._hint_dup = PinnedCache(lambda: 2 * self._hint_slots)      # are the two halves of a hint tensor equal?
+        self._hint_slices = PinnedCache(4)                              # this rank's contiguous part of a hint tensor
+        self._twin_val = PinnedCache(8)                                 # are the two CFG halves of (x, t, hint, cond_feat) equal?
+        self._tkv_val = PinnedCache(6)                                  # text K / V per (network, conditioning tensor)
+        self._graphs = PinnedCache(lambda: self._graph_slots, evict="oldest")       # a GraphEntry per conditioning key
+
+    def __setattr__(self, name, value):
+        if value is None and isinstance(self.__dict__.get(name), PinnedCache):
+            self.__dict__[name].clear()         # `w._graphs = None`, the earlier spelling of a clear: the cache object stays
+        else:
+            super().__setattr__(name, value)
 
     def reset_caches(self):
         """Drop the per-clip caches (hint stem, shard slices, captured graphs).  Never needed for correctness — entries pin
-        their source storage, see _guided_hint — only to release the previous clip's memory early."""
-        self._hint_val = None
-        self._hint_slices = None
-        self._hint_dup = None
-        self._twin_val = None
-        self._tkv_val = None
-        self._graphs = None
+        their source storage, see caches.PinnedCache — only to release the previous clip's memory early."""
+        for cache in (self._hint_val, self._hint_dup, self._hint_slices, self._twin_val, self._tkv_val, self._graphs):
+            cache.clear()
 
     def _guided_hint(self, hint5d: torch.Tensor, rows=None, half: bool = False):
-        """hint_stem(1 - (hint+1)/2), cached per source tensor.  An entry is keyed by (address, shape, strides, in-place
-        version) AND keeps a reference to the source tensor: while the entry lives its storage cannot be freed, so no
-        later tensor (the next clip's hint) can be handed that address by the caching allocator — a key match always
-        means the same bytes."""
+        """hint_stem(1 - (hint+1)/2), cached per source tensor."""
         net = self.diffusion_model.controlnet
-        key = self._tensor_key(hint5d) + (PACK_GENERATION[0], half)        # (a re-pack replaces the stem's weights)
-        if self.cache_hint_stem and isinstance(self._hint_val, dict) and key in self._hint_val:
-            return self._hint_val[key][1]
+        key = tensor_key(hint5d) + (PACK_GENERATION[0], half)        # (a re-pack replaces the stem's weights)
+        g = self._hint_val.get(key) if self.cache_hint_stem else None
+        if g is not None:
+            return g
         # The two CFG halves carry the SAME hint (the sampling scripts give `uc` a clone of c's control_hint, sampling_tv2v.py:339-344,
         # and the guider concatenates them): the stem — eight per-frame convolutions at up to 512 x 768 — is evaluated on one half and its
         # output repeated.  Whether the halves are equal is decided by comparing them once per hint tensor (a device compare and one
-        # host sync, remembered with the tensor's identity + version like the caches above; never decided while capturing a graph).
-        dup = False
+        # host sync, remembered per tensor; never decided while capturing a graph).
+        dup = None
         if self.dedup_hint and hint5d.shape[0] % 2 == 0:
-            if not isinstance(self._hint_dup, dict) or len(self._hint_dup) >= 2 * self._hint_slots:
-                self._hint_dup = {}
-            ent = self._hint_dup.get(key[:-1])
-            if ent is None and not torch.cuda.is_current_stream_capturing():
+            dup = self._hint_dup.get(key[:-1])
+            if dup is None and not torch.cuda.is_current_stream_capturing():
                 k = hint5d.shape[0] // 2
-                ent = self._hint_dup[key[:-1]] = (hint5d, bool(torch.equal(hint5d[:k], hint5d[k:])))
-            dup = ent is not None and ent[1]
-        dup = dup or half           # (half: the caller — _cfg_twins — has compared the halves itself)
+                dup = bool(torch.equal(hint5d[:k], hint5d[k:]))
+                self._hint_dup.put(key[:-1], hint5d, dup)
+        dup = bool(dup) or half     # (half: the caller — _cfg_twins — has compared the halves itself)
         src = hint5d[: hint5d.shape[0] // 2] if dup else hint5d
         # control_hint in [-1,1] -> 1 - (h+1)/2 (wrappers.py:160-162), fused into the layout change
         hint8 = ops.ncthw_to_nhwc(src.float().contiguous(), 8, scale=-0.5, shift=0.5)
@@ -1286,9 +1288,7 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
         if dup and not half:
             g = torch.cat([g, g])
         if self.cache_hint_stem:
-            if not isinstance(self._hint_val, dict) or len(self._hint_val) >= self._hint_slots:     # one entry per CFG half (+ shards)
-                self._hint_val = {}
-            self._hint_val[key] = (hint5d, g)
+            self._hint_val.put(key, hint5d, g)
         return g
 
     # The two CFG halves of an evaluation (guiders.py:57-67: x, sigma, control_hint and cond_feat are the SAME tensor twice, only the
@@ -1300,7 +1300,6 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
     # hint's); anything else — different latents in the two halves, odd batches, sharded evaluation — takes the general path.  bench.py
     # reports the FLOPs executed (`executed_flops_per_step`) next to the algorithmic count the metric is priced with.
     share_cfg_prefix = policy.on("share_cfg_prefix")
-    _twin_val = None
 
     def _cfg_twins(self, x: torch.Tensor, t: torch.Tensor, c: Dict[str, torch.Tensor]) -> bool:
         if not self.share_cfg_prefix or x.shape[0] % 2 or x.shape[0] < 2 or torch.cuda.is_current_stream_capturing():
@@ -1313,32 +1312,27 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
             marks.append(ops.get_mark(c["cond_feat"], "_halves_equal"))
         if marks[0] is True and marks[1] is True and all(m is not None for m in marks[2:]):
             return all(marks)
-        key = self._tensor_key(x) + self._tensor_key(t) + tuple(self._tensor_key(c[n]) for n in ("control_hint", "cond_feat") if c.get(n) is not None)
-        if not isinstance(self._twin_val, dict) or len(self._twin_val) >= 8:
-            self._twin_val = {}
-        ent = self._twin_val.get(key)
-        if ent is None:
-            same = (x[:k] == x[k:]).all() & (t[:k] == t[k:]).all() & (c["control_hint"][:k] == c["control_hint"][k:]).all()
+        srcs = [x, t] + [c[n] for n in ("control_hint", "cond_feat") if c.get(n) is not None]
+        key = tuple(tensor_key(s) for s in srcs)
+        same = self._twin_val.get(key)
+        if same is None:
+            eq = (x[:k] == x[k:]).all() & (t[:k] == t[k:]).all() & (c["control_hint"][:k] == c["control_hint"][k:]).all()
             if c.get("cond_feat") is not None:
-                same = same & (c["cond_feat"][:k] == c["cond_feat"][k:]).all()
-            ent = self._twin_val[key] = ([x, t] + [c[n] for n in ("control_hint", "cond_feat") if c.get(n) is not None], bool(same.item()))
-        return ent[1]
-
-    _tkv_val = None
+                eq = eq & (c["cond_feat"][:k] == c["cond_feat"][k:]).all()
+            same = bool(eq.item())
+            self._twin_val.put(key, srcs, same)
+        return same
 
     def _text_kv(self, net, context: torch.Tensor, ctx2d: torch.Tensor) -> "TextKV":
         """net.text_kv(ctx2d), kept per (network, conditioning tensor) while the per-clip caches are on (`cache_hint_stem`): the text
-        K / V projections are constant over the 59 evaluations of a clip (the reference recomputes them every time).  Same
-        keying discipline as _guided_hint: identity + version of the source tensor, which the entry pins."""
+        K / V projections are constant over the 59 evaluations of a clip (the reference recomputes them every time)."""
         if not self.cache_hint_stem:
             return net.text_kv(ctx2d)
-        key = (id(net),) + self._tensor_key(context) + (PACK_GENERATION[0],)
-        if isinstance(self._tkv_val, dict) and key in self._tkv_val:
-            return self._tkv_val[key][1]
-        tkv = net.text_kv(ctx2d)
-        if not isinstance(self._tkv_val, dict) or len(self._tkv_val) >= 6:
-            self._tkv_val = {}
-        self._tkv_val[key] = (context, tkv)
+        key = (id(net),) + tensor_key(context) + (PACK_GENERATION[0],)
+        tkv = self._tkv_val.get(key)
+        if tkv is None:
+            tkv = net.text_kv(ctx2d)
+            self._tkv_val.put(key, context, tkv)
         return tkv
 
     # One network evaluation is ~560 kernel launches issued from Python; where the kernels are short (the 16x24 / 8x12 levels, the
@@ -1352,7 +1346,6 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
     # the two-stream CFG halves (CCEDIT_SPLIT_CFG=1: capturing four streams that fork and join inside each other crashed the
     # runtime on ROCm 7.2 — not pursued, the batched pass is the default).
     use_graph = policy.on("graph") and not _SPLIT_CFG
-    _graphs = None
     _graph_failed = False
 
     # A long clip (ccedit_amd/windows.py) evaluates W windows in turn at every sampler evaluation: W conditioning keys alive at once.
@@ -1379,187 +1372,194 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
         self.graph_counts[kind] += 1
 
     def forward(self, x: torch.Tensor, t: torch.Tensor, c: Dict[str, torch.Tensor], **kwargs) -> torch.Tensor:
-        # row-sharded evaluations are captured too when their exchanges are stream operations (RCCL; the host-staged gloo transport of the
-        # CPU / one-GPU tests is not): the launch count per rank is the single-GPU one while every kernel is N times shorter
+        # any extra keyword forces the eager path; row-sharded evaluations are captured too when their exchanges are stream operations
+        # (RCCL; the host-staged gloo of the CPU / one-GPU tests is not): single-GPU launch count per rank, every kernel N times shorter
         if (self.use_graph and not OpenAIWrapperControlLDM3DTV2V._graph_failed and not kwargs and x.is_cuda
                 and self.frame_shard is None
                 and (self.row_shard is None or (not isinstance(self.row_shard, (tuple, list)) and self.row_shard.can_capture()))
                 and ops.PROFILE is None and TRACE is None and not torch.cuda.is_current_stream_capturing()):
             return self._forward_graphed(x, t, c)
-        return self._forward_eager(x, t, c, **kwargs)
+        return self._forward_eager(x, t, c)
+
+    def _graph_key(self, x, t, c, twins: bool) -> tuple:
+        # PACK_GENERATION: a captured graph holds the addresses of the packed weights it was recorded with
+        return (tuple(x.shape), x.dtype, tuple(t.shape), t.dtype, self.cache_hint_stem, self.overlap_controlnet, PACK_GENERATION[0], twins,
+                None if self.row_shard is None else (id(self.row_shard), self.row_shard.attn),
+                tuple(sorted((k, tensor_key(v)) if torch.is_tensor(v) else (k, repr(v)) for k, v in c.items())))
 
     def _forward_graphed(self, x, t, c):
         # the shared CFG prefix is a property of the VALUES of x and t: decided here, outside any capture, and part of the key — a
         # graph recorded for identical halves is never replayed for different ones
         twins = self._cfg_twins(x, t, c) if (self.frame_shard is None and self.row_shard is None) else False
-        # PACK_GENERATION: a captured graph holds the addresses of the packed weights it was recorded with
-        key = (tuple(x.shape), x.dtype, tuple(t.shape), t.dtype, self.cache_hint_stem, self.overlap_controlnet, PACK_GENERATION[0], twins,
-               None if self.row_shard is None else (id(self.row_shard), self.row_shard.attn),
-               tuple(sorted((k, self._tensor_key(v)) if torch.is_tensor(v) else (k, repr(v)) for k, v in c.items())))
-        if self._graphs is None:
-            self._graphs = {}
+        key = self._graph_key(x, t, c, twins)
         ent = self._graphs.get(key)
         if ent is None:
-            while len(self._graphs) >= self._graph_slots:       # a clip uses one key (W with windows); keep the previous clip's until it is replaced
-                self._graphs.pop(next(iter(self._graphs)))
-            # the conditioning tensors are pinned while the entry lives: a key match always means the same bytes (see _guided_hint)
-            self._graphs[key] = dict(pins=[v for v in c.values() if torch.is_tensor(v)])
+            # a clip uses one key (W with windows); the previous clip's entries stay until they are replaced (evict="oldest")
+            ent = GraphEntry(pins=[v for v in c.values() if torch.is_tensor(v)])
+            self._graphs.put(key, ent.pins, ent)
             self._count("eager")
-            return self._forward_eager(x, t, c, _twins=twins)
-        if "graph" not in ent:
-            ok = True
-            try:
-                ent["x"], ent["t"] = x.clone(), t.clone()
-                g = torch.cuda.CUDAGraph()
-                # thread_local: calls from OTHER threads (the process group's watchdog polling its events when torch.distributed is
-                # initialised — bench.py --gpus N) must not invalidate the capture
-                with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode="thread_local"):
-                    # scratch arenas used while capturing must live in this graph's pool, and nothing outside the capture may go on
-                    # using them: their zero fills are only RECORDED, and after a failed capture never run at all — the eager
-                    # fallback would accumulate statistics onto uninitialised memory and wait on garbage split-K counters
-                    ops.reset_stream_scratch()
-                    try:
-                        ent["out"] = self._forward_eager(ent["x"], ent["t"], c, _twins=twins)
-                        if self._fail_capture_for_test:
-                            raise RuntimeError("capture failure injected by a test")
-                    finally:
-                        ops.reset_stream_scratch()
-                ent["graph"] = g
-                self._count("capture")
-                ent["pins"].append(dict(self._hint_val) if isinstance(self._hint_val, dict) else None)   # the cached stem output it reads
-                ent["pins"].append(dict(self._tkv_val) if isinstance(self._tkv_val, dict) else None)     # ... and the cached text K / V
-            except Exception as e:                              # capture is an optimisation: report once, keep evaluating eagerly
-                import warnings
-                ok = False
-                warnings.warn(f"HIP graph capture of the network evaluation failed ({type(e).__name__}: {e}); continuing without graphs")
-            # Row-sharded: the ranks must AGREE on graph-or-eager before anyone goes on.  A rank that fell back alone would run
-            # the ControlNet's exchanges on the sibling communicator / side stream while its peers replay a single-stream graph: collectives
-            # on different communicators in different orders, i.e. a deadlock.  One all-reduced flag, issued outside any capture; every
-            # rank reaches it (a rank whose capture succeeded has not replayed yet).
-            if self.row_shard is not None:
-                ok = self.row_shard.all_agree(ok)
-            if not ok:
-                OpenAIWrapperControlLDM3DTV2V._graph_failed = True
-                self._graphs = None
-                ops.reset_stream_scratch()                      # (again: whatever the aborted capture left behind)
-                return self._forward_eager(x, t, c, _twins=twins)
-        else:
-            ent["x"].copy_(x)
-            ent["t"].copy_(t)
+            return self._forward_eager(x, t, c, twins)
+        if ent.captured:
+            ent.x.copy_(x)
+            ent.t.copy_(t)
             self._count("replay")
-        ent["graph"].replay()
-        return ent["out"].clone()
+        elif not self._capture(ent, x, t, c, twins):
+            OpenAIWrapperControlLDM3DTV2V._graph_failed = True
+            self._graphs.clear()
+            ops.reset_stream_scratch()                          # (again: whatever the aborted capture left behind)
+            return self._forward_eager(x, t, c, twins)
+        ent.graph.replay()
+        return ent.out.clone()
 
-    def _forward_eager(self, x: torch.Tensor, t: torch.Tensor, c: Dict[str, torch.Tensor], **kwargs) -> torch.Tensor:
-        pair = isinstance(self.frame_shard, (tuple, list)) and not kwargs.get("_half")
+    def _capture(self, ent: GraphEntry, x, t, c, twins: bool) -> bool:
+        """Record one evaluation into ent.graph.  True when every rank has a graph to replay; False: all of them go on eagerly."""
+        ok = True
+        try:
+            ent.x, ent.t = x.clone(), t.clone()
+            g = torch.cuda.CUDAGraph()
+            # thread_local: calls from OTHER threads (the process group's watchdog polling its events when torch.distributed is
+            # initialised — bench.py --gpus N) must not invalidate the capture
+            with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode="thread_local"):
+                # scratch arenas used while capturing must live in this graph's pool, and nothing outside the capture may go on
+                # using them: their zero fills are only RECORDED, and after a failed capture never run at all — the eager
+                # fallback would accumulate statistics onto uninitialised memory and wait on garbage split-K counters
+                ops.reset_stream_scratch()
+                try:
+                    ent.out = self._forward_eager(ent.x, ent.t, c, twins)
+                    if self._fail_capture_for_test:
+                        raise RuntimeError("capture failure injected by a test")
+                finally:
+                    ops.reset_stream_scratch()
+            ent.graph = g
+            self._count("capture")
+            # the cached stem output and text K / V the graph reads: copies of the references, which outlive a cleared cache
+            ent.pins += [list(self._hint_val.values()), list(self._tkv_val.values())]
+        except Exception as e:                              # capture is an optimisation: report once, keep evaluating eagerly
+            ok = False
+            warnings.warn(f"HIP graph capture of the network evaluation failed ({type(e).__name__}: {e}); continuing without graphs")
+        # Row-sharded: the ranks must AGREE on graph-or-eager before anyone goes on (ADVICE r5).  A rank that fell back alone would run
+        # the ControlNet's exchanges on the sibling communicator / side stream while its peers replay a single-stream graph: collectives
+        # on different communicators in different orders, i.e. a deadlock.  One all-reduced flag, issued outside any capture; every
+        # rank reaches it (a rank whose capture succeeded has not replayed yet).
+        if self.row_shard is not None:
+            ok = self.row_shard.all_agree(ok)
+        return ok
+
+    def _forward_eager(self, x: torch.Tensor, t: torch.Tensor, c: Dict[str, torch.Tensor], twins: Optional[bool] = None) -> torch.Tensor:
+        """As two CFG halves on two streams where that is configured, else in one piece; `twins`: _cfg_twins if the caller knows it."""
+        pair = isinstance(self.frame_shard, (tuple, list))
         # RowShard.cfg_pair (round 6): the two CFG halves are independent evaluations — each on its own stream and communicator, so
         # one half's exchanges (head all-to-alls, halo rows with their statistics) wait under the other half's kernels
-        rpair = isinstance(self.row_shard, (tuple, list)) and not kwargs.get("_half")
-        if rpair and x.shape[0] != 2:
-            raise ValueError("a RowShard.cfg_pair shards the two CFG halves of a batch-2 step")
-        if pair and x.shape[0] != 2:
-            raise ValueError("a FrameShard.cfg_pair shards the two CFG halves of a batch-2 step")
-        if pair or rpair or (_SPLIT_CFG and x.shape[0] == 2 and self.frame_shard is None and ops.PROFILE is None and TRACE is None
-                             and not kwargs.get("_half")):
-            # the two CFG halves are independent: two streams (and, frame-sharded, two communicators with mirrored
-            # partitions — one half's exchanges overlap the other half's kernels)
-            shards = self.frame_shard if pair else (None, None)
-            rshards = self.row_shard if rpair else (None, None)
-            main = torch.cuda.current_stream()
-            if OpenAIWrapperControlLDM3DTV2V._half_stream is None:
-                OpenAIWrapperControlLDM3DTV2V._half_stream = torch.cuda.Stream()
-            hs = OpenAIWrapperControlLDM3DTV2V._half_stream
-            hs.wait_stream(main)
-            halves = [{k: (v[i:i + 1].contiguous() if torch.is_tensor(v) else v) for k, v in c.items()} for i in range(2)]
-            with torch.cuda.stream(hs):
-                e1 = self._forward_eager(x[1:2].contiguous(), t[1:2].contiguous(), halves[1], _half=True, _shard=shards[1], _rshard=rshards[1])
-            e0 = self._forward_eager(x[0:1].contiguous(), t[0:1].contiguous(), halves[0], _half=True, _shard=shards[0], _rshard=rshards[0])
-            main.wait_stream(hs)
-            e1.record_stream(main)
-            return torch.cat([e0, e1])
+        rpair = isinstance(self.row_shard, (tuple, list))
+        if (pair or rpair) and x.shape[0] != 2:
+            raise ValueError(f"a {'RowShard' if rpair else 'FrameShard'}.cfg_pair shards the two CFG halves of a batch-2 step")
+        if pair or rpair or (_SPLIT_CFG and x.shape[0] == 2 and self.frame_shard is None and ops.PROFILE is None and TRACE is None):
+            # ADVICE r6: with split_cfg=1 and a SINGLE RowShard the halves run unsharded (row_shards is (None, None)), as before
+            return self._forward_cfg_halves(x, t, c, self.frame_shard if pair else (None, None), self.row_shard if rpair else (None, None))
+        return self._evaluate(x, t, c, frame_shard=self.frame_shard, row_shard=self.row_shard, half=False, twins=twins)
+
+    def _forward_cfg_halves(self, x, t, c, frame_shards, row_shards) -> torch.Tensor:
+        """The two CFG halves are independent: two streams (and, frame-sharded, two communicators with mirrored partitions — one
+        half's exchanges overlap the other half's kernels)."""
+        main = torch.cuda.current_stream()
+        if OpenAIWrapperControlLDM3DTV2V._half_stream is None:
+            OpenAIWrapperControlLDM3DTV2V._half_stream = torch.cuda.Stream()
+        hs = OpenAIWrapperControlLDM3DTV2V._half_stream
+        hs.wait_stream(main)
+        halves = [{k: (v[i:i + 1].contiguous() if torch.is_tensor(v) else v) for k, v in c.items()} for i in range(2)]
+        def half(i):        # (its slices of x and t are made on the stream it runs on)
+            return self._evaluate(x[i:i + 1].contiguous(), t[i:i + 1].contiguous(), halves[i], frame_shard=frame_shards[i],
+                                  row_shard=row_shards[i], half=True, twins=False)
+        with torch.cuda.stream(hs):
+            e1 = half(1)
+        e0 = half(0)
+        main.wait_stream(hs)
+        e1.record_stream(main)
+        return torch.cat([e0, e1])
+
+    def _shard_inputs(self, x, c, sh, rs):
+        """(x, control_hint, cond_feat) as this rank evaluates them: under a frame shard its keyframes of every clip (everything
+        spatial is frame-local), under a row shard its latent rows of every frame and the 8x finer hint rows that feed them."""
+        hint, cond_feat = c["control_hint"], c.get("cond_feat", None)
+        if sh is None and rs is None:
+            return x, hint, cond_feat
+        if sh is not None:
+            if sh.t_glob != x.shape[2]:
+                raise ValueError(f"frame shard built for T={sh.t_glob}, got T={x.shape[2]}")
+            if rs is not None:
+                raise ValueError("frame_shard and row_shard are alternative decompositions of one clip")
+            x = x[:, :, sh.t0:sh.t1]
+            part, mine = (sh.t0, sh.t1), hint[:, :, sh.t0:sh.t1]
+        else:
+            rs.check_latent(x.shape[3])
+            r0, r1 = rs.rows(x.shape[3])
+            x = x[:, :, :, r0:r1]
+            part, mine = ("rows", r0, r1), hint[:, :, :, 8 * r0:8 * r1]
+            if cond_feat is not None:
+                cond_feat = cond_feat[:, :, r0:r1]
+        key = tensor_key(hint) + part
+        piece = self._hint_slices.get(key)
+        if piece is None:               # a stable tensor object, so that the hint-stem cache can hit
+            piece = mine.contiguous()
+            self._hint_slices.put(key, hint, piece)
+        return x, piece, cond_feat
+
+    def _run_controlnet(self, x8, x8h, hint5, t, context, ctx2d, geo: Geometry, *, half: bool, twins: bool):
+        """The ControlNet's residuals, in line or on a side stream beside the UNet encoder (overlap_controlnet): (control,
+        control_ready), the event the UNet waits for before it first reads them, None in line."""
+        net, rs = self.diffusion_model.controlnet, geo.rows
+        # Row-sharded: a captured evaluation keeps everything on ONE stream — capturing RCCL collectives issued from two streams that
+        # fork and join inside the graph crashes the runtime (ROCm 7.2, one or two communicators alike: tools/exp/rows_rccl_debug.py),
+        # and with every kernel N times shorter it is the graph, not the overlap, that matters.  Eager RCCL evaluations (graphs off)
+        # do use the side stream, the ControlNet's exchanges on a communicator of their own (RowShard.sibling).
+        rows_side_ok = rs is None or (not half and rs.can_capture()      # (a half of a RowShard pair: the other half is what overlaps)
+                                      and not (self.use_graph and not OpenAIWrapperControlLDM3DTV2V._graph_failed))
+        if not (self.overlap_controlnet and geo.shard is None and rows_side_ok and ops.PROFILE is None and TRACE is None):
+            guided = self._guided_hint(hint5, rows=rs, half=twins)
+            return net.run(x8h, guided, t, self._text_kv(net, context, ctx2d), context.shape[1], geo, shared=twins), None
+        main = torch.cuda.current_stream()
+        side = self._side_stream.get(main.cuda_stream)
+        if side is None:
+            side = self._side_stream[main.cuda_stream] = torch.cuda.Stream()
+        side.wait_stream(main)                      # x8 / ctx2d / t are ready
+        with torch.cuda.stream(side):
+            # rows sharded: the ControlNet's exchanges go through a communicator of their own (RowShard.sibling)
+            rs_side = None if rs is None else rs.sibling()
+            geo_side = geo if rs is None else Geometry(geo.b, geo.t, geo.shard, rows=rs_side)
+            guided = self._guided_hint(hint5, rows=rs_side, half=twins)
+            control = net.run(x8h, guided, t, self._text_kv(net, context, ctx2d), context.shape[1], geo_side, shared=twins)
+            control_ready = torch.cuda.Event()
+            control_ready.record(side)
+        for tns in (x8, ctx2d):
+            tns.record_stream(side)                 # allocated on the main stream, read on the side stream (x8h is a view of x8)
+        for tns in control:
+            tns.record_stream(main)                 # and vice versa
+        return control, control_ready
+
+    def _evaluate(self, x, t, c, *, frame_shard, row_shard, half: bool, twins: Optional[bool]) -> torch.Tensor:
+        """One evaluation on the current stream.  `half`: x is one CFG half of a step; `twins`: are x's halves identical (None: find out)."""
         if c.get("concat") is not None and c["concat"].numel():
             raise NotImplementedError("'concat' conditioning is not used by the TV2V configs")
-        net = self.diffusion_model
+        net, sh, rs = self.diffusion_model, frame_shard, row_shard
         b, _, nt, lh, lw = x.shape
         if lh % 8 or lw % 8:
             raise ValueError(f"latent {lh}x{lw}: frame sizes must be multiples of 64 pixels (three stride-2 levels whose "
                              f"skips are concatenated with the 2x-upsampled decoder tensors, controlmodel.py:539-543)")
         if tuple(c["control_hint"].shape[-2:]) != (8 * lh, 8 * lw):
             raise ValueError(f"control_hint {tuple(c['control_hint'].shape)} does not match latent {lh}x{lw} (x8)")
-        sh = kwargs.get("_shard", None) if kwargs.get("_half") else self.frame_shard
-        hint5 = c["control_hint"]
-        if sh is not None:             # keep this rank's keyframes of every clip; everything spatial is frame-local
-            if sh.t_glob != nt:
-                raise ValueError(f"frame shard built for T={sh.t_glob}, got T={nt}")
-            x = x[:, :, sh.t0:sh.t1]
-            hint5 = hint5[:, :, sh.t0:sh.t1]
-            hk = self._tensor_key(c["control_hint"]) + (sh.t0, sh.t1)
-            if not isinstance(self._hint_slices, dict) or len(self._hint_slices) >= 4:
-                self._hint_slices = {}
-            if hk not in self._hint_slices:
-                # a stable tensor object so the hint-stem cache can hit; the entry pins the source (see _guided_hint)
-                self._hint_slices[hk] = (c["control_hint"], hint5.contiguous())
-            hint5 = self._hint_slices[hk][1]
-        rs = kwargs.get("_rshard", None) if kwargs.get("_half") else self.row_shard
-        cond_feat = c.get("cond_feat", None)
-        if rs is not None:             # keep this rank's latent rows of every frame (and the 8x finer hint rows that feed them)
-            if sh is not None:
-                raise ValueError("frame_shard and row_shard are alternative decompositions of one clip")
-            rs.check_latent(lh)
-            r0, r1 = rs.rows(lh)
-            x = x[:, :, :, r0:r1]
-            hk = self._tensor_key(c["control_hint"]) + ("rows", r0, r1)
-            if not isinstance(self._hint_slices, dict) or len(self._hint_slices) >= 4:
-                self._hint_slices = {}
-            if hk not in self._hint_slices:
-                self._hint_slices[hk] = (c["control_hint"], hint5[:, :, :, 8 * r0:8 * r1].contiguous())
-            hint5 = self._hint_slices[hk][1]
-            if cond_feat is not None:
-                cond_feat = cond_feat[:, :, r0:r1]
-        geo = Geometry(b, x.shape[2], sh, rows=rs)
+        xs, hint5, cond_feat = self._shard_inputs(x, c, sh, rs)
+        geo = Geometry(b, xs.shape[2], sh, rows=rs)
         context = c["crossattn"]
         ctx2d = context.to(torch.bfloat16).reshape(-1, context.shape[-1]).contiguous()
-        x8 = ops.ncthw_to_nhwc(x.float().contiguous(), 8)
+        x8 = ops.ncthw_to_nhwc(xs.float().contiguous(), 8)
         # identical CFG halves: their shared prefix is evaluated once (see _cfg_twins); never for sharded / traced / split evaluations
-        twins = kwargs.get("_twins")
-        if sh is not None or rs is not None or TRACE is not None or kwargs.get("_half"):
+        if sh is not None or rs is not None or TRACE is not None or half:
             twins = False
         elif twins is None:
             twins = self._cfg_twins(x, t, c)
         twins = bool(twins) and _splits_at_text(net.input_blocks[1]) and _splits_at_text(net.controlnet.input_blocks[1])
         x8h = x8[: x8.shape[0] // 2] if twins else x8
-        control_ready = None
-        # Row-sharded: a captured evaluation keeps everything on ONE stream — capturing RCCL collectives issued from two streams that
-        # fork and join inside the graph crashes the runtime (ROCm 7.2, one or two communicators alike: tools/exp/rows_rccl_debug.py),
-        # and with every kernel N times shorter it is the graph, not the overlap, that matters.  Eager RCCL evaluations (graphs off)
-        # do use the side stream, the ControlNet's exchanges on a communicator of their own (RowShard.sibling).
-        rows_side_ok = rs is None or (rs.can_capture() and not (self.use_graph and not OpenAIWrapperControlLDM3DTV2V._graph_failed))
-        if kwargs.get("_half") and rs is not None:
-            rows_side_ok = False                        # a CFG half of a RowShard pair: the other half is what overlaps, one stream each
-        if self.overlap_controlnet and sh is None and rows_side_ok and ops.PROFILE is None and TRACE is None:
-            main = torch.cuda.current_stream()
-            if OpenAIWrapperControlLDM3DTV2V._side_stream is None:
-                OpenAIWrapperControlLDM3DTV2V._side_stream = {}
-            side = OpenAIWrapperControlLDM3DTV2V._side_stream.setdefault(main.cuda_stream, None)
-            if side is None:
-                side = OpenAIWrapperControlLDM3DTV2V._side_stream[main.cuda_stream] = torch.cuda.Stream()
-            side.wait_stream(main)                      # x8 / ctx2d / t are ready
-            with torch.cuda.stream(side):
-                # rows sharded: the ControlNet's exchanges go through a communicator of their own (RowShard.sibling)
-                rs_side = None if rs is None else rs.sibling()
-                geo_side = geo if rs is None else Geometry(b, x.shape[2], sh, rows=rs_side)
-                guided = self._guided_hint(hint5, rows=rs_side, half=twins)
-                control = net.controlnet.run(x8h, guided, t, self._text_kv(net.controlnet, context, ctx2d), context.shape[1], geo_side,
-                                             shared=twins)
-                control_ready = torch.cuda.Event()
-                control_ready.record(side)
-            for tns in (x8, ctx2d):
-                tns.record_stream(side)                 # allocated on the main stream, read on the side stream (x8h is a view of x8)
-            for tns in control:
-                tns.record_stream(main)                 # and vice versa
-        else:
-            guided = self._guided_hint(hint5, rows=rs, half=twins)
-            control = net.controlnet.run(x8h, guided, t, self._text_kv(net.controlnet, context, ctx2d), context.shape[1], geo, shared=twins)
+        control, control_ready = self._run_controlnet(x8, x8h, hint5, t, context, ctx2d, geo, half=half, twins=twins)
         img_control = None
         if cond_feat is not None and (sh is None or sh.owner_of(nt // 2) == sh.rank):
             # TVI2V (wrappers.py:176-190): controlnet_img on the reference latent; its residuals only touch keyframe T//2,

@@ -120,7 +120,7 @@ class _ShardComm:
     def all_agree(self, ok: bool) -> bool:
         """True iff `ok` holds on EVERY rank of the communicator (a MIN all-reduce of one flag through host memory, not counted as a
         data-path exchange).  Used where ranks must take the same branch before issuing further collectives — e.g. whether the HIP-graph
-        capture of a sharded evaluation succeeded everywhere (network._forward_graphed)."""
+        capture of a sharded evaluation succeeded everywhere (network._capture)."""
         flag = torch.tensor([1 if ok else 0], dtype=torch.int32)
         if not self.staged:
             flag = flag.cuda()
@@ -234,7 +234,7 @@ class RowShard(_ShardComm):
     @staticmethod
     def cfg_pair(groups=(None, None), attn: str = "heads"):
         """Two RowShards over the same ranks, one per CFG half of a step (uc, c): the wrapper evaluates the halves as two B = 1 passes
-        on two HIP streams (network._forward_eager), each with its own communicator, so the exchanges of one half are hidden behind
+        on two HIP streams (network._forward_cfg_halves), each with its own communicator, so the exchanges of one half are hidden behind
         the kernels of the other.  `groups`: one process group per half; the second is created here over the same ranks when it is
         not given (`dist.new_group` is collective: every rank calls cfg_pair at the same point)."""
         g0, g1 = groups

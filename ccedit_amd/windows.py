@@ -78,8 +78,8 @@ class WindowedDenoiser:
     guider; cond['control_hint'] (B, 3, N, H, W).  N == T is one window with coefficients 1.0 — the wrapped closure's own bits.
 
     Per clip, not per evaluation: the plan and its device tables (per N), and the windows' conditioning — control_hint slices made
-    contiguous once per source tensor (keyed by identity + in-place version, the entry pins the source: ccedit_amd/network.py,
-    _guided_hint) so that the network's hint-stem cache and captured graphs see W stable tensors; every other entry of `cond` is
+    contiguous once per source tensor (keyed by identity + in-place version, the entry pins the source: the discipline of
+    ccedit_amd/caches.py) so that the network's hint-stem cache and captured graphs see W stable tensors; every other entry of `cond` is
     handed on as the same object (the text K / V cache hits for all windows).  The CFG marks survive: a gather of twin halves is
     twin halves, a slice of equal halves has equal halves — no device compare, no host sync per evaluation.
     `wrapper` (the network wrapper) is told how many windows its per-clip caches must hold (reserve_windows)."""

@@ -65,7 +65,7 @@ def main(out_path):
     e_graph = w(xx, t, c).clone()
     e_moved = w(torch.cat([xb, xb]).to(dev), t2, c).clone()
     e_back = w(xx, t, c).clone()
-    graphed = bool(getattr(w, "_graphs", None)) and any("graph" in e for e in w._graphs.values())
+    graphed = any(e.captured for e in w._graphs.values())
     assert graphed == (w.use_graph and not type(w)._graph_failed), "the HIP graph was not captured"
     assert torch.equal(e_eager, e_graph) and torch.equal(e_eager, e_back), "HIP-graph replay differs from the eager evaluation"
     assert not torch.equal(e_eager, e_moved), "the replay did not pick up the new latent / timestep"
@@ -76,7 +76,7 @@ def main(out_path):
     assert all(torch.equal(f[0], fi) for fi in f[1:]), "replays of the second HIP graph differ from its eager evaluation"
     assert torch.equal(w(xx, t, c), e_eager) and torch.equal(w(xx, t, c2), f[0]), "the two graphs disturb each other"
     if graphed:
-        assert sum("graph" in e for e in w._graphs.values()) == 2
+        assert sum(e.captured for e in w._graphs.values()) == 2
 
     out = dict(eps=run(x, x, cu, cc),                 # the CFG pair of the benchmark: same latent, two prompts
                eps_same=run(x, x, cc, cc),            # identical halves -> identical predictions

@@ -89,7 +89,7 @@ def _worker(rank, world, port, q, crossframe=False, mode="a2a"):
         # conditioning tensors and replayed afterwards — capture and replay must reproduce the eager bits
         assert shards[0].can_capture()
         again = [w(xg, tg, cc).cpu() for _ in range(3)]          # capture + replay, replay, replay
-        graphed = bool(getattr(w, "_graphs", None)) and any("graph" in e for e in w._graphs.values())
+        graphed = any(e.captured for e in w._graphs.values())
         assert graphed == (w.use_graph and not type(w)._graph_failed), "the sharded evaluation was not captured"
         assert all(torch.equal(out, a_) for a_ in again), "HIP-graph replay of the row-sharded evaluation differs from the eager one"
         del cls.issue_log[n_first:]                              # (the capture pass issued the sequence once more)

@@ -345,7 +345,7 @@ def test_shared_cfg_prefix_equals_full_evaluation(g160_wrapper):
     from ccedit_amd import ops
     assert ops.get_mark(seen["x"], "_cfg_twin_halves") is True and ops.get_mark(seen["t"], "_cfg_twin_halves") is True
     assert ops.get_mark(seen["c"]["control_hint"], "_halves_equal") is True and ops.get_mark(seen["c"]["crossattn"], "_halves_equal") is False
-    w._twin_val = None
+    w._twin_val.clear()
     assert w._cfg_twins(seen["x"], seen["t"], seen["c"]) is True and not w._twin_val, "marked halves must not need the device compare"
     # a mark is void once its tensor is written IN PLACE after marking (an inpainting blend, per-half noise): the wrapper must
     # fall back to comparing values — and find the halves different
@@ -355,7 +355,7 @@ def test_shared_cfg_prefix_equals_full_evaluation(g160_wrapper):
     hint_cat = seen["c"]["control_hint"]
     hint_cat[:1].mul_(0.5)
     assert ops.get_mark(hint_cat, "_halves_equal") is None
-    w._twin_val = None
+    w._twin_val.clear()
     from ccedit_amd.sgm_compat import build_network_spec
     from ccedit_amd.utils.synth import synth_state_dict
     from oracle import ccedit_oracle as O
@@ -386,7 +386,7 @@ def test_hip_graph_replay_reproduces_eager_evaluation(g160_wrapper):
             for n, c in (("a", ca), ("b", cb)):
                 for i, (x, t) in enumerate(zip(xs, ts)):
                     assert torch.equal(w(x, t, c), eager[(i, n)]), f"graph replay differs: conditioning {n}, call {i}, round {rep}"
-        assert not type(w)._graph_failed and sum("graph" in e for e in w._graphs.values()) == 2
+        assert not type(w)._graph_failed and sum(e.captured for e in w._graphs.values()) == 2
     finally:
         w.use_graph = saved
         w.reset_caches()
@@ -441,7 +441,7 @@ def test_repack_invalidates_captured_graphs_and_hint_stem_cache(g160_wrapper):
         w.use_graph = True
         w.reset_caches()
         outs = [w(x, t, c).clone() for _ in range(3)]            # eager, capture, replay
-        assert torch.equal(outs[0], outs[2]) and any("graph" in e for e in w._graphs.values())
+        assert torch.equal(outs[0], outs[2]) and any(e.captured for e in w._graphs.values())
         with torch.no_grad():
             p.mul_(2.0)
             stem.mul_(0.5)
@@ -484,7 +484,7 @@ def test_hint_stem_is_shared_between_identical_cfg_halves(g160_wrapper):
             got = w(x, t, c).clone()
             assert torch.equal(got, ref)
             same = bool(torch.equal(hint[:1], hint[1:]))
-            assert [v[1] for v in w._hint_dup.values()] == [same]
+            assert list(w._hint_dup.values()) == [same]
     finally:
         w.dedup_hint, w.use_graph = saved, saved_graph
         w.reset_caches()
@@ -582,7 +582,7 @@ def test_two_clips_through_one_sampler_and_wrapper(g160_wrapper):
     for seed in (101, 202, 101):
         got.append(run(smp, den, seed))
         gc.collect()
-        ptrs.append(sorted(k[0] for k in (g160_wrapper._hint_val or {})))
+        ptrs.append(sorted(k[0] for k in g160_wrapper._hint_val))
     assert torch.equal(got[0], want1), "clip 1 through the shared sampler differs from a fresh run"
     assert torch.equal(got[1], want2), "clip 2 was sampled with stale per-clip state of clip 1"
     assert torch.equal(got[2], want1)

@@ -257,7 +257,7 @@ def _row_worker(rank, world, port, q):
     for p_ in parts[1:]:
         want_total += p_
     ok &= torch.equal(total, want_total)
-    # all_agree: the ranks take the same branch (graph or eager after a capture attempt, network._forward_graphed) — true only when
+    # all_agree: the ranks take the same branch (graph or eager after a capture attempt, network._capture) — true only when
     # every rank says so; not a data-path exchange (neither counted nor logged)
     nc = rs.n_collectives
     ok &= rs.all_agree(True) is True and rs.all_agree(rank != world - 1) is False and rs.all_agree(rank == 0) is (world == 1)

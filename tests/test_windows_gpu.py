@@ -224,7 +224,7 @@ def test_three_windows_replay_three_graphs_without_host_compares(g160_wrapper):
         counts = dict(w.graph_counts)
         assert counts == dict(eager=3, capture=3, replay=9), counts
         assert not w._twin_val, "the network compared CFG halves on the device: a mark was lost on the way through the windows"
-        assert len(w._graphs) == 3 and all("graph" in e for e in w._graphs.values())
+        assert len(w._graphs) == 3 and all(e.captured for e in w._graphs.values())
         assert len(w._hint_val) == 3, "one cached hint-stem output per window"
         assert bool(torch.isfinite(out).all()) and out.shape == (1, 4, 6, 16, 24)
         # the limits of a plain clip come back with reserve_windows(0)

@@ -17,6 +17,6 @@ for i in range(4):
     outs.append(w(x2, ts, cond).clone())
     dist.all_reduce(t)
 torch.cuda.synchronize()
-print("graph failed:", type(w)._graph_failed, "graphs:", sum("graph" in e for e in (w._graphs or {}).values()),
+print("graph failed:", type(w)._graph_failed, "graphs:", sum(e.captured for e in w._graphs.values()),
       "replays equal eager:", all(torch.equal(outs[0], o) for o in outs[1:]), flush=True)
 dist.destroy_process_group()

@@ -93,7 +93,7 @@ def run_clip(wrapper, dev, n, steps, window=None, overlap=None):
                replay_min_ms=round(min(ms["replay"]), 3) if ms.get("replay") else None,
                replay_max_ms=round(max(ms["replay"]), 3) if ms.get("replay") else None,
                peak_memory_mb=round(torch.cuda.max_memory_allocated() / 2 ** 20, 1), finite=bool(torch.isfinite(out).all()),
-               host_compares=len(wrapper._twin_val or {}))
+               host_compares=len(wrapper._twin_val))
     return res
 
 
