@@ -444,7 +444,8 @@ __global__ __launch_bounds__(256) void gn_temporal_cached_kernel(const bf16* __r
 // 1 KB burst whatever C is (the wave-per-(pixel, slice) mapping above runs 40 of 64 lanes at C = 320 / 640 / 1280: 2.7 - 3.9 TB/s).
 // 320 threads = 8 / 4 / 2 pixels of 320 / 640 / 1280 channels.  Statistics: every thread writes the sums of the (at most two) groups
 // its granule touches into its OWN LDS slot; one thread per (pixel, group) adds the two or three granules of that group in
-// ascending order — no atomics, same bits every run.  C % 320 == 0, C / 32 >= 8.
+// ascending order — no atomics, same bits every run.  Whole pixels per workgroup: 320 % (C / 8) == 0 with C % 320 == 0 and C <= 1280,
+// i.e. C in {320, 640, 1280} (C / 32 >= 8, at most 8 pixels per workgroup).  NOT C = 960: 320 / 120 leaves 80 threads on a third pixel.
 constexpr int kGtFlatThreads = 320;
 template <int CT>            // rows cached per thread (>= T): 17 for the 17-keyframe clips — 12 registers fewer than the general 20
 __global__ __launch_bounds__(kGtFlatThreads) void gn_temporal_flat_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
@@ -804,12 +805,14 @@ void launch_gn_apply(dim3 grid, hipStream_t s, const bf16* x, bf16* y, const dou
         while (rpb > 8 * RS && (int64_t)((hw + rpb - 1) / rpb) * grid.y < 2048) rpb >>= 1;
         hipLaunchKernelGGL(gn_spatial_apply_flat_kernel, dim3((hw + rpb - 1) / rpb, grid.y), dim3(gt * RS), 0, s, x, y, stats, gamma, beta,
                            hw, C, eps, silu, rpb, RS);
+        cc_note_kernel("gn_spatial_apply_flat_kernel RS=%d", RS);
         return;
     }
     const int cols = (C / 8 + 63) / 64;
 #define CC_GA(N) hipLaunchKernelGGL(gn_spatial_apply_kernel<N>, grid, dim3(256), 0, s, x, y, stats, gamma, beta, hw, C, eps, silu, apb)
     if (cols == 1) CC_GA(1); else if (cols == 2) CC_GA(2); else if (cols == 3) CC_GA(3); else if (cols == 4) CC_GA(4); else CC_GA(kMaxCols);
 #undef CC_GA
+    cc_note_kernel("gn_spatial_apply_kernel<%d>", cols < kMaxCols ? cols : kMaxCols);
 }
 
 __global__ void zero_f64_kernel(double* p, int n) {
@@ -828,6 +831,7 @@ extern "C" int ccedit_groupnorm_spatial(const void* x, void* y, const float* gam
     hipStream_t s = (hipStream_t)stream;
     if (C % 256 == 0 && (int64_t)hw * (C / 256) <= 256 * kGnOneUnits) {       // small frames: one pass, one launch
         hipLaunchKernelGGL(gn_spatial_onepass_kernel, dim3(32, frames), dim3(256), 0, s, (const bf16*)x, (bf16*)y, gamma, beta, hw, C, eps, silu);
+        cc_note_kernel("gn_spatial_onepass_kernel");
         return cc_launch_status("groupnorm_spatial (one pass)");
     }
     // (a kernel, not hipMemsetAsync: the runtime's fill of these 17 KB takes ~23 us of device time per call, 0.5 ms per step)
@@ -879,7 +883,9 @@ extern "C" int ccedit_groupnorm_temporal(const void* x, void* y, const float* ga
     const int flat_env = cc_policy().gn_flat;      // 0: A/B against the wave-per-slice mapping
     // (measured, 2 x 17 frames: 70 / 38 us against 73 / 40 at 64x96 / 32x48; the small levels — a few hundred workgroups — are
     //  1 - 2 us better with the wave-per-slice mapping's larger grid)
-    if (flat_env && T <= kGtCacheT && C % 320 == 0 && C <= 1280 && waves * (C >> 3) >= 700 * kGtFlatThreads) {
+    // (the flat kernel needs whole pixels per workgroup: 320 % (C / 8) == 0, i.e. C in {320, 640, 1280}.  C = 960 would give its
+    //  threads 240..319 a third pixel that the next workgroup owns, with statistics nobody computed: it takes the cached arm)
+    if (flat_env && T <= kGtCacheT && kGtFlatThreads % (C >> 3) == 0 && C % 320 == 0 && C <= 1280 && waves * (C >> 3) >= 700 * kGtFlatThreads) {
         const int ppb = kGtFlatThreads / (C >> 3);
         if (T <= 17)
             hipLaunchKernelGGL(gn_temporal_flat_kernel<17>, dim3((unsigned)((waves + ppb - 1) / ppb)), dim3(kGtFlatThreads), 0, (hipStream_t)stream,
@@ -887,13 +893,16 @@ extern "C" int ccedit_groupnorm_temporal(const void* x, void* y, const float* ga
         else
             hipLaunchKernelGGL(gn_temporal_flat_kernel<kGtCacheT>, dim3((unsigned)((waves + ppb - 1) / ppb)), dim3(kGtFlatThreads), 0, (hipStream_t)stream,
                                (const bf16*)x, (bf16*)y, gamma, beta, waves, T, hw, C, eps, silu);
+        cc_note_kernel(T <= 17 ? "gn_temporal_flat_kernel<17>" : "gn_temporal_flat_kernel<20>");
     } else if (T <= kGtCacheT && (C >> 3) % nsl == 0) {
         const int64_t nw = waves * nsl;
         hipLaunchKernelGGL(gn_temporal_cached_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                            (const bf16*)x, (bf16*)y, gamma, beta, B, T, hw, C, nsl, eps, silu);
+        cc_note_kernel("gn_temporal_cached_kernel nsl=%d", nsl);
     } else {
         hipLaunchKernelGGL(gn_temporal_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, gamma,
                            beta, B, T, hw, C, eps, silu);
+        cc_note_kernel("gn_temporal_kernel");
     }
     return cc_launch_status("groupnorm_temporal");
 }
@@ -905,6 +914,7 @@ extern "C" int ccedit_groupnorm_temporal_stats(const void* x, float* stats, int3
     const int64_t waves = (int64_t)B * hw;
     hipLaunchKernelGGL(gn_temporal_stats_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16*)x, stats, B, T, hw, C);
+    cc_note_kernel("gn_temporal_stats_kernel");
     return cc_launch_status("groupnorm_temporal_stats");
 }
 
@@ -918,6 +928,7 @@ extern "C" int ccedit_groupnorm_temporal_apply(const void* x, void* y, const flo
     const int64_t waves = (int64_t)B * hw;
     hipLaunchKernelGGL(gn_temporal_apply_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16*)x, (bf16*)y, gamma, beta, stats, B, T, hw, C, count, eps, silu, dst_frames, dst_off);
+    cc_note_kernel("gn_temporal_apply_kernel");
     return cc_launch_status("groupnorm_temporal_apply");
 }
 
@@ -985,6 +996,7 @@ extern "C" int ccedit_row_stats(const void* x, float* stats, int64_t rows, int32
 #define CC_RS(N) hipLaunchKernelGGL(row_stats_kernel<N>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, stats, rows, C, eps, rpw)
     if (cols == 1) CC_RS(1); else if (cols == 2) CC_RS(2); else CC_RS(kLnCols);
 #undef CC_RS
+    cc_note_kernel("row_stats_kernel<%d> rpw=%d", cols < kLnCols ? cols : kLnCols, rpw);
     return cc_launch_status("row_stats");
 }
 
@@ -1000,5 +1012,6 @@ extern "C" int ccedit_layernorm(const void* x, void* y, const float* gamma, cons
 #define CC_LN(N) hipLaunchKernelGGL(layernorm_kernel<N>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, gamma, beta, rows, C, eps, rpw)
     if (cols == 1) CC_LN(1); else if (cols == 2) CC_LN(2); else CC_LN(kLnCols);
 #undef CC_LN
+    cc_note_kernel("layernorm_kernel<%d> rpw=%d", cols < kLnCols ? cols : kLnCols, rpw);
     return cc_launch_status("layernorm");
 }
