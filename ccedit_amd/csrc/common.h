@@ -183,3 +183,13 @@ int cc_mjpeg_entropy(const int16_t* coef, const int32_t* tab, uint8_t* scratch, 
 int cc_mjpeg_pack_scan(const int32_t* seg_len, int64_t* seg_off, int32_t* frame_bytes, int32_t N, int32_t H, int32_t W, int32_t hdr_len, hipStream_t s);
 int cc_mjpeg_pack(const uint8_t* scratch, const int32_t* seg_len, const int64_t* seg_off, const uint8_t* header, uint8_t* out, int32_t N, int32_t H,
                   int32_t W, int32_t hdr_len, int64_t out_bytes, hipStream_t s);
+
+// JPEG decoding launchers (jpegdec.hip); entry points and argument checks in core.cpp
+int64_t cc_jpegdec_plane_bytes(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs);
+int64_t cc_jpegdec_blocks(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs);
+int64_t cc_jpegdec_intervals(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int32_t restart_interval);
+int cc_jpegdec_entropy(const uint8_t* data, int64_t data_bytes, const int64_t* intervals, const int32_t* tab, int16_t* coef, int32_t* status,
+                       int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int32_t restart_interval, hipStream_t s);
+int cc_jpegdec_idct(const int16_t* coef, const int32_t* tab, uint8_t* planes, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs,
+                    int32_t vs, hipStream_t s);
+int cc_jpegdec_rgb(const uint8_t* planes, uint8_t* out, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, hipStream_t s);

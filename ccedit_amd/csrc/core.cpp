@@ -330,3 +330,61 @@ extern "C" int ccedit_mjpeg_pack(const void* segments, const int32_t* seg_len, c
     return cc_mjpeg_pack((const uint8_t*)segments, seg_len, seg_off, (const uint8_t*)header, (uint8_t*)out, N, H, W, hdr_len, out_bytes,
                          (hipStream_t)stream);
 }
+
+// ---- JPEG decoding (kernels and launchers: jpegdec.hip).  Geometry and everything else the host can see is checked here, before any HIP
+// call; interval offsets and tables are device data, held in range by the kernels themselves.
+static int jpegdec_geom_ok(const char* fn, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs) {
+    CC_CHECK_ARG(H >= 1 && W >= 1 && H <= 65520 && W <= 65520, "%s: frames of %dx%d (H and W 1 ... 65520)", fn, H, W);
+    CC_CHECK_ARG(ncomp == 1 || ncomp == 3, "%s: ncomp=%d (1 greyscale, 3 YCbCr)", fn, ncomp);
+    CC_CHECK_ARG(ncomp == 1 || (hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2),
+                 "%s: luma sampling %dx%d (1x1, 2x1 or 2x2: 4:4:4, 4:2:2, 4:2:0)", fn, hs, vs);
+    return CCEDIT_OK;
+}
+
+static int jpegdec_shape_ok(const char* fn, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs) {
+    CC_CHECK_ARG(N >= 1, "%s: N=%d frames (N >= 1)", fn, N);
+    if (int rc = jpegdec_geom_ok(fn, H, W, ncomp, hs, vs)) return rc;
+    CC_CHECK_ARG((double)N * (double)cc_jpegdec_plane_bytes(H, W, ncomp, hs, vs) < (double)(kPixelMax * 4) &&
+                     (double)N * (double)cc_jpegdec_blocks(H, W, ncomp, hs, vs) < (double)kPixelMax,
+                 "%s: N=%d frames of %dx%d are more than one call takes (2^33 bytes of planes, 2^31 blocks)", fn, N, H, W);
+    CC_CHECK_ARG((double)N * H * W < (double)kPixelMax,          // one thread per pixel: a launch holds fewer than 2^32 threads
+                 "%s: N=%d frames of %dx%d are more than one call takes (2^31 pixels)", fn, N, H, W);
+    return CCEDIT_OK;
+}
+
+extern "C" int64_t ccedit_jpegdec_plane_bytes(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs) {
+    if (jpegdec_geom_ok("ccedit_jpegdec_plane_bytes", H, W, ncomp, hs, vs)) return CCEDIT_EINVAL;
+    return cc_jpegdec_plane_bytes(H, W, ncomp, hs, vs);
+}
+
+extern "C" int ccedit_jpegdec_entropy(const void* data, int64_t data_bytes, const int64_t* intervals, const int32_t* tables, void* coef,
+                                      int32_t* status, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs,
+                                      int32_t restart_interval, void* stream) {
+    CC_CHECK_ARG(data && intervals && tables && coef && status, "ccedit_jpegdec_entropy: null pointer");
+    if (int rc = jpegdec_shape_ok("ccedit_jpegdec_entropy", N, H, W, ncomp, hs, vs)) return rc;
+    CC_CHECK_ARG(data_bytes >= 1 && data_bytes < kPixelMax * 4, "ccedit_jpegdec_entropy: data_bytes=%lld (1 ... 2^33)", (long long)data_bytes);
+    CC_CHECK_ARG(restart_interval >= 0 && restart_interval <= 65535, "ccedit_jpegdec_entropy: restart_interval=%d MCUs (0 ... 65535)",
+                 restart_interval);
+    CC_CHECK_ARG((double)N * (double)cc_jpegdec_intervals(H, W, ncomp, hs, vs, restart_interval) < (double)kPixelMax,
+                 "ccedit_jpegdec_entropy: N=%d frames hold more than 2^31 restart intervals", N);
+    CC_CHECK_ARG(((uintptr_t)coef & 15) == 0 && ((uintptr_t)intervals & 7) == 0 && (((uintptr_t)tables | (uintptr_t)status) & 3) == 0,
+                 "ccedit_jpegdec_entropy: coef must be 16-byte aligned, intervals 8-byte, tables and status 4-byte");
+    return cc_jpegdec_entropy((const uint8_t*)data, data_bytes, intervals, tables, (int16_t*)coef, status, N, H, W, ncomp, hs, vs,
+                              restart_interval, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_jpegdec_idct(const void* coef, const int32_t* tables, void* planes, int32_t N, int32_t H, int32_t W, int32_t ncomp,
+                                   int32_t hs, int32_t vs, void* stream) {
+    CC_CHECK_ARG(coef && tables && planes, "ccedit_jpegdec_idct: null pointer");
+    if (int rc = jpegdec_shape_ok("ccedit_jpegdec_idct", N, H, W, ncomp, hs, vs)) return rc;
+    CC_CHECK_ARG(((uintptr_t)coef & 15) == 0 && ((uintptr_t)planes & 7) == 0 && ((uintptr_t)tables & 3) == 0,
+                 "ccedit_jpegdec_idct: coef must be 16-byte aligned, planes 8-byte, tables 4-byte");
+    return cc_jpegdec_idct((const int16_t*)coef, tables, (uint8_t*)planes, N, H, W, ncomp, hs, vs, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_jpegdec_rgb(const void* planes, void* out, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs,
+                                  void* stream) {
+    CC_CHECK_ARG(planes && out, "ccedit_jpegdec_rgb: null pointer");
+    if (int rc = jpegdec_shape_ok("ccedit_jpegdec_rgb", N, H, W, ncomp, hs, vs)) return rc;
+    return cc_jpegdec_rgb((const uint8_t*)planes, (uint8_t*)out, N, H, W, ncomp, hs, vs, (hipStream_t)stream);
+}

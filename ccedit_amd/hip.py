@@ -168,6 +168,13 @@ _SIGS = {
     "ccedit_mjpeg_pack_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ccedit_mjpeg_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int64, C.c_void_p]),
+    # JPEG decoding (csrc/jpegdec.hip): added within ABI 12, nothing existing changed
+    "ccedit_jpegdec_plane_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ccedit_jpegdec_entropy": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_jpegdec_idct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_void_p]),
+    "ccedit_jpegdec_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }
 KTH_WORKSPACE_BYTES_PER_ROW = 4128      # ccedit_kth_values: (prefix, rank) x 4 + 4 x 256 counters, uint32
 

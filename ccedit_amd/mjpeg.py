@@ -8,7 +8,8 @@ there is no host fallback.  This module is the ONE place of the constants: the f
 The kernels receive them as one int32 table (device_tables); the restatement imports them from here.
 
 The container is RIFF `AVI ` with one `MJPG` video stream, one `00dc` chunk per frame and an `idx1` index; read_avi walks the same
-structure and hands the chunks to Pillow, which is how an .avi becomes a video SOURCE of the entry points.
+structure, which is how an .avi becomes a video SOURCE of the entry points: decode_avi_u8 hands the chunks to Pillow on the host,
+decode_avi_device to the decoder on the GPU (ccedit_amd/jpegdec.py) — the same frames, byte for byte.
 """
 from __future__ import annotations
 
@@ -302,3 +303,36 @@ def decode_avi_u8(path: str) -> np.ndarray:
             raise ValueError(f"{path}: frame {i} is {a.shape[0]}x{a.shape[1]}, the stream header says {h}x{w}")
         frames.append(a)
     return np.stack(frames, axis=0)
+
+
+def parse_avi(path: str):
+    """An MJPG .avi -> (jpegs, their jpegdec.parse() results, H, W): every frame parsed ONCE and held to the stream header's size.
+    jpegdec.JpegUnsupported (naming file and frame): a frame outside the subset the device decodes."""
+    from . import jpegdec
+    jpegs, _, h, w = read_avi(path)
+    infos = []
+    for i, j in enumerate(jpegs):
+        try:
+            info = jpegdec.parse(j)
+        except jpegdec.JpegUnsupported as e:
+            raise jpegdec.JpegUnsupported(f"{path}: frame {i}: {e}") from e
+        if (info.height, info.width) != (h, w):
+            raise ValueError(f"{path}: frame {i} is {info.height}x{info.width}, the stream header says {h}x{w}")
+        infos.append(info)
+    return jpegs, infos, h, w
+
+
+def decode_avi_device(path: str, device, select=None):
+    """All frames of an MJPG .avi -> uint8 (N, H, W, 3) on `device`, decoded there (ccedit_amd/jpegdec.py): only the compressed bytes go
+    up.  The frames equal decode_avi_u8's byte for byte.  `select`: number of frames -> the indices to decode (every frame is still
+    parsed, so that a file goes one way as a whole).  jpegdec.JpegUnsupported: a frame outside the subset the device decodes.
+    Corrupt entropy-coded data, which Pillow decodes with a warning, is a ValueError naming file, frame and restart interval."""
+    from . import jpegdec
+    jpegs, infos, _, _ = parse_avi(path)
+    pick = range(len(jpegs)) if select is None else [int(i) for i in select(len(jpegs))]
+    try:
+        return jpegdec.decode([jpegs[i] for i in pick], device, infos=[infos[i] for i in pick])
+    except jpegdec.JpegUnsupported:
+        raise
+    except ValueError as e:
+        raise ValueError(f"{path}: {'' if select is None else 'selected '}{e}") from e

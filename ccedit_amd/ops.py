@@ -1102,3 +1102,71 @@ def mjpeg_pack(segments: torch.Tensor, seg_len: torch.Tensor, seg_off: torch.Ten
     hip.check(hip.lib().ccedit_mjpeg_pack(segments.data_ptr(), seg_len.data_ptr(), seg_off.data_ptr(), header.data_ptr(), out.data_ptr(), frames, h, w,
                                           header.numel(), int(out_bytes), _stream()), "ccedit_mjpeg_pack")
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# JPEG decoding (csrc/jpegdec.hip; the parser, the tables and the frame loop: ccedit_amd/jpegdec.py)
+# ------------------------------------------------------------------------------------------
+JPEGDEC_TABLE_WORDS = 3416
+
+
+def jpegdec_plane_bytes(h: int, w: int, ncomp: int, hs: int, vs: int) -> int:
+    n = int(hip.lib().ccedit_jpegdec_plane_bytes(int(h), int(w), int(ncomp), int(hs), int(vs)))
+    if n < 0:
+        hip.check(n, "ccedit_jpegdec_plane_bytes")
+    return n
+
+
+def _jpegdec_counts(h: int, w: int, ncomp: int, hs: int, vs: int, restart_interval: int):
+    """-> (blocks per frame, restart intervals per frame)"""
+    if ncomp == 1:
+        hs = vs = 1
+    mcus = -(-w // (8 * hs)) * -(-h // (8 * vs))
+    return mcus * (1 if ncomp == 1 else hs * vs + 2), (-(-mcus // restart_interval) if restart_interval else 1)
+
+
+def jpegdec_entropy(data: torch.Tensor, intervals: torch.Tensor, tables: torch.Tensor, frames: int, h: int, w: int, ncomp: int, hs: int, vs: int,
+                    restart_interval: int):
+    """entropy-coded bytes (uint8 (B,)) and each restart interval's [start, end) in them (int64 (N * I, 2)) -> (coef int16 (N, blocks, 64):
+    MCU order, natural order inside a block; status int32 (N, I): 0, or why the interval stopped)."""
+    _chk_u8(data, "jpegdec_entropy: data", 1)
+    _chk_i32(tables, "jpegdec_entropy: tables", (JPEGDEC_TABLE_WORDS,))
+    if not (0 <= int(restart_interval) <= 65535) or int(frames) < 1:
+        raise ValueError(f"jpegdec_entropy: frames={frames} (>= 1), restart_interval={restart_interval} (0 ... 65535)")
+    jpegdec_plane_bytes(h, w, ncomp, hs, vs)                # (checks the geometry)
+    blocks, per = _jpegdec_counts(h, w, ncomp, hs, vs, int(restart_interval))
+    if (intervals.dtype != torch.int64 or not intervals.is_cuda or not intervals.is_contiguous() or tuple(intervals.shape) != (frames * per, 2)
+            or data.numel() < 1):
+        raise ValueError(f"jpegdec_entropy: intervals: expected a contiguous cuda int64 tensor {(frames * per, 2)} and at least one byte of data, "
+                         f"got {intervals.dtype} {tuple(intervals.shape)}, {data.numel()} bytes")
+    coef = torch.empty((frames, blocks, 64), dtype=torch.int16, device=data.device)
+    status = torch.empty((frames, per), dtype=torch.int32, device=data.device)
+    hip.check(hip.lib().ccedit_jpegdec_entropy(data.data_ptr(), data.numel(), intervals.data_ptr(), tables.data_ptr(), coef.data_ptr(),
+                                               status.data_ptr(), int(frames), int(h), int(w), int(ncomp), int(hs), int(vs), int(restart_interval),
+                                               _stream()), "ccedit_jpegdec_entropy")
+    return coef, status
+
+
+def jpegdec_idct(coef: torch.Tensor, tables: torch.Tensor, h: int, w: int, ncomp: int, hs: int, vs: int) -> torch.Tensor:
+    """coef (N, blocks, 64) -> the component planes uint8 (N, plane_bytes): luma, Cb, Cr, each padded to whole MCUs."""
+    _chk_i32(tables, "jpegdec_idct: tables", (JPEGDEC_TABLE_WORDS,))
+    pb = jpegdec_plane_bytes(h, w, ncomp, hs, vs)
+    blocks, _ = _jpegdec_counts(h, w, ncomp, hs, vs, 0)
+    if coef.dtype != torch.int16 or not coef.is_cuda or not coef.is_contiguous() or coef.dim() != 3 or tuple(coef.shape[1:]) != (blocks, 64):
+        raise ValueError(f"jpegdec_idct: expected contiguous cuda int16 coefficients (N, {blocks}, 64), got {coef.dtype} {tuple(coef.shape)}")
+    planes = torch.empty((coef.shape[0], pb), dtype=torch.uint8, device=coef.device)
+    hip.check(hip.lib().ccedit_jpegdec_idct(coef.data_ptr(), tables.data_ptr(), planes.data_ptr(), coef.shape[0], int(h), int(w), int(ncomp), int(hs),
+                                            int(vs), _stream()), "ccedit_jpegdec_idct")
+    return planes
+
+
+def jpegdec_rgb(planes: torch.Tensor, h: int, w: int, ncomp: int, hs: int, vs: int) -> torch.Tensor:
+    """planes (N, plane_bytes) -> uint8 frames (N, H, W, 3)."""
+    _chk_u8(planes, "jpegdec_rgb: planes", 2)
+    pb = jpegdec_plane_bytes(h, w, ncomp, hs, vs)
+    if planes.shape[1] != pb or planes.shape[0] < 1:
+        raise ValueError(f"jpegdec_rgb: planes {tuple(planes.shape)}, a frame of {h}x{w} has {pb} bytes of planes")
+    out = torch.empty((planes.shape[0], int(h), int(w), 3), dtype=torch.uint8, device=planes.device)
+    hip.check(hip.lib().ccedit_jpegdec_rgb(planes.data_ptr(), out.data_ptr(), planes.shape[0], int(h), int(w), int(ncomp), int(hs), int(vs), _stream()),
+              "ccedit_jpegdec_rgb")
+    return out

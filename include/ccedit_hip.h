@@ -570,6 +570,43 @@ int ccedit_mjpeg_pack_scan(const int32_t* seg_len, int64_t* seg_off, int32_t* fr
 int ccedit_mjpeg_pack(const void* segments, const int32_t* seg_len, const int64_t* seg_off, const void* header, void* out, int32_t N, int32_t H,
                       int32_t W, int32_t hdr_len, int64_t out_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG decoding (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  The JPEG sources of the entry points
+ * (a directory of .jpg frames, a Motion-JPEG .avi) decoded on the device: the entropy-coded bytes of N baseline JPEG frames of ONE
+ * geometry and ONE set of tables -> uint8 frames [N][H][W][3].  ccedit_amd/jpegdec.py parses the streams on the host (markers, tables,
+ * where each restart interval lies) and refuses what is outside the subset before any call.  Kernels: csrc/jpegdec.hip; the entropy
+ * stage's decode core is csrc/jpegdec_core.h, plain C++ that a host program compiles too.  Everything is integer arithmetic and equals
+ * tests/_jpegdec_numpy.py byte for byte, which equals libjpeg(-turbo)'s accurate integer IDCT, "fancy" up-sampling and YCbCr -> RGB.
+ *
+ * Geometry: H, W 1 ... 65520; ncomp 1 (greyscale; hs and vs are ignored, a one-component scan is not interleaved) or 3 (YCbCr, luma
+ * sampling hs x vs = 1x1, 2x1 or 2x2, chroma 1x1).  An MCU is 8 hs x 8 vs pixels: hs * vs luma blocks (row by row), then Cb, then Cr.
+ * restart_interval: MCUs per restart interval, 0 = the whole frame is one interval.  I = intervals per frame = ceil(MCUs / interval).
+ * One call takes N frames of fewer than 2^31 pixels, 2^31 blocks and 2^33 bytes of planes in all (what one launch per stage can index);
+ * ccedit_amd/jpegdec.py cuts a clip into calls far below that.
+ * `tables`: int32 [3416] from ccedit_amd/jpegdec.py (table_array: [0] quantisation tables 3 x 64 per COMPONENT in natural order, 0 ... 255;
+ * [192] six selectors, the DC table of component 0 1 2 and the AC table of component 0 1 2, each 0 or 1; [200] four Huffman tables DC 0,
+ * DC 1, AC 0, AC 1 of 804 words: lut [512] by the next 9 bits, length << 8 | symbol; maxcode [18] by length, -1 = none; valoff [18];
+ * values [256]).  It is device data: every value that becomes an index is masked to its table.
+ *
+ * ccedit_jpegdec_plane_bytes: bytes of one frame's component planes (padded to whole MCUs: luma, then Cb, Cr), a multiple of 64;
+ *   -1 for a geometry outside the above.
+ * ccedit_jpegdec_entropy: data (data_bytes bytes) holds the entropy-coded bytes; intervals int64 [N * I][2] are the [start, end) of each
+ *   restart interval in it (clamped into the buffer by the kernel).  One thread per interval decodes its MCUs into coef, int16
+ *   [N][blocks][64] in MCU order, natural (row-major) order inside a block, 16-byte aligned, zeroed by the call itself; the DC prediction
+ *   starts at 0 in every interval.  status int32 [N * I]: 0, or why the interval stopped (1 invalid Huffman code, 2 the data ends before
+ *   the interval's blocks do, 3 a coefficient index passes 63, 4 DC size category above 11).  No read leaves [start, end), no write
+ *   leaves the interval's blocks, whatever the bytes are.
+ * ccedit_jpegdec_idct: coef -> planes uint8 [N][plane_bytes], 8-byte aligned: dequantisation, inverse DCT, level shift, clamp.
+ * ccedit_jpegdec_rgb: planes -> out uint8 [N][H][W][3]: chroma up-sampling over the component's real size (ceil(W / hs) x ceil(H / vs)),
+ *   YCbCr -> RGB; greyscale is replicated to the three channels.
+ */
+int64_t ccedit_jpegdec_plane_bytes(int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs);
+int ccedit_jpegdec_entropy(const void* data, int64_t data_bytes, const int64_t* intervals, const int32_t* tables, void* coef, int32_t* status,
+                           int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int32_t restart_interval, void* stream);
+int ccedit_jpegdec_idct(const void* coef, const int32_t* tables, void* planes, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs,
+                        int32_t vs, void* stream);
+int ccedit_jpegdec_rgb(const void* planes, void* out, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -273,9 +273,66 @@ def load_vae_file(model, vae_path: str) -> None:
 
 # ------------------------------------------------------------------------------------------
 # frame / video I/O: reference scripts/sampling/util.py:288-382, 689-762
-# Image files, GIFs and the JPEG frames of a Motion-JPEG .avi (ccedit_amd/mjpeg.py: read_avi walks the container) go through Pillow;
+# Image files, GIFs and the JPEG frames of a Motion-JPEG .avi (ccedit_amd/mjpeg.py: read_avi walks the container) go through Pillow on
+# the host route.  With a device, .jpg / .jpeg files and .avi frames are decoded THERE (ccedit_amd/jpegdec.py: the same bytes as Pillow's);
+# a file outside the subset the device decodes goes through Pillow as before, with one line on stderr per clip.
 # mp4 needs a codec library (decord / cv2 / imageio-ffmpeg) that is not installed here and raises.
 # ------------------------------------------------------------------------------------------
+_JPEG_EXT = (".jpg", ".jpeg")
+
+
+def _jpeg_files_u8_device(paths, device, what: str):
+    """The image files `paths` -> list of uint8 (1, h, w, 3) tensors on `device`, or None when they go through Pillow as before: not all
+    of them are .jpg / .jpeg, or the parser refuses one (one line on stderr names it), or one is not a three-component JPEG
+    (_decode_rgb_u8 takes RGB images only, and says so).  Each file is parsed once.  Corrupt entropy-coded data, which Pillow decodes
+    with a warning, is a ValueError here, naming file, frame and interval."""
+    import sys
+    from ccedit_amd import jpegdec
+    if not paths or not all(p.lower().endswith(_JPEG_EXT) for p in paths):
+        return None
+    datas, infos = [], []
+    for p in paths:
+        with open(p, "rb") as f:
+            datas.append(f.read())
+        try:
+            infos.append(jpegdec.parse(datas[-1]))
+        except jpegdec.JpegUnsupported as e:
+            sys.stderr.write(f"[jpegdec] {what}: {os.path.basename(p)}: {e}; this clip is decoded by Pillow on the host\n")
+            return None
+        if infos[-1].ncomp != 3:
+            return None
+    try:
+        if len({(i.height, i.width) for i in infos}) == 1:
+            return [jpegdec.decode(datas, device, infos=infos)]
+        return [jpegdec.decode([d], device, infos=[i]) for d, i in zip(datas, infos)]
+    except jpegdec.JpegUnsupported:
+        raise
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from e
+
+
+def _avi_u8_device(video_path: str, device, select=None):
+    """The frames of an MJPG .avi (all, or those at the indices select(number of frames)) -> uint8 (N, h, w, 3) on `device`, decoded
+    there; only they are decoded, but every frame is parsed, so that a clip goes ONE way as a whole: None when the parser refuses
+    any frame (one line on stderr names it), and the clip then goes through Pillow as before."""
+    import sys
+    from ccedit_amd import jpegdec, mjpeg
+    try:
+        return mjpeg.decode_avi_device(video_path, device, select)
+    except jpegdec.JpegUnsupported as e:
+        sys.stderr.write(f"[jpegdec] {e}; this clip is decoded by Pillow on the host\n")
+        return None
+
+
+def _u8_to_float_device(groups, size) -> torch.Tensor:
+    """uint8 (n, h, w, 3) tensors on the device -> fp32 (T, 3, H, W) in [-1, 1]: what _frames_to_device does after its upload."""
+    from ccedit_amd import ops
+    if len(groups) > 1:
+        assert size, "frames of different sizes need a target size"
+    out = [ops.resize_u8_pil(g.contiguous(), size or tuple(g.shape[1:3]), to_float=True) for g in groups]
+    return (out[0] if len(out) == 1 else torch.cat(out, dim=1)).permute(1, 0, 2, 3)
+
+
 def _decode_rgb_u8(path: str) -> np.ndarray:
     """Image file -> uint8 (H, W, 3) on the host (the decode is Pillow's on both routes)."""
     from PIL import Image
@@ -301,11 +358,14 @@ def _frames_to_device(frames, size, device) -> torch.Tensor:
 
 def load_img(p_cond_img: str, size: tuple = None, device=None) -> torch.Tensor:
     """util.py:360-382: image file -> (1, 3, H, W) in [-1, 1], optional bicubic resize to size = (H, W).
-    device=None: Pillow and torch on the host, as the reference.  With a device the decoded uint8 image is uploaded and resized /
-    scaled there (same values, bit for bit)."""
+    device=None: Pillow and torch on the host, as the reference.  With a device a .jpg / .jpeg file is decoded there (ccedit_amd/jpegdec.py),
+    any other image is decoded by Pillow and uploaded as uint8; either is resized / scaled there (same values, bit for bit)."""
     if device is not None:
         if size:
             assert len(size) == 2, "size should be (H, W)"
+        on_device = _jpeg_files_u8_device([p_cond_img], device, p_cond_img)
+        if on_device is not None:
+            return _u8_to_float_device(on_device, size)
         return _frames_to_device([_decode_rgb_u8(p_cond_img)], size, device)
     from PIL import Image
     img = Image.open(p_cond_img)
@@ -370,18 +430,29 @@ def _decode_video_u8(video_path: str) -> np.ndarray:
 
 def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
     """(not in the reference) ALL frames of what load_video_keyframes reads -> uint8 (F, H, W, 3) on `device` at size = (H, W): the
-    source side of --propagate.  Decoding stays on the host (Pillow); the frames reach the output size by the routes of the keyframes —
-    image files by Pillow's 8-bit bicubic (ops.resize_u8_pil), .gif frames by the fp32 bicubic of F.interpolate and then the nearest
-    byte (ops.resize_bicubic, ops.frames_to_u8 with rounding)."""
+    source side of --propagate.  JPEG sources (a directory of .jpg / .jpeg files, the frames of an .avi) are decoded on the device
+    (ccedit_amd/jpegdec.py: only the compressed bytes go up; Pillow's bytes exactly); everything else, and a JPEG the device decoder
+    refuses, is decoded by Pillow on the host and uploaded.  The frames reach the output size by the routes of the keyframes —
+    image files by Pillow's 8-bit bicubic (ops.resize_u8_pil), .gif and .avi frames by the fp32 bicubic of F.interpolate and then the
+    nearest byte (ops.resize_bicubic, ops.frames_to_u8 with rounding)."""
     from ccedit_amd import ops
     assert device is not None and size and len(size) == 2, "load_video_frames_u8 works on a device, size should be (H, W)"
     if os.path.isdir(video_path):
-        frames = [_decode_rgb_u8(os.path.join(video_path, f)) for f in sorted(os.listdir(video_path))]
+        files = sorted(os.listdir(video_path))
+        on_device = _jpeg_files_u8_device([os.path.join(video_path, f) for f in files], device, video_path)
+        if on_device is not None:
+            out = [ops.resize_u8_pil(g.contiguous(), size) for g in on_device]
+            return out[0] if len(out) == 1 else torch.cat(out, dim=0)
+        frames = [_decode_rgb_u8(os.path.join(video_path, f)) for f in files]
         groups = [np.stack(frames, axis=0)] if len({f.shape for f in frames}) == 1 else [f[None] for f in frames]
         out = [ops.resize_u8_pil(torch.from_numpy(np.ascontiguousarray(g)).to(device), size) for g in groups]
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
     if _is_frame_file(video_path):
-        x = _frames_to_device(list(_decode_video_u8(video_path)), None, device).contiguous()     # (F, 3, h, w) in [-1, 1]
+        on_device = _avi_u8_device(video_path, device) if video_path.endswith(".avi") else None
+        if on_device is not None:
+            x = _u8_to_float_device([on_device], None).contiguous()
+        else:
+            x = _frames_to_device(list(_decode_video_u8(video_path)), None, device).contiguous()     # (F, 3, h, w) in [-1, 1]
         x = ops.resize_bicubic(x, size)
         return ops.frames_to_u8(x.permute(1, 0, 2, 3)[None].contiguous(), rounding=True)[0]
     if video_path.endswith(".mp4"):
@@ -418,18 +489,29 @@ def save_avi_u8(save_path: str, frames, fps: int, quality: int = 90) -> str:
 def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None,
                          device=None) -> torch.Tensor:
     """util.py:689-762: directory of frame images, a .gif or a Motion-JPEG .avi -> keyframes (T, 3, H, W) in [-1, 1].
-    device=None: everything on the host, as the reference.  With a device, decoding stays on the host (Pillow, uint8); the keyframes
-    are uploaded once as uint8 and resized / scaled by the kernels of ccedit_amd/csrc/pixel.hip: image files exactly as on the
-    host (Pillow's 8-bit bicubic), .gif frames by the fp32 bicubic of F.interpolate (equal to fp32 rounding)."""
+    device=None: everything on the host, as the reference.  With a device, JPEG sources (.jpg / .jpeg files, the frames of an .avi) are
+    decoded there (ccedit_amd/jpegdec.py: only the compressed bytes go up, the frames are Pillow's byte for byte); everything else, and
+    a JPEG the device decoder refuses, is decoded by Pillow on the host and uploaded once as uint8.  Either way the keyframes are
+    resized / scaled by the kernels of ccedit_amd/csrc/pixel.hip: image files exactly as on the host (Pillow's 8-bit bicubic), .gif
+    and .avi frames by the fp32 bicubic of F.interpolate (equal to fp32 rounding)."""
     if device is not None and size:
         assert len(size) == 2, "size should be (H, W)"
     if os.path.isdir(video_path):
         files = sorted(os.listdir(video_path))
         idx = keyframe_indices(len(files), original_fps, target_fps, num_keyframes)
         if device is not None:
+            on_device = _jpeg_files_u8_device([os.path.join(video_path, files[i]) for i in idx], device, video_path)
+            if on_device is not None:
+                return _u8_to_float_device(on_device, size)
             return _frames_to_device([_decode_rgb_u8(os.path.join(video_path, files[i])) for i in idx], size, device)
         return torch.cat([load_img(os.path.join(video_path, files[i]), size) for i in idx], dim=0)
     if _is_frame_file(video_path):
+        if device is not None and video_path.endswith(".avi"):
+            from ccedit_amd import ops
+            on_device = _avi_u8_device(video_path, device, lambda n: keyframe_indices(n, original_fps, target_fps, num_keyframes))
+            if on_device is not None:
+                x = _u8_to_float_device([on_device], None).contiguous()
+                return ops.resize_bicubic(x, size) if size else x
         frames = _decode_video_u8(video_path)
         if device is not None:
             from ccedit_amd import ops
