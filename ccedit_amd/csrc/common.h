@@ -84,6 +84,7 @@ struct CcPolicy {
     int g8_conv = 1;        // ... its tap-gather mode for 3x3 convs onto >= 1024 channels
     int g8_temporal = 1;    // ... and for Conv1d k3 over T at >= 640 channels
     int g8_split = -1;      // split-K at the 8x12 level: -1 auto, 0 off, n fixed
+    int g8_mfma16 = 1;      // ... its K loop on v_mfma_f32_16x16x32_bf16 (0: 32x32x16; 1 and 2 select the same kernels, 2 is what tests set)
     int lin320 = 1;         // register-resident-weight K = 320 Linears (0: tap_gemm)
     int lin320s = 1;        // ... the streaming deep-ring variant (0: the K-split kernel)
     int lin640 = 1;         // streaming K = 640 Linears (0: g8)

@@ -61,7 +61,7 @@ struct PolicyEntry {
 };
 const PolicyEntry kPolicy[] = {
     {"conv_halo", &CcPolicy::conv_halo},     {"g8", &CcPolicy::g8},           {"g8_conv", &CcPolicy::g8_conv},
-    {"g8_temporal", &CcPolicy::g8_temporal}, {"g8_split", &CcPolicy::g8_split}, {"lin320", &CcPolicy::lin320},
+    {"g8_temporal", &CcPolicy::g8_temporal}, {"g8_split", &CcPolicy::g8_split}, {"g8_mfma16", &CcPolicy::g8_mfma16}, {"lin320", &CcPolicy::lin320},
     {"lin320s", &CcPolicy::lin320s},         {"lin640", &CcPolicy::lin640},   {"temp320", &CcPolicy::temp320},
     {"attn_short", &CcPolicy::attn_short},   {"attn_text", &CcPolicy::attn_text}, {"attn_spatial", &CcPolicy::attn_spatial},
     {"attn_pv16", &CcPolicy::attn_pv16},     {"attn_opt", &CcPolicy::attn_opt},       {"gn_flat", &CcPolicy::gn_flat}, {"gn_apply_flat", &CcPolicy::gn_apply_flat},

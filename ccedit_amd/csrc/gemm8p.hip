@@ -199,9 +199,24 @@ __device__ __forceinline__ size_t g8_out_row(const CcGemmDesc& d, int64_t m) {  
 //     W' xhat + b' = rstd (W' x - mean W' 1) + b'
 // so the accumulators start at b' / rstd - mean * colsum(W') and the epilogue multiplies by rstd: `to_q(norm(x))`, the GEGLU
 // projection of `ff(norm(x))` (attention.py:695-716) without the normalised tensor ever being written or read.
-template <int TIH, int TJH, int EPI, int GATHER, int SPLIT = 0, int LNF = 0>
+//
+// MF16 = 1 (policy g8_mfma16): the same tiles, LDS image, staging and phases with the K loop on v_mfma_f32_16x16x32_bf16 — the
+// chip holds a higher clock under that shape.  A 32-row band is two 16-row sub-tiles x two k-steps of 32:
+// again four ds_read_b128 per band.  A 32 x 32 accumulator block is four f32x4, quad 2 a + b = channel sub-tile a x pixel sub-tile
+// b; a lane owns pixels 16 b + lane % 16 and channels 16 a + 4 (lane / 16) + e of it (2 pixels x 2 channel quads; 1 x 4 for
+// MF16 = 0).  Only init_acc, ln_rstd and the staging writes of the epilogues know that map; k is summed in groups of 32, not 16.
+template <int MF16>
+struct G8Acc {
+    f32x16 v;
+};
+template <>
+struct G8Acc<1> {
+    f32x4 v[4];
+};
+
+template <int TIH, int TJH, int EPI, int GATHER, int SPLIT = 0, int LNF = 0, int MF16 = 0>
 __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
-    static_assert(TIH * TJH == 2, "eight MFMAs per phase");
+    static_assert(TIH * TJH == 2, "two 32 x 32 accumulator blocks per phase: 8 MFMAs of 32x32x16 or 16 of 16x16x32");
     constexpr int BM = TIH * 128, BN = TJH * 256;
     constexpr int AH = TIH * 8192, BH = TJH * 16384;          // bytes of an A / B half tile (128-byte rows)
     constexpr int BUF = 2 * AH + 2 * BH;                      // [A0 | A1 | B0 | B1]
@@ -216,6 +231,12 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     const int l31 = lane & 31, hi = lane >> 5;
+    const int l15 = lane & 15, h4 = lane >> 4;           // MF16: pixel column / channel quad of the 16x16 accumulator layout
+    // MF16: first channel of this lane inside a 32-channel band, sub-tile a at + a * CSTEP.  GEGLU: the A request puts the 16
+    // value rows of a band into sub-tile 0 and their gates into sub-tile 1 (see a_row), so LDS row 16 a + 4 h4 + e holds packed row
+    // 16 (h4 / 2) + 8 a + 4 (h4 % 2) + e and a lane has a value and its gate at the same (h4, e) of quads b and 2 + b
+    const int crow0 = EPI == G8_GEGLU ? 16 * (h4 >> 1) + 4 * (h4 & 1) : 4 * h4;
+    constexpr int CSTEP = EPI == G8_GEGLU ? 8 : 16;
     const int nk_all = d.Kpad >> 6;
     const int flags = d.cgroup >> 24;           // tuning only: 1 = no output stores, 2 = next tile requested AFTER the epilogue
     const int S = SPLIT ? d.split_k : 1;
@@ -246,7 +267,10 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
     // LDS row rho = i * 64 + rsub of A half h belongs to wave row rho / (TIH * 32); it holds weight row (= output channel)
     //   wave_row * CW + h * (TIH * 32) + rho % (TIH * 32),   CW = 2 * TIH * 32 channels per wave row,
     // so that the 2 TIH row tiles a wave accumulates are CW CONSECUTIVE channels (whole 128-byte lines in the epilogue).
-    const int a_row = (rsub / (TIH * 32)) * CW + rsub % (TIH * 32);
+    // MF16 + GEGLU: 8-row groups 1 and 2 of every 32-row band change places (bits 3 and 4 of the row), so that a band's LDS rows are
+    // [values 0-7 | values 8-15 | gates 0-7 | gates 8-15].  Whole groups move: a 1 KB DMA piece is still eight whole 128-byte lines.
+    const int rsrc = (MF16 && EPI == G8_GEGLU) ? ((rsub & ~24) | ((rsub & 8) << 1) | ((rsub & 16) >> 1)) : rsub;
+    const int a_row = (rsrc / (TIH * 32)) * CW + rsrc % (TIH * 32);
     const uint32_t a_lane = ((uint32_t)a_row * (uint32_t)d.Kpad + gcol * 8) * 2;          // per-lane byte offset into W (issue 0, half 0)
     const char* const Wp = (const char*)d.W;
     const char* const Ap = (const char*)d.A;
@@ -258,7 +282,14 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
     const char* fb[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        const int off = l31 * 128 + (((2 * ks + hi) ^ sw) << 4);
+        // MF16: read ks = 2 a + ks2 is sub-tile a (rows 16 a + l15 of the band), k-step ks2 of 32: granule 4 ks2 + h4, same swizzle.
+        // Banks, enumerated on the CPU over the four 16-lane groups ds_read_b128 is served in ({0-3,12-15,20-27}, {4-11,16-19,
+        // 28-31} and the same + 32; bank = (address / 4) % 64): a group holds 8 rows of each parity for two values of h4; rows of one
+        // parity share a 128-byte half of the bank space, their 8 values of (r >> 1) & 7 are distinct, so are the granules
+        // (4 ks2 + h4) ^ ((r >> 1) & 7): 16 lanes x 16 bytes on 64 distinct banks — 1-way for both sub-tiles and both k-steps.
+        // (Row maps that interleave the sub-tiles, 16 (m >> 3) + 8 a + (m & 7), are 2-way.)
+        const int r16 = 16 * (ks >> 1) + l15;
+        const int off = MF16 ? r16 * 128 + (((4 * (ks & 1) + h4) ^ ((r16 >> 1) & 7)) << 4) : l31 * 128 + (((2 * ks + hi) ^ sw) << 4);
         fa[ks] = smem + wr * (TIH * 4096) + off;                 // A half h at + h * AH, row tile ti at + ti * 4096
         fb[ks] = smem + 2 * AH + wc * (TJH * 4096) + off;        // B half h at + h * BH, pixel tile tj at + tj * 4096
     }
@@ -386,7 +417,7 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
         }
         return *(const f32x2*)(d.ln_stats + 2 * m);
     };
-    f32x16 acc[NI][NJ];
+    G8Acc<MF16> acc[NI][NJ];
     auto pixbase = [&](int tjf) { return (tjf / TJH) * (TJH * 128) + wc * (TJH * 32) + (tjf % TJH) * 32; };
     auto init_acc = [&](int pt_, int ct_, bool with_bias = !SPLIT) {
         if (!with_bias) {           // split-K partial: the bias is the reducer's starting value
@@ -395,7 +426,52 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
 #pragma unroll
                 for (int tj = 0; tj < NJ; ++tj)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[tf][tj][e] = 0.f;
+                    for (int e = 0; e < 16; ++e) {
+                        if constexpr (MF16) acc[tf][tj].v[e >> 2][e & 3] = 0.f;
+                        else acc[tf][tj].v[e] = 0.f;
+                    }
+            return;
+        }
+        if constexpr (MF16) {
+            // quad 2 a + b of block (tf, tj): channels 32 tf + crow0 + a * CSTEP + e, pixel 16 b + l15 — eight 16-byte loads per
+            // vector (16 for MF16 = 0), and the start value of a LayerNorm-folded tile needs (mean, rstd) of two pixels per tile
+            float mean[LNF ? NJ : 1][2], invr[LNF ? NJ : 1][2];
+            if constexpr (LNF) {
+#pragma unroll
+                for (int tj = 0; tj < NJ; ++tj)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const f32x2 st = ln_row((int64_t)pt_ * BN + pixbase(tj) + 16 * b + l15);
+                        mean[tj][b] = st[0];
+                        invr[tj][b] = 1.0f / st[1];
+                    }
+            }
+            const float* const gbias = LNF ? nullptr : d.group_bias;
+            const int ldgb = d.ldgb ? d.ldgb : d.N;
+#pragma unroll
+            for (int tf = 0; tf < NI; ++tf)
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    const int c = min(ct_ * BM + wr * CW + 32 * tf + crow0 + a * CSTEP, d.N - 4);          // (past N: never stored)
+                    f32x4 bv = {0.f, 0.f, 0.f, 0.f}, cs = {0.f, 0.f, 0.f, 0.f};
+                    if (d.bias) bv = *(const f32x4*)(d.bias + c);
+                    if constexpr (LNF) cs = *(const f32x4*)(d.ln_colsum + c);
+#pragma unroll
+                    for (int tj = 0; tj < NJ; ++tj) {
+                        f32x4 v = bv;
+                        if (gbias) {          // a 32-pixel tile lies in ONE clip
+                            const int64_t m = min((int64_t)pt_ * BN + pixbase(tj), d.M - 1);
+                            const f32x4 gb = *(const f32x4*)(gbias + (size_t)(m / d.group_rows) * ldgb + c);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] += gb[e];
+                        }
+#pragma unroll
+                        for (int b = 0; b < 2; ++b)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                acc[tf][tj].v[2 * a + b][e] = LNF ? bv[e] * invr[LNF ? tj : 0][b] - mean[LNF ? tj : 0][b] * cs[e] : v[e];
+                    }
+                }
             return;
         }
         if constexpr (LNF) {
@@ -417,7 +493,7 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
 #pragma unroll
                     for (int tj = 0; tj < NJ; ++tj)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[tf][tj][4 * q + e] = b[e] * invr[tj] - mean[tj] * cs[e];
+                        for (int e = 0; e < 4; ++e) acc[tf][tj].v[4 * q + e] = b[e] * invr[tj] - mean[tj] * cs[e];
                 }
             return;
         }
@@ -437,13 +513,13 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
                         const int64_t m = min((int64_t)pt_ * BN + pixbase(tj), d.M - 1);
                         const f32x4 gb = *(const f32x4*)(gbias + (size_t)(m / d.group_rows) * ldgb + c);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[tf][tj][4 * q + e] = b[e] + gb[e];
+                        for (int e = 0; e < 4; ++e) acc[tf][tj].v[4 * q + e] = b[e] + gb[e];
                     }
                 } else {
 #pragma unroll
                     for (int tj = 0; tj < NJ; ++tj)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[tf][tj][4 * q + e] = b[e];
+                        for (int e = 0; e < 4; ++e) acc[tf][tj].v[4 * q + e] = b[e];
                 }
             }
     };
@@ -495,14 +571,32 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
             auto mma = [&](const bf16x8(&xf)[NX][4], int xh, int yh) {
                 const int ah = XA ? xh : yh, bh = XA ? yh : xh;
                 __builtin_amdgcn_s_setprio(1);
+                if constexpr (MF16) {
+                    // 16 MFMAs of 16x16x32 on the same operands: fragment 2 a + ks2 of a band is sub-tile a, k-step ks2.  The eight
+                    // accumulator quads of the phase in turn, then again for the second k-step: no back-to-back dependence
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks)
+                    for (int ks2 = 0; ks2 < 2; ++ks2)
 #pragma unroll
-                    for (int ti = 0; ti < TIH; ++ti)
+                        for (int ti = 0; ti < TIH; ++ti)
 #pragma unroll
-                        for (int tj = 0; tj < TJH; ++tj)
-                            acc[ah * TIH + ti][bh * TJH + tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                                XA ? xf[ti][ks] : y[ti][ks], XA ? y[tj][ks] : xf[tj][ks], acc[ah * TIH + ti][bh * TJH + tj], 0, 0, 0);
+                            for (int tj = 0; tj < TJH; ++tj)
+#pragma unroll
+                                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                                    for (int b = 0; b < 2; ++b)
+                                        acc[ah * TIH + ti][bh * TJH + tj].v[2 * a + b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                                            XA ? xf[ti][2 * a + ks2] : y[ti][2 * a + ks2], XA ? y[tj][2 * b + ks2] : xf[tj][2 * b + ks2],
+                                            acc[ah * TIH + ti][bh * TJH + tj].v[2 * a + b], 0, 0, 0);
+                } else {
+#pragma unroll
+                    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                        for (int ti = 0; ti < TIH; ++ti)
+#pragma unroll
+                            for (int tj = 0; tj < TJH; ++tj)
+                                acc[ah * TIH + ti][bh * TJH + tj].v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                                    XA ? xf[ti][ks] : y[ti][ks], XA ? y[tj][ks] : xf[tj][ks], acc[ah * TIH + ti][bh * TJH + tj].v, 0, 0, 0);
+                }
                 __builtin_amdgcn_s_setprio(0);
             };
             // phase 0: X half 0 (first: retired by the lgkmcnt before the barrier), Y half 0; request Y1 of tile t + 1
@@ -595,7 +689,10 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
                     for (int q = 0; q < 4; ++q) {
                         f32x4 v;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[tf][tj][4 * q + e];
+                        for (int e = 0; e < 4; ++e) {
+                            if constexpr (MF16) v[e] = acc[tf][tj].v[q][e];
+                            else v[e] = acc[tf][tj].v[4 * q + e];
+                        }
                         g8_store_agent(mine + ((tf * NJ + tj) * 4 + q) * 64, v);
                     }
             g8_vmcnt<0>();                                            // this wave's slot has left the CU (agent-scope stores) ...
@@ -620,7 +717,10 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
 #pragma unroll
                             for (int q = 0; q < 4; ++q)
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) acc[tf][tj][4 * q + e] += v[q][e];
+                                for (int e = 0; e < 4; ++e) {
+                                    if constexpr (MF16) acc[tf][tj].v[q][e] += v[q][e];
+                                    else acc[tf][tj].v[4 * q + e] += v[q][e];
+                                }
                         }
                 }
             }
@@ -643,8 +743,11 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
         const bool gn = d.gn_stats != nullptr;
 #endif
         auto gn_slots = [&](int tjf) { return d.gn_stats + (size_t)(min(pix0 + pixbase(tjf), d.M - 1) / d.gn_rows) * 64; };
-        float ln_rstd[LNF ? NJ : 1];                 // LNF: rstd of this lane's pixel of every pixel tile (the accumulators hold W' x / 1 - ...)
-        if constexpr (LNF) {
+        float ln_rstd[LNF ? NJ * (MF16 ? 2 : 1) : 1];   // LNF: rstd of this lane's pixel(s) of every pixel tile (the accumulators hold W' x / 1 - ...)
+        if constexpr (LNF && MF16) {                 // index 2 tj + b: pixel 16 b + l15
+#pragma unroll
+            for (int tj = 0; tj < 2 * NJ; ++tj) ln_rstd[tj] = ln_row(pix0 + pixbase(tj >> 1) + 16 * (tj & 1) + l15)[1];
+        } else if constexpr (LNF) {
 #pragma unroll
             for (int tj = 0; tj < NJ; ++tj) ln_rstd[tj] = ln_row(pix0 + pixbase(tj) + l31)[1];
         }
@@ -669,14 +772,34 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
             for (int tjf = 0; tjf < NJ; ++tjf) {
 #pragma unroll
                 for (int tf = 0; tf < NI; ++tf) {
+                    if constexpr (MF16) {
+                        // quad b holds values, quad 2 + b their gates (see crow0): outputs 16 tf + 4 h4 + e of pixel row pr = 16 b + l15,
+                        // i.e. granule 2 tf + h4 / 2, half h4 % 2 of the staged row.  Banks of the staging writes, enumerated on the CPU
+                        // for this and the plain epilogue (ds_write_b64: four groups of 16 consecutive lanes = one h4, 16 pixel rows; bank =
+                        // (address / 4) % 32): the 16 rows of a group take 16 / 8 / 4 distinct granules at RB = 256 / 128 / 64, all in the
+                        // same 8-byte half — 2-way, 2-way and 4-way, exactly what MF16 = 0 gets from 16 lanes of one `hi` (the swizzle
+                        // belongs to the layout-independent read side and stays).  The fp32 staging of the residual epilogue
+                        // (ds_write_b128: eight groups of 8 consecutive lanes, 8 rows with 8 distinct granules) is 1-way in both.
 #pragma unroll
-                    for (int gq = 0; gq < 2; ++gq) {
-                        bf16x4 o;
+                        for (int b = 0; b < 2; ++b) {
+                            const int pr = 16 * b + l15;
+                            bf16x4 o;
 #pragma unroll
-                        // (scalar fp32 GELU: the packed-fp32 form — v_pk_fma_f32 / v_pk_mul_f32, two values per issue slot — measured
-                        //  the same within noise in the same-box A/B, 852 / 885 vs 836 / 900 TF/s on 52224 x 5120 <- 640)
-                        for (int e = 0; e < 4; ++e) o[e] = f2bf(ln_mul(tjf, acc[tf][tjf][8 * gq + e]) * gelu_erf_f(ln_mul(tjf, acc[tf][tjf][8 * gq + 4 + e])));
-                        *(bf16x4*)(stg + l31 * RB + (((2 * tf + gq) ^ (l31 & (G - 1))) << 4) + hi * 8) = o;
+                            for (int e = 0; e < 4; ++e)
+                                o[e] = f2bf(ln_mul(2 * tjf + b, acc[tf][tjf].v[b][e]) * gelu_erf_f(ln_mul(2 * tjf + b, acc[tf][tjf].v[2 + b][e])));
+                            *(bf16x4*)(stg + pr * RB + (((2 * tf + (h4 >> 1)) ^ (pr & (G - 1))) << 4) + (h4 & 1) * 8) = o;
+                        }
+                    } else {
+#pragma unroll
+                        for (int gq = 0; gq < 2; ++gq) {
+                            bf16x4 o;
+#pragma unroll
+                            // (scalar fp32 GELU: the packed-fp32 form — v_pk_fma_f32 / v_pk_mul_f32, two values per issue slot — measured
+                            //  the same within noise in the same-box A/B, 852 / 885 vs 836 / 900 TF/s on 52224 x 5120 <- 640)
+                            for (int e = 0; e < 4; ++e)
+                                o[e] = f2bf(ln_mul(tjf, acc[tf][tjf].v[8 * gq + e]) * gelu_erf_f(ln_mul(tjf, acc[tf][tjf].v[8 * gq + 4 + e])));
+                            *(bf16x4*)(stg + l31 * RB + (((2 * tf + gq) ^ (l31 & (G - 1))) << 4) + hi * 8) = o;
+                        }
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -708,10 +831,16 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
                     for (int u = 0; u < 2; ++u)
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            f32x4 v;
+                            if constexpr (MF16) {
+                                // quad q = 2 a + b: channels 32 u + 16 a + 4 h4 .. + 3 of pixel row 16 b + l15 => granule 8 u + 4 a + h4
+                                const int pr = 16 * (q & 1) + l15;
+                                *(f32x4*)(stg + pr * 256 + (((8 * u + 4 * (q >> 1) + h4) ^ (pr & 15)) << 4)) = acc[2 * cs + u][tjf].v[q];
+                            } else {
+                                f32x4 v;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = acc[2 * cs + u][tjf][4 * q + e];
-                            *(f32x4*)(stg + l31 * 256 + (((8 * u + 2 * q + hi) ^ (l31 & 15)) << 4)) = v;
+                                for (int e = 0; e < 4; ++e) v[e] = acc[2 * cs + u][tjf].v[4 * q + e];
+                                *(f32x4*)(stg + l31 * 256 + (((8 * u + 2 * q + hi) ^ (l31 & 15)) << 4)) = v;
+                            }
                         }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -782,9 +911,17 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         bf16x4 o;
+                        if constexpr (MF16) {
+                            // quad q = 2 a + b: channels 32 tf + 16 a + 4 h4 .. + 3 of pixel row 16 b + l15 => granule 4 tf + 2 a + h4 / 2, half h4 % 2
+                            const int pr = 16 * (q & 1) + l15;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = f2bf(ln_mul(tjf, acc[tf][tjf][4 * q + e]));
-                        *(bf16x4*)(stg + l31 * RB + (((4 * tf + q) ^ (l31 & (G - 1))) << 4) + hi * 8) = o;
+                            for (int e = 0; e < 4; ++e) o[e] = f2bf(ln_mul(2 * tjf + (q & 1), acc[tf][tjf].v[q][e]));
+                            *(bf16x4*)(stg + pr * RB + (((4 * tf + (q & 2) + (h4 >> 1)) ^ (pr & (G - 1))) << 4) + (h4 & 1) * 8) = o;
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) o[e] = f2bf(ln_mul(tjf, acc[tf][tjf].v[4 * q + e]));
+                            *(bf16x4*)(stg + l31 * RB + (((4 * tf + q) ^ (l31 & (G - 1))) << 4) + hi * 8) = o;
+                        }
                     }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -833,17 +970,30 @@ __global__ __launch_bounds__(512) void g8_kernel(const CcGemmDesc d) {
         // those would be too, i.e. more than KEEP + 16 operations — so a count of at most KEEP + 12 (margin: the compiler may merge
         // bias loads) proves it has landed WITHOUT waiting for the epilogue's stores to be acknowledged (measured: ~1.5 us per tile).
         // Without a bias there is no such padding and the count is KEEP.
-        if (!SPLIT && (d.bias || d.group_bias)) g8_vmcnt<KEEP + 12>();          // (split-K partials start from zero: no bias loads)
+        // (The 12 assumes NI = 4, 16 bias loads: in the MF16 = 0 128ch x 512pix shape, NI = 2, a bias without a row bias gives only 8 and
+        //  the count proves nothing there — older than the MF16 arm and left alone, since that arm must stay instruction for
+        //  instruction; K tile 0 was requested a whole epilogue earlier.  MF16: 2 NI bias loads of 16 bytes, which cannot merge;
+        //  the margin of a quarter gives 6 < 8 and 3 < 4.)
+        if (!SPLIT && (d.bias || d.group_bias)) g8_vmcnt<KEEP + (MF16 ? (3 * NI) / 2 : 12)>();          // (split-K partials start from zero: no bias loads)
         else g8_vmcnt<KEEP>();
     }
 }
 
-template <int TIH, int TJH, int EPI, int GATHER, int SPLIT = 0, int LNF = 0>
+// Policy g8_mfma16: 0 = the K loop on 32x32x16 MFMAs, non-zero = on 16x16x32.  The isolated A/B (tools/exp/g8_mfma_ab.py,
+// profiles/g8_mfma16_ab.txt) found no arm class clearly slower on 16x16x32: the short-K temporal and
+// LayerNorm-folded 128ch x 512pix launches differ by 1-2 % either way, inside the spread of three rounds, so no arm is carved out and
+// values 1 and 2 select the same kernels (2 stays the spelling tests use for "every arm").
+static bool g8_use_mfma16() { return cc_policy().g8_mfma16 != 0; }
+
+template <int TIH, int TJH, int EPI, int GATHER, int SPLIT = 0, int LNF = 0, int MF16 = 0>
 int g8_launch_shape(const CcGemmDesc& d, hipStream_t s, int n_cu, int split_k = 1) {
+    if constexpr (!MF16) {
+        if (g8_use_mfma16()) return g8_launch_shape<TIH, TJH, EPI, GATHER, SPLIT, LNF, 1>(d, s, n_cu, split_k);
+    }
     constexpr int BM = TIH * 128, BN = TJH * 256;
     constexpr int LDS = 2 * (2 * TIH * 8192 + 2 * TJH * 16384) + (SPLIT ? 16 : 0);
     static unsigned long long attr_done = 0;
-    if (int rc = cc_max_dynamic_lds((const void*)g8_kernel<TIH, TJH, EPI, GATHER, SPLIT, LNF>, LDS, &attr_done, "g8_kernel")) return rc;
+    if (int rc = cc_max_dynamic_lds((const void*)g8_kernel<TIH, TJH, EPI, GATHER, SPLIT, LNF, MF16>, LDS, &attr_done, "g8_kernel")) return rc;
     const int64_t pt_n = (d.M + BN - 1) / BN, ct_n = (d.N + BM - 1) / BM;
     CcGemmDesc dd = d;
     dd.cgroup = 0;
@@ -879,7 +1029,7 @@ int g8_launch_shape(const CcGemmDesc& d, hipStream_t s, int n_cu, int split_k = 
         cc_note_kernel(GATHER == G8_TEMPORAL ? "g8_kernel %dch x %dpix, temporal taps, split-K" : (GATHER == G8_CONV3 ? "g8_kernel %dch x %dpix, 3x3 taps, split-K" : (GATHER == G8_SUBPIX ? "g8_kernel %dch x %dpix, upsample parity taps, split-K" : "g8_kernel %dch x %dpix, split-K")), BM, BN);
     else
         cc_note_kernel(GATHER == G8_TEMPORAL ? "g8_kernel %dch x %dpix, temporal taps" : (GATHER == G8_CONV3 ? "g8_kernel %dch x %dpix, 3x3 taps" : (GATHER == G8_SUBPIX ? "g8_kernel %dch x %dpix, upsample parity taps" : "g8_kernel %dch x %dpix")), BM, BN);
-    hipLaunchKernelGGL((g8_kernel<TIH, TJH, EPI, GATHER, SPLIT, LNF>), dim3((unsigned)wgs), dim3(512), LDS, s, dd);
+    hipLaunchKernelGGL((g8_kernel<TIH, TJH, EPI, GATHER, SPLIT, LNF, MF16>), dim3((unsigned)wgs), dim3(512), LDS, s, dd);
     return cc_launch_status("g8_kernel");
 }
 

@@ -46,6 +46,7 @@ TABLE = {
     "g8_conv": (1, "lib", "0: 3x3 convs onto >= 1024 channels not on the persistent kernel"),
     "g8_temporal": (1, "lib", "0: Conv1d k3 at >= 640 channels not on the persistent kernel"),
     "g8_split": (-1, "lib", "split-K at the 8x12 level: -1 auto, 0 off, n fixed"),
+    "g8_mfma16": (1, "lib", "0: the persistent kernel's K loop on 32x32x16 MFMAs instead of 16x16x32 (2: same as 1, the value tests set)"),
     "lin320": (1, "lib", "0: K = 320 Linears on tap_gemm"),
     "lin320s": (1, "lib", "0: the K-split lin320 kernel instead of the streaming one"),
     "lin640": (1, "lib", "0: K = 640 Linears on the persistent kernel"),
