@@ -609,6 +609,8 @@ def nhwc_to_ncthw(x: torch.Tensor, b: int, t: int, c: int) -> torch.Tensor:
     """(B*T, H, W, ld) bf16|fp32 -> fp32 (B, c, T, H, W) taking the first c channels."""
     assert x.is_cuda and x.is_contiguous() and x.ndim == 4
     n, h, w, ld = x.shape
+    if n != b * t or c > ld or c < 1:
+        raise ValueError(f"nhwc_to_ncthw: x {tuple(x.shape)} is not (b * t = {b} * {t}, h, w, >= c = {c})")
     y = torch.empty((b, c, t, h, w), dtype=torch.float32, device=x.device)
     hip.check(hip.lib().ccedit_nhwc_to_ncthw(x.data_ptr(), int(x.dtype == torch.float32), ld, y.data_ptr(), b, c, t, h, w,
                                              _stream()), "ccedit_nhwc_to_ncthw")
@@ -702,6 +704,10 @@ def embedding_lookup(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor) ->
 
 def gaussian_sample(moments: torch.Tensor, noise: torch.Tensor, zc: int, scale: float = 1.0) -> torch.Tensor:
     """moments: fp32 [frames*hw, >=2*zc] channels-last rows [mean | logvar]; noise: fp32 (frames, zc, h, w)."""
+    if not (moments.is_cuda and noise.is_cuda):
+        raise ValueError(f"gaussian_sample: moments on {moments.device}, noise on {noise.device}: both must be on the GPU")
+    if moments.dim() != 2 or moments.shape[1] < 2 * zc:
+        raise ValueError(f"gaussian_sample: moments {tuple(moments.shape)} has fewer than 2 * zc = {2 * zc} columns")
     assert moments.dtype == torch.float32 and noise.dtype == torch.float32 and noise.is_contiguous() and moments.stride(-1) == 1
     n, c, h, w = noise.shape
     assert c == zc and moments.shape[0] == n * h * w
@@ -723,6 +729,10 @@ def mask_blend(x: torch.Tensor, z: torch.Tensor, mask: torch.Tensor) -> torch.Te
 
 def cfg_denoise(x: torch.Tensor, eps2: torch.Tensor, sigma: float, scale: float) -> torch.Tensor:
     """x: fp32 latent (n elems); eps2: fp32 [2, n] (uncond first). -> denoised (guided) fp32."""
+    if not (x.is_cuda and eps2.is_cuda):
+        raise ValueError(f"cfg_denoise: x on {x.device}, eps2 on {eps2.device}: both must be on the GPU")
+    if eps2.numel() != 2 * x.numel():
+        raise ValueError(f"cfg_denoise: eps2 {tuple(eps2.shape)} does not hold two halves of x {tuple(x.shape)}")
     assert x.dtype == torch.float32 and eps2.dtype == torch.float32 and x.is_contiguous() and eps2.is_contiguous()
     den = torch.empty_like(x)
     hip.check(hip.lib().ccedit_cfg_denoise(x.data_ptr(), eps2.data_ptr(), den.data_ptr(), x.numel(), sigma, scale, _stream()),
@@ -731,7 +741,14 @@ def cfg_denoise(x: torch.Tensor, eps2: torch.Tensor, sigma: float, scale: float)
 
 
 def axpby(x: torch.Tensor, z: torch.Tensor, a: float, b: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    assert x.dtype == torch.float32 and z.dtype == torch.float32 and x.is_contiguous() and z.is_contiguous()
+    for name, tns in (("x", x), ("z", z), ("out", out)):
+        if tns is None:
+            continue
+        if not tns.is_cuda:
+            raise ValueError(f"axpby: {name} is on {tns.device}, not on the GPU")
+        if tns.numel() != x.numel() or tns.dtype != x.dtype:
+            raise ValueError(f"axpby: {name} {tuple(tns.shape)} {tns.dtype} does not match x {tuple(x.shape)} {x.dtype}")
+    assert x.dtype == torch.float32 and x.is_contiguous() and z.is_contiguous() and (out is None or out.is_contiguous())
     y = torch.empty_like(x) if out is None else out
     hip.check(hip.lib().ccedit_axpby(x.data_ptr(), z.data_ptr(), y.data_ptr(), x.numel(), a, b, _stream()), "ccedit_axpby")
     return y
@@ -739,7 +756,9 @@ def axpby(x: torch.Tensor, z: torch.Tensor, a: float, b: float, out: Optional[to
 
 def softmax_rows(s: torch.Tensor, cols: int, cols_pad: int, scale: float) -> torch.Tensor:
     """s: fp32 [rows, >= cols] -> bf16 [rows, cols_pad] = softmax(s[:, :cols] * scale), zero pad."""
-    assert s.dtype == torch.float32 and s.is_cuda and s.stride(-1) == 1
+    assert s.dtype == torch.float32 and s.is_cuda and s.dim() == 2 and s.stride(-1) == 1
+    if s.shape[1] < cols:
+        raise ValueError(f"softmax_rows: s {tuple(s.shape)} has fewer than cols = {cols} columns")
     p = torch.empty((s.shape[0], cols_pad), dtype=BF16, device=s.device)
     hip.check(hip.lib().ccedit_softmax_rows(s.data_ptr(), p.data_ptr(), s.shape[0], cols, cols_pad, s.stride(0), cols_pad,
                                             scale, _stream()), "ccedit_softmax_rows")
