@@ -242,9 +242,19 @@ def bound_silu(x):
     emu_silu checks the sum of it over every bf16 input."""
     x = x.to(F64)
     ref = ref_silu(x).abs()
-    # a result below 2^-126 is subnormal in bf16 as in fp32: no 8-bit significand there, and the hardware may flush it (the fp32
-    # emulation on subnormal bf16 inputs misses the two terms above by 256 x: the quantum of a bf16 subnormal is 2^-133)
-    return 2.0 ** -8 * ref + 2.0 ** -22 * x.abs() + torch.where(ref < 2.0 ** -126, 2.0 ** -126, 0.0)
+    return 2.0 ** -8 * ref + silu_f32_term(x) + flush_term(ref)
+
+
+def silu_f32_term(x):
+    """The fp32 share of bound_silu (derivation there): what silu_f's own arithmetic may add to a result BEFORE it is rounded to
+    the output format.  tests/_epilogue_ref.py uses it as the SiLU budget of the GEMM epilogues, which call the same silu_f."""
+    return 2.0 ** -22 * x.to(F64).abs()
+
+
+def flush_term(ref_abs):
+    """A result below 2^-126 is subnormal in bf16 as in fp32: no 8-bit significand there, and the hardware may flush it (the fp32
+    emulation on subnormal bf16 inputs misses the other terms by 256 x: the quantum of a bf16 subnormal is 2^-133)."""
+    return torch.where(ref_abs < 2.0 ** -126, 2.0 ** -126, 0.0)
 
 
 def emu_silu(x, ieee_div=False):
