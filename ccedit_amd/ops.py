@@ -563,9 +563,9 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: 
               kv_div: int = 1, kv_inner: int = 1, kv_outer_rows: Optional[int] = None, kv_inner_rows: int = 0,
               kv_seq_rows: int = 1, out: Optional[torch.Tensor] = None,
               seg1_len: int = 0, seg1_div: int = 1, seg1_mul: int = 0, seg1_add: int = 0, causal: bool = False,
-              q_log2: bool = False) -> torch.Tensor:
+              q_log2: bool = False, scale: Optional[float] = None) -> torch.Tensor:
     """q/k/v: 2-D row-major views [rows, >= heads*d] (may be column slices of a fused buffer).  q_log2: q already carries
-    d^-0.5 * log2(e) (folded into the to_q weights by the packer)."""
+    d^-0.5 * log2(e) (folded into the to_q weights by the packer).  scale: the softmax scale, None = d^-0.5 (ignored with q_log2)."""
     for tns in (q, k, v):
         assert tns.dtype == BF16 and tns.is_cuda and tns.stride(-1) == 1
     if out is None:
@@ -577,7 +577,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: 
     a.q_inner, a.q_outer_rows, a.q_inner_rows, a.q_seq_rows = q_inner, (lq if q_outer_rows is None else q_outer_rows), q_inner_rows, q_seq_rows
     a.kv_div, a.kv_inner = kv_div, kv_inner
     a.kv_outer_rows, a.kv_inner_rows, a.kv_seq_rows = (lk if kv_outer_rows is None else kv_outer_rows), kv_inner_rows, kv_seq_rows
-    a.scale = float(d) ** -0.5
+    a.scale = float(d) ** -0.5 if scale is None else float(scale)
     a.seg1_len, a.seg1_div, a.seg1_mul, a.seg1_add = seg1_len, seg1_div, seg1_mul, seg1_add
     a.causal = int(causal)
     a.flags = hip.ATTN_Q_LOG2 if q_log2 else 0

@@ -40,9 +40,24 @@ class Case:
         return f"{self.kernel} d={self.d}"
 
 
-def expected_kernel(case: Case) -> str:
+POLICY_DEFAULTS = dict(attn_short=1, attn_text=1, attn_spatial=1, attn_pv16=1, attn_opt=1)       # CcPolicy, common.h
+
+
+def expected_arm(case: Case, policy: dict = None) -> dict:
     """ccedit_attention's selection (attention.hip) with the applicability rules of attnshort.hip / attntext.hip / attnspatial.hip
-    restated under the default policy; the alignment conditions hold for every buffer `build` makes (asserted there)."""
+    restated from their literals, under `policy` (switches of ccedit_policy_set that differ from the defaults); the alignment
+    conditions hold for every buffer `build` makes (asserted there).  Besides the kernel: what decides the code path inside it.
+
+        kernel        label of ccedit_last_kernel without " d=..."
+        nw            waves per workgroup (32 query rows each)
+        buffers       K / V tiles in LDS: 1 (attn_kernel, Lk <= 64), 2 (its ring), 3 (the spatial ring), 0 = all keys staged at once
+        masked_tail   the last 64-key tile reaches past Lk (general / spatial); keys past Lk are masked (short: Lk < 32, text: Lk < 96)
+        block_order   "qtile": heads of a (batch, query tile) back to back (attn_kernel at Lk <= 128 without a leading segment, and
+                      the text kernel); "head": query tiles of a (batch, head) back to back; "pixel": the short kernel's persistent loop
+        opt, pv16     spatial kernel only: the optimistic first pass, the 16x16x32 PV product (d = 40)
+    """
+    pol = dict(POLICY_DEFAULTS, **(policy or {}))
+    assert set(pol) == set(POLICY_DEFAULTS)
     r = Rules(case.heads, case.d, **case.desc)
     c = case.heads * case.d
     plain_q = not r.q_log2
@@ -51,12 +66,23 @@ def expected_kernel(case: Case) -> str:
     text = (case.d in (40, 80) and 64 <= r.lk <= 96 and r.seg1_len == 0 and not r.causal and c % 320 == 0 and 32 % max(c // 320, 1) == 0
             and r.q_inner == 1 and r.q_seq_rows == 1 and r.q_outer_rows == r.lq and r.kv_inner == 1 and r.kv_seq_rows == 1
             and r.kv_outer_rows >= r.lk and r.batches % r.kv_div == 0 and r.kv_div * r.lq >= 2048)
-    spatial = case.d in (40, 80) and r.lq >= 1024 and r.lk >= 192 and not r.causal and r.seg1_len % 64 == 0
-    if plain_q and short:
-        return "attn_short_kernel"
-    if plain_q and text:
-        return "attn_text_kernel"
-    return "attn_spatial_kernel" if spatial else "attn_kernel"
+    spatial = ((case.d == 40 or (case.d == 80 and pol["attn_spatial"] == 1)) and r.lq >= 1024 and r.lk >= 192 and not r.causal
+               and r.seg1_len % 64 == 0)
+    if pol["attn_short"] and plain_q and short:
+        return dict(kernel="attn_short_kernel", nw=4, buffers=0, masked_tail=r.lk < 32, block_order="pixel")
+    if pol["attn_text"] and plain_q and text:
+        return dict(kernel="attn_text_kernel", nw=8, buffers=0, masked_tail=r.lk < 96, block_order="qtile")
+    if pol["attn_spatial"] and spatial:
+        return dict(kernel="attn_spatial_kernel", nw=8, buffers=3, masked_tail=r.lk % 64 != 0, block_order="head",
+                    opt=bool(pol["attn_opt"]), pv16=bool(pol["attn_pv16"]) and case.d == 40)
+    assert case.d in (8, 16, 32, 40, 64, 80, 128, 160), "head dim not instantiated"
+    nw = 1 if r.lq <= 32 else (8 if case.d <= 80 and r.lq >= 1024 else 4)
+    return dict(kernel="attn_kernel", nw=nw, buffers=1 if r.lk <= 64 else 2, masked_tail=r.lk % 64 != 0,
+                block_order="qtile" if r.lk <= 128 and r.seg1_len == 0 else "head")
+
+
+def expected_kernel(case: Case, policy: dict = None) -> str:
+    return expected_arm(case, policy)["kernel"]
 
 
 def _temporal(tl, tg, hw=12, clips=2, q_frames=None):

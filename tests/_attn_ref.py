@@ -12,6 +12,7 @@ and ccedit_amd/csrc/attention.hip literally, one row index at a time:
     head h                = columns [h * d, (h + 1) * d) of each view
     causal                = key j is visible to query i iff j <= i
     q_log2                = scores are q.k * ln 2 (q arrives in log2 units), no d^-0.5
+    scale                 = scores are q.k * scale; None: d^-0.5 (ignored with q_log2)
 
 `Rules` holds exactly these; tests/test_attn_ref.py derives classes from it that make one mistake each, to show that the cases of
 tests/test_attn_desc_gpu.py would notice it.
@@ -22,7 +23,7 @@ import torch
 
 _DEFAULTS = dict(q_inner=1, q_outer_rows=None, q_inner_rows=0, q_seq_rows=1, kv_div=1, kv_inner=1, kv_outer_rows=None,
                  kv_inner_rows=0, kv_seq_rows=1, out=None, seg1_len=0, seg1_div=1, seg1_mul=0, seg1_add=0, causal=False,
-                 q_log2=False)
+                 q_log2=False, scale=None)
 
 
 class Rules:
@@ -70,7 +71,9 @@ class Rules:
 
     # ---- scores ----
     def score_scale(self):
-        return math.log(2.0) if self.q_log2 else float(self.d) ** -0.5
+        if self.q_log2:
+            return math.log(2.0)
+        return float(self.d) ** -0.5 if self.scale is None else float(self.scale)
 
     def visible(self, i, j):
         return (not self.causal) or j <= i
