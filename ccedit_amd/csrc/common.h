@@ -194,3 +194,13 @@ int cc_jpegdec_entropy(const uint8_t* data, int64_t data_bytes, const int64_t* i
 int cc_jpegdec_idct(const int16_t* coef, const int32_t* tab, uint8_t* planes, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs,
                     int32_t vs, hipStream_t s);
 int cc_jpegdec_rgb(const uint8_t* planes, uint8_t* out, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, hipStream_t s);
+
+// GIF launchers (gif.hip); entry points and argument checks in core.cpp
+int64_t cc_gif_slot_bytes();
+int cc_gif_histogram(const uint8_t* frames, int64_t* moments, int32_t N, int32_t H, int32_t W, hipStream_t s);
+int cc_gif_palette(int64_t* moments, uint8_t* cells, uint8_t* palettes, int32_t N, hipStream_t s);
+int cc_gif_map(const uint8_t* frames, const uint8_t* cells, uint8_t* indices, int32_t N, int32_t H, int32_t W, hipStream_t s);
+int cc_gif_lzw(const uint8_t* indices, uint8_t* slots, int32_t* chunk_bits, int32_t N, int32_t H, int32_t W, int32_t chunk, hipStream_t s);
+int cc_gif_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t* frame_bytes, int32_t N, int32_t H, int32_t W, int32_t chunk, hipStream_t s);
+int cc_gif_pack(const uint8_t* slots, const int32_t* chunk_bits, const int64_t* chunk_off, uint8_t* out, int32_t N, int32_t H, int32_t W, int32_t chunk,
+                int64_t out_bytes, hipStream_t s);

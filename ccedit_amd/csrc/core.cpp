@@ -388,3 +388,73 @@ extern "C" int ccedit_jpegdec_rgb(const void* planes, void* out, int32_t N, int3
     if (int rc = jpegdec_shape_ok("ccedit_jpegdec_rgb", N, H, W, ncomp, hs, vs)) return rc;
     return cc_jpegdec_rgb((const uint8_t*)planes, (uint8_t*)out, N, H, W, ncomp, hs, vs, (hipStream_t)stream);
 }
+
+// ---- GIF (kernels and launchers: gif.hip).  Everything the host can see is checked here, before any HIP call; the chunk bit lengths and
+// offsets the pack functions read are device data and are held in range by the kernels themselves.
+static const int64_t kGifMaxPixels = (int64_t)1 << 24, kGifMaxChunks = (int64_t)1 << 22;
+static const int32_t kGifChunkMax = 3072, kGifMaxFrames = 65535;
+
+static int gif_shape_ok(const char* fn, int32_t N, int32_t H, int32_t W) {
+    CC_CHECK_ARG(N >= 1 && N <= kGifMaxFrames, "%s: N=%d frames (1 ... 65535)", fn, N);
+    CC_CHECK_ARG(H >= 1 && W >= 1 && H <= 65535 && W <= 65535 && (int64_t)H * W <= kGifMaxPixels,
+                 "%s: frames of %dx%d (H and W 1 ... 65535, H * W <= 2^24)", fn, H, W);
+    CC_CHECK_ARG((int64_t)N * H * W * 3 < kPixelMax * 4, "%s: N=%d frames of %dx%d are more than one call takes (2^33 bytes)", fn, N, H, W);
+    return CCEDIT_OK;
+}
+
+static int gif_chunk_ok(const char* fn, int32_t N, int32_t H, int32_t W, int32_t chunk) {
+    if (int rc = gif_shape_ok(fn, N, H, W)) return rc;
+    CC_CHECK_ARG(chunk >= 1 && chunk <= kGifChunkMax, "%s: chunk=%d pixels (1 ... 3072: a chunk's dictionary never reaches code 4095)", fn, chunk);
+    CC_CHECK_ARG((int64_t)N * (((int64_t)H * W + chunk - 1) / chunk) <= kGifMaxChunks, "%s: N=%d frames of %dx%d in chunks of %d pixels are more "
+                 "than 2^22 chunks", fn, N, H, W, chunk);
+    return CCEDIT_OK;
+}
+
+extern "C" int64_t ccedit_gif_slot_bytes(void) { return cc_gif_slot_bytes(); }
+
+extern "C" int ccedit_gif_histogram(const void* frames, int64_t* moments, int32_t N, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(frames && moments, "ccedit_gif_histogram: null pointer (frames and moments are required)");
+    if (int rc = gif_shape_ok("ccedit_gif_histogram", N, H, W)) return rc;
+    CC_CHECK_ARG(((uintptr_t)moments & 7) == 0, "ccedit_gif_histogram: moments must be 8-byte aligned");
+    return cc_gif_histogram((const uint8_t*)frames, moments, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_gif_palette(int64_t* moments, void* cells, void* palettes, int32_t N, void* stream) {
+    CC_CHECK_ARG(moments && cells && palettes, "ccedit_gif_palette: null pointer (moments, cells and palettes are required)");
+    CC_CHECK_ARG(N >= 1 && N <= kGifMaxFrames, "ccedit_gif_palette: N=%d frames (1 ... 65535)", N);
+    CC_CHECK_ARG(((uintptr_t)moments & 7) == 0, "ccedit_gif_palette: moments must be 8-byte aligned");
+    return cc_gif_palette(moments, (uint8_t*)cells, (uint8_t*)palettes, N, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_gif_map(const void* frames, const void* cells, void* indices, int32_t N, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(frames && cells && indices, "ccedit_gif_map: null pointer (frames, cells and indices are required)");
+    if (int rc = gif_shape_ok("ccedit_gif_map", N, H, W)) return rc;
+    return cc_gif_map((const uint8_t*)frames, (const uint8_t*)cells, (uint8_t*)indices, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_gif_lzw(const void* indices, void* slots, int32_t* chunk_bits, int32_t N, int32_t H, int32_t W, int32_t chunk, void* stream) {
+    CC_CHECK_ARG(indices && slots && chunk_bits, "ccedit_gif_lzw: null pointer (indices, slots and chunk_bits are required)");
+    if (int rc = gif_chunk_ok("ccedit_gif_lzw", N, H, W, chunk)) return rc;
+    CC_CHECK_ARG((((uintptr_t)slots | (uintptr_t)chunk_bits) & 3) == 0, "ccedit_gif_lzw: slots and chunk_bits must be 4-byte aligned");
+    return cc_gif_lzw((const uint8_t*)indices, (uint8_t*)slots, chunk_bits, N, H, W, chunk, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_gif_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t* frame_bytes, int32_t N, int32_t H, int32_t W,
+                                    int32_t chunk, void* stream) {
+    CC_CHECK_ARG(chunk_bits && chunk_off && frame_bytes, "ccedit_gif_pack_scan: null pointer");
+    if (int rc = gif_chunk_ok("ccedit_gif_pack_scan", N, H, W, chunk)) return rc;
+    CC_CHECK_ARG((((uintptr_t)chunk_bits | (uintptr_t)frame_bytes) & 3) == 0 && ((uintptr_t)chunk_off & 7) == 0,
+                 "ccedit_gif_pack_scan: chunk_bits and frame_bytes must be 4-byte aligned, chunk_off 8-byte");
+    return cc_gif_pack_scan(chunk_bits, chunk_off, frame_bytes, N, H, W, chunk, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_gif_pack(const void* slots, const int32_t* chunk_bits, const int64_t* chunk_off, void* out, int32_t N, int32_t H, int32_t W,
+                               int32_t chunk, int64_t out_bytes, void* stream) {
+    CC_CHECK_ARG(slots && chunk_bits && chunk_off && out, "ccedit_gif_pack: null pointer");
+    if (int rc = gif_chunk_ok("ccedit_gif_pack", N, H, W, chunk)) return rc;
+    CC_CHECK_ARG(out_bytes >= 1 && out_bytes < kPixelMax * 4, "ccedit_gif_pack: out_bytes=%lld (1 ... 2^33: the sum of frame_bytes)",
+                 (long long)out_bytes);
+    CC_CHECK_ARG((((uintptr_t)slots | (uintptr_t)chunk_bits | (uintptr_t)out) & 3) == 0 && ((uintptr_t)chunk_off & 7) == 0,
+                 "ccedit_gif_pack: slots, chunk_bits and out must be 4-byte aligned, chunk_off 8-byte");
+    return cc_gif_pack((const uint8_t*)slots, chunk_bits, chunk_off, (uint8_t*)out, N, H, W, chunk, out_bytes, (hipStream_t)stream);
+}

@@ -1189,3 +1189,114 @@ def jpegdec_rgb(planes: torch.Tensor, h: int, w: int, ncomp: int, hs: int, vs: i
     hip.check(hip.lib().ccedit_jpegdec_rgb(planes.data_ptr(), out.data_ptr(), planes.shape[0], int(h), int(w), int(ncomp), int(hs), int(vs), _stream()),
               "ccedit_jpegdec_rgb")
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# GIF output (csrc/gif.hip; constants, the frame loop and the container: ccedit_amd/gif.py)
+# ------------------------------------------------------------------------------------------
+def gif_slot_bytes() -> int:
+    from . import gif
+    n = int(hip.lib().ccedit_gif_slot_bytes())
+    if n != gif.SLOT_BYTES:
+        raise hip.HipLibraryError(f"ccedit_gif_slot_bytes: the library reserves {n} bytes per chunk, ccedit_amd/gif.py says {gif.SLOT_BYTES}")
+    return n
+
+
+def _gif_frames(frames: torch.Tensor, name: str):
+    from . import gif
+    _chk_u8(frames, name, 4)
+    n, h, w, c = frames.shape
+    if c != 3 or n < 1:
+        raise ValueError(f"{name}: RGB frames (N, H, W, 3), N >= 1, got {tuple(frames.shape)}")
+    gif.check_size(h, w)
+    return n, h, w
+
+
+def _gif_chunks(name: str, n: int, h: int, w: int, chunk: int) -> int:
+    from . import gif
+    gif.check_size(h, w)
+    if int(chunk) != chunk or not 1 <= int(chunk) <= gif.CHUNK or int(n) < 1:
+        raise ValueError(f"{name}: frames={n} (>= 1), chunk={chunk!r} pixels (an integer 1 ... {gif.CHUNK})")
+    return gif.chunks_of(h, w, chunk)
+
+
+def gif_histogram(frames: torch.Tensor) -> torch.Tensor:
+    """uint8 frames (N, H, W, 3) -> moments int64 (N, 5, 33, 33, 33): count, sum r, sum g, sum b, sum r^2 + g^2 + b^2 per cell
+    (r >> 3, g >> 3, b >> 3) at index cell + 1: a zero border."""
+    from . import gif
+    n, h, w = _gif_frames(frames, "gif_histogram")
+    moments = torch.empty((n, gif.MOMENTS, gif.SIDE, gif.SIDE, gif.SIDE), dtype=torch.int64, device=frames.device)
+    hip.check(hip.lib().ccedit_gif_histogram(frames.data_ptr(), moments.data_ptr(), n, h, w, _stream()), "ccedit_gif_histogram")
+    return moments
+
+
+def gif_palette(moments: torch.Tensor):
+    """moments (N, 5, 33, 33, 33), turned into their inclusive 3-D prefix sums IN PLACE -> (cells uint8 (N, 32, 32, 32): cell -> palette
+    index, palettes uint8 (N, 256, 3)): Wu's cuts, the rounded box means."""
+    from . import gif
+    if (moments.dtype != torch.int64 or not moments.is_cuda or not moments.is_contiguous() or moments.dim() != 5 or moments.shape[0] < 1
+            or tuple(moments.shape[1:]) != (gif.MOMENTS, gif.SIDE, gif.SIDE, gif.SIDE)):
+        raise ValueError(f"gif_palette: expected contiguous cuda int64 moments (N, {gif.MOMENTS}, {gif.SIDE}, {gif.SIDE}, {gif.SIDE}), got "
+                         f"{moments.dtype} {moments.device} {tuple(moments.shape)}")
+    n = moments.shape[0]
+    cells = torch.empty((n, gif.GRID, gif.GRID, gif.GRID), dtype=torch.uint8, device=moments.device)
+    palettes = torch.empty((n, gif.COLORS, 3), dtype=torch.uint8, device=moments.device)
+    hip.check(hip.lib().ccedit_gif_palette(moments.data_ptr(), cells.data_ptr(), palettes.data_ptr(), n, _stream()), "ccedit_gif_palette")
+    return cells, palettes
+
+
+def gif_map(frames: torch.Tensor, cells: torch.Tensor) -> torch.Tensor:
+    """frames (N, H, W, 3), cells (N, 32, 32, 32) -> indices uint8 (N, H, W)."""
+    from . import gif
+    n, h, w = _gif_frames(frames, "gif_map")
+    _chk_u8(cells, "gif_map: cells", 4)
+    if tuple(cells.shape) != (n, gif.GRID, gif.GRID, gif.GRID):
+        raise ValueError(f"gif_map: cells {tuple(cells.shape)} for {n} frames: expected {(n, gif.GRID, gif.GRID, gif.GRID)}")
+    indices = torch.empty((n, h, w), dtype=torch.uint8, device=frames.device)
+    hip.check(hip.lib().ccedit_gif_map(frames.data_ptr(), cells.data_ptr(), indices.data_ptr(), n, h, w, _stream()), "ccedit_gif_map")
+    return indices
+
+
+def gif_lzw(indices: torch.Tensor, chunk: Optional[int] = None):
+    """indices (N, H, W) -> (slots uint8 (N * C, slot_bytes), chunk_bits int32 (N * C,)): every chunk of `chunk` pixels (default: gif.CHUNK)
+    coded on its own."""
+    from . import gif
+    chunk = gif.CHUNK if chunk is None else chunk
+    _chk_u8(indices, "gif_lzw: indices", 3)
+    n, h, w = indices.shape
+    c = _gif_chunks("gif_lzw", n, h, w, chunk)
+    slots = torch.empty((n * c, gif_slot_bytes()), dtype=torch.uint8, device=indices.device)
+    chunk_bits = torch.empty((n * c,), dtype=torch.int32, device=indices.device)
+    hip.check(hip.lib().ccedit_gif_lzw(indices.data_ptr(), slots.data_ptr(), chunk_bits.data_ptr(), n, h, w, int(chunk), _stream()), "ccedit_gif_lzw")
+    return slots, chunk_bits
+
+
+def gif_pack_scan(chunk_bits: torch.Tensor, frames: int, h: int, w: int, chunk: Optional[int] = None):
+    """-> (chunk_off int64 (N * C,): every chunk's bit offset in the packed output, frame_bytes int32 (N,))."""
+    from . import gif
+    chunk = gif.CHUNK if chunk is None else chunk
+    c = _gif_chunks("gif_pack_scan", frames, h, w, chunk)
+    _chk_i32(chunk_bits, "gif_pack_scan: chunk_bits", (frames * c,))
+    chunk_off = torch.empty((frames * c,), dtype=torch.int64, device=chunk_bits.device)
+    frame_bytes = torch.empty((frames,), dtype=torch.int32, device=chunk_bits.device)
+    hip.check(hip.lib().ccedit_gif_pack_scan(chunk_bits.data_ptr(), chunk_off.data_ptr(), frame_bytes.data_ptr(), int(frames), int(h), int(w),
+                                             int(chunk), _stream()), "ccedit_gif_pack_scan")
+    return chunk_off, frame_bytes
+
+
+def gif_pack(slots: torch.Tensor, chunk_bits: torch.Tensor, chunk_off: torch.Tensor, frames: int, h: int, w: int, chunk: int,
+             out_bytes: int) -> torch.Tensor:
+    """-> uint8 (out_bytes,): the frames' LZW byte streams back to back, each its chunks' bits back to back, zero-padded to a byte."""
+    c = _gif_chunks("gif_pack", frames, h, w, chunk)
+    _chk_u8(slots, "gif_pack: slots", 2)
+    if tuple(slots.shape) != (frames * c, gif_slot_bytes()):
+        raise ValueError(f"gif_pack: slots {tuple(slots.shape)}: expected {(frames * c, gif_slot_bytes())}")
+    _chk_i32(chunk_bits, "gif_pack: chunk_bits", (frames * c,))
+    if chunk_off.dtype != torch.int64 or not chunk_off.is_cuda or not chunk_off.is_contiguous() or tuple(chunk_off.shape) != (frames * c,):
+        raise ValueError(f"gif_pack: chunk_off: expected a contiguous cuda int64 tensor {(frames * c,)}, got {chunk_off.dtype} {tuple(chunk_off.shape)}")
+    if int(out_bytes) < 1:
+        raise ValueError(f"gif_pack: out_bytes={out_bytes} (the sum of frame_bytes, >= 1)")
+    out = torch.empty(((int(out_bytes) + 3) // 4 * 4,), dtype=torch.uint8, device=slots.device)
+    hip.check(hip.lib().ccedit_gif_pack(slots.data_ptr(), chunk_bits.data_ptr(), chunk_off.data_ptr(), out.data_ptr(), int(frames), int(h), int(w),
+                                        int(chunk), int(out_bytes), _stream()), "ccedit_gif_pack")
+    return out[:int(out_bytes)]

@@ -607,6 +607,46 @@ int ccedit_jpegdec_idct(const void* coef, const int32_t* tables, void* planes, i
                         int32_t vs, void* stream);
 int ccedit_jpegdec_rgb(const void* planes, void* out, int32_t N, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GIF (added without an ABI bump: seven new functions, CCEDIT_ABI_VERSION stays 12).  `--gif_encoder device`: uint8 frames [N][H][W][3]
+ * on the device (what ccedit_frames_to_u8 writes) -> per frame a palette of 256 colours, the pixels' indices and their LZW byte stream;
+ * ccedit_amd/gif.py: constants, the frame loop, the container.  Kernels: csrc/gif.hip.  Every byte equals tests/_gif_numpy.py.
+ * H and W are 1 ... 65535 with H * W <= 2^24; N <= 65535.
+ *
+ * The palette is Wu's variance-minimising quantiser on a grid of 32^3 cells (cell = r >> 3, g >> 3, b >> 3).  `moments`: int64
+ * [N][5][33][33][33], index [cell r + 1][cell g + 1][cell b + 1] with a zero border: count, sum r, sum g, sum b, sum r^2 + g^2 + b^2 of
+ * the full 8-bit values.  A box is (r0, r1] x (g0, g1] x (b0, b1] on that grid; (0, 32]^3 is cut up to 255 times.  The next box to cut is
+ * the lowest-indexed one of maximal score (the variance m2 - (dr^2 + dg^2 + db^2) / w in float64; 0 for a box of one cell), until that
+ * maximum is <= 0.  A cut position's score is (hr hr + hg hg + hb hb) / hw + (or or + og og + ob ob) / ow over the two halves, float64
+ * from int64 operands, products summed left to right, IEEE division, no multiply-add contraction; positions with an empty half are
+ * skipped; per direction the strictly greater score wins (the lowest position on ties); direction r if its best >= both others, else
+ * g if its best >= both others, else b.  A box that cannot be cut gets score 0 and consumes no palette entry.
+ *
+ * ccedit_gif_slot_bytes: bytes of one chunk's slot in `slots` (chunk + 2 codes of 12 bits, a multiple of 16).
+ * ccedit_gif_histogram: frames -> moments (zeroed by the call itself), 8-byte aligned.  Integer atomics: no dependence on the order.
+ * ccedit_gif_palette: moments -> their inclusive 3-D prefix sums IN PLACE, then the cuts -> cells uint8 [N][32][32][32] (cell -> box =
+ *   palette index) and palettes uint8 [N][256][3]: the box means (sum + w / 2) / w, unused entries 0.
+ * ccedit_gif_map: frames, cells -> indices uint8 [N][H][W]; there is no nearest-colour search.
+ * ccedit_gif_lzw: indices -> LZW codes.  A frame's H * W indices in raster order are cut into chunks of `chunk` pixels (1 ... 3072; the
+ *   encoder uses 3072), C = ceil(H W / chunk) per frame, each coded from an empty dictionary (9 bits, next code 258).  After every code
+ *   (the chunk's last one included) an entry is counted, and the width grows when the next free code exceeds 1 << width.  A chunk ends
+ *   with Clear (256) at that width, a frame's last chunk with EOI (257); a frame's first chunk starts with Clear at 9 bits.  Codes are
+ *   packed LSB first into chunk i's slot at slots + i * slot_bytes (4-byte aligned), its bit length goes to chunk_bits[i] (int32 [N * C]).
+ * ccedit_gif_pack_scan: chunk_bits (clamped into the slot) -> chunk_off (int64 [N * C]: the bit offset of every chunk in the packed
+ *   output, the frames back to back, each zero-padded to a byte) and frame_bytes (int32 [N]).
+ * ccedit_gif_pack: the chunks' bits shifted to their offsets in out (out_bytes = the sum of frame_bytes; the buffer holds out_bytes
+ *   rounded up to a multiple of 4, 4-byte aligned, zeroed by the call itself).  A chunk whose bits would leave the output is skipped.
+ */
+int64_t ccedit_gif_slot_bytes(void);
+int ccedit_gif_histogram(const void* frames, int64_t* moments, int32_t N, int32_t H, int32_t W, void* stream);
+int ccedit_gif_palette(int64_t* moments, void* cells, void* palettes, int32_t N, void* stream);
+int ccedit_gif_map(const void* frames, const void* cells, void* indices, int32_t N, int32_t H, int32_t W, void* stream);
+int ccedit_gif_lzw(const void* indices, void* slots, int32_t* chunk_bits, int32_t N, int32_t H, int32_t W, int32_t chunk, void* stream);
+int ccedit_gif_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t* frame_bytes, int32_t N, int32_t H, int32_t W, int32_t chunk,
+                         void* stream);
+int ccedit_gif_pack(const void* slots, const int32_t* chunk_bits, const int64_t* chunk_off, void* out, int32_t N, int32_t H, int32_t W,
+                    int32_t chunk, int64_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

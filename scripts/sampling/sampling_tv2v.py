@@ -34,6 +34,8 @@ gets an edited frame, the two neighbouring edited keyframes carried along motion
 csrc/propagate.hip), written to <save_path>/<basemodel>/result_full/gif/ (or mjpeg/) at --original_fps; log_info.json gains `fullrate_paths`.
 `--save_type mjpeg` writes true-colour video: Motion-JPEG in an .avi, every frame encoded on the GPU (ccedit_amd/mjpeg.py, csrc/mjpeg.hip) at
 --video_quality; such an .avi is also a video SOURCE wherever a .gif is.
+`--gif_encoder device` (with --save_type gif) quantises and LZW-codes every .gif a job writes on the GPU (ccedit_amd/gif.py, csrc/gif.hip);
+the default, `pillow`, writes them on the host as before.
 """
 from __future__ import annotations
 
@@ -130,6 +132,11 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--gpu_io", action="store_true",
                    help="pixel I/O on the GPU (ccedit_amd/csrc/pixel.hip): frame / depth resize, depth hint normalisation and the uint8 "
                         "frames of --save_type gif; decoding and file writing stay on the host.  Default off: everything as before")
+    p.add_argument("--gif_encoder", type=str, default="pillow", choices=["pillow", "device"],
+                   help="(not in the reference script) who encodes the files of --save_type gif, result_full/gif/ of --propagate included.  "
+                        "pillow (default): Pillow on the host, byte for byte as before.  device: colour quantisation (Wu's quantiser, a local "
+                        "palette of 256 colours per frame) and LZW coding on the GPU (ccedit_amd/gif.py, csrc/gif.hip); with --gpu_io the "
+                        "uint8 frames never leave the device, only palettes and LZW bytes come back.  An error with any other --save_type")
 
 
 def make_parser() -> argparse.ArgumentParser:
@@ -154,6 +161,8 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
                     "(or --prompt_listpath / --videos_directory / --json_path)")
         if args.save_type not in ("gif", "mjpeg"):
             p.error(f"--propagate writes result_full/ as gif or as Motion-JPEG: add --save_type gif or --save_type mjpeg (got {args.save_type})")
+    if getattr(args, "gif_encoder", "pillow") == "device" and args.save_type != "gif":
+        p.error(f"--gif_encoder device encodes the files of --save_type gif (got --save_type {args.save_type})")
     if not 1 <= getattr(args, "video_quality", 90) <= 100:
         p.error(f"--video_quality must be in 1 ... 100 (got {args.video_quality})")
     if args.save_type == "mjpeg" and (args.H % 16 or args.W % 16):
@@ -199,7 +208,8 @@ def check_propagate(args, video_paths) -> None:
 def propagate_chunk(args, cvideos, samples, dev, save_path):
     """--propagate for one chunk: per clip all source frames on the device, the edited keyframes as the uint8 frames result/ holds
     (frames_to_u8 without rounding of the decoder output), propagate_clip, <save_path>/result_full/gif/animation-XXXX.gif (--save_type
-    mjpeg: result_full/mjpeg/animation-XXXX.avi, encoded from the frames where they are, on the device) at --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
+    mjpeg: result_full/mjpeg/animation-XXXX.avi, encoded from the frames where they are, on the device; so is the gif with --gif_encoder
+    device) at --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
     from ccedit_amd import ops
     from ccedit_amd.propagate import propagate_clip
     from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask, save_avi_u8, save_gif_u8
@@ -216,6 +226,8 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
         full = propagate_clip(source, idx, edited[b], masks=masks)
         if args.save_type == "mjpeg":
             paths.append(save_avi_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps, args.video_quality))
+        elif getattr(args, "gif_encoder", "pillow") == "device":        # encoded from the frames where they are, on the device
+            paths.append(save_gif_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps, gif_encoder="device"))
         else:
             paths.append(save_gif_u8(os.path.join(save_path, "result_full"), full.cpu().numpy(), args.original_fps))
     return paths
@@ -310,6 +322,8 @@ def save_result(args, tag, x):
     """sampling_tv2v.py:473-515: clamp to [0,1]; .npy frames (default) or an animated gif / a Motion-JPEG .avi + frame grid."""
     from scripts.sampling.util import perform_save_locally_video, save_frames
     quality = dict(video_quality=args.video_quality) if args.save_type == "mjpeg" else {}
+    if getattr(args, "gif_encoder", "pillow") == "device":
+        quality["gif_encoder"] = "device"
     if args.save_type in ("gif", "mjpeg") and getattr(args, "gpu_io", False):
         perform_save_locally_video(os.path.join(args.save_path, "result"), x, fps=args.target_fps, savetype=args.save_type, gpu_io=True, signed=True,
                                    **quality)
@@ -688,6 +702,8 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 io = {}
             if args.save_type == "mjpeg":
                 io["video_quality"] = args.video_quality
+            if getattr(args, "gif_encoder", "pillow") == "device":
+                io["gif_encoder"] = "device"
             perform_save_locally_video(os.path.join(save_path, "original"), to01(keyframes), args.target_fps, args.save_type, save_grid=False, **io)
             keyframes_paths = perform_save_locally_video(os.path.join(save_path, "result"), to01(samples), args.target_fps, args.save_type,
                                                          return_savepaths=True, save_grid=False, **io)

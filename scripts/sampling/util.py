@@ -461,13 +461,33 @@ def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
     raise ValueError("Unsupported video format. Only support dirctory, .mp4, .gif and .avi (Motion-JPEG).")
 
 
-def save_gif_u8(save_path: str, frames: np.ndarray, fps: int) -> str:
-    """uint8 frames (T, H, W, 3) -> <save_path>/gif/animation-XXXX.gif, numbered and written like perform_save_locally_video's."""
-    from PIL import Image
+GIF_ENCODERS = ("pillow", "device")
+
+
+def _write_gif_device(savepath: str, frames, fps: int) -> str:
+    """uint8 frames (T, H, W, 3), on the device or on the host (then uploaded once) -> `savepath`: palettes and LZW streams come from the
+    device (ccedit_amd/gif.py, csrc/gif.hip), only they come back; the container is written here on the host."""
+    from ccedit_amd import gif
+    if not torch.is_tensor(frames):
+        frames = torch.from_numpy(np.ascontiguousarray(frames))
+    if not frames.is_cuda:
+        frames = frames.to(torch.device("cuda", torch.cuda.current_device()))
+    return gif.write_gif(savepath, gif.encode_frames(frames.contiguous()), gif.duration_ms(fps), frames.shape[2], frames.shape[1])
+
+
+def save_gif_u8(save_path: str, frames, fps: int, gif_encoder: str = "pillow") -> str:
+    """uint8 frames (T, H, W, 3) -> <save_path>/gif/animation-XXXX.gif, numbered and written like perform_save_locally_video's.
+    gif_encoder='device' (not in the reference): the frames, a device tensor or a host array that is uploaded once, are quantised and
+    LZW-coded on the device; 'pillow' (the default) writes the file with Pillow, byte for byte as before."""
+    if gif_encoder not in GIF_ENCODERS:
+        raise ValueError(f"gif_encoder {gif_encoder!r}: one of {GIF_ENCODERS}")
     os.makedirs(os.path.join(save_path, "gif"), exist_ok=True)
     count = len(os.listdir(os.path.join(save_path, "gif")))
-    imgs = [Image.fromarray(f) for f in frames]
     savepath = os.path.join(save_path, "gif", f"animation-{count:04}.gif")
+    if gif_encoder == "device":
+        return _write_gif_device(savepath, frames, fps)
+    from PIL import Image
+    imgs = [Image.fromarray(f) for f in frames]
     imgs[0].save(savepath, save_all=True, append_images=imgs[1:], duration=int(round(1000.0 / fps)), loop=0)
     return savepath
 
@@ -610,7 +630,7 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
 
 def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, savetype: str = "gif",
                                return_savepaths: bool = False, save_grid: bool = True, gpu_io: bool = False, signed: bool = False,
-                               video_quality: int = 90):
+                               video_quality: int = 90, gif_encoder: str = "pillow"):
     """util.py:288-352: samples (B, 3, T, H, W) in [0, 1] -> <save_path>/gif/animation-XXXX.gif (+ grid/grid-XXXX.png:
     the T frames side by side).  savetype='mp4' needs a codec library and raises.
     savetype='mjpeg' (not in the reference): <save_path>/mjpeg/animation-XXXX.avi, Motion-JPEG at `video_quality` (1 ... 100), numbered and
@@ -618,10 +638,17 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
     bytes either way — and every frame is encoded on the device (ccedit_amd/mjpeg.py, csrc/mjpeg.hip).
     gpu_io (savetype='gif' or 'mjpeg', device tensor): the uint8 frames are made on the device (ccedit_frames_to_u8) and 3 bytes per pixel
     instead of 12 come to the host; the files are byte-identical.  `signed` (with gpu_io only): samples are the decoder's output in
-    [-1, 1] and clamp((x + 1) / 2, 0, 1) is part of the same kernel."""
+    [-1, 1] and clamp((x + 1) / 2, 0, 1) is part of the same kernel.
+    gif_encoder='device' (savetype='gif' only, not in the reference): the gif is quantised and LZW-coded on the device (ccedit_amd/gif.py,
+    csrc/gif.hip) from the uint8 frames the Pillow branch would have quantised — with gpu_io they never leave the device, otherwise they
+    are uploaded once: the same bytes either way.  File names, numbering, returned paths and the grid PNG are those of 'pillow'."""
     from PIL import Image
     assert samples.dim() == 5, "Expected samples to have shape (B, C, T, H, W)"
     assert savetype in ["gif", "mp4", "npy", "mjpeg"]
+    if gif_encoder not in GIF_ENCODERS:
+        raise ValueError(f"gif_encoder {gif_encoder!r}: one of {GIF_ENCODERS}")
+    if gif_encoder == "device" and savetype != "gif":
+        raise ValueError(f"gif_encoder='device' encodes gifs: savetype must be 'gif', got {savetype!r}")
     assert gpu_io or not signed, "signed samples are only taken on the gpu_io route"
     if savetype == "mp4":
         raise NotImplementedError("mp4 encoding needs imageio-ffmpeg / cv2, not installed here: use savetype='gif'")
@@ -632,7 +659,7 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
             raise ValueError("gpu_io saves uint8 frames (savetype='gif') of a device tensor")
         x = samples.detach().float().contiguous()
         u8 = ops.frames_to_u8(x, rounding=False, unit_range=not signed)                                # (B, T, H, W, 3)
-        u8 = u8 if savetype == "mjpeg" else u8.cpu().numpy()                                           # (mjpeg: the frames stay on the device)
+        u8 = u8 if savetype == "mjpeg" or gif_encoder == "device" else u8.cpu().numpy()               # (mjpeg, device gif: the frames stay on the device)
         u8_grid = ops.frames_to_u8(x, rounding=True, unit_range=not signed).cpu().numpy() if save_grid else None
     if savetype == "npy":          # (not in the reference) the frames themselves: <save_path>/npy/frames-XXXX.npy, (T, H, W, C) float32 in [0, 1]
         os.makedirs(os.path.join(save_path, "npy"), exist_ok=True)
@@ -663,8 +690,13 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
             count += 1
             savepaths.append(savepath)
             continue
-        frames = [Image.fromarray(f) for f in ((255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b])]
         savepath = os.path.join(save_path, "gif", f"animation-{count:04}.gif")
+        if gif_encoder == "device":
+            _write_gif_device(savepath, (255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b], fps)
+            count += 1
+            savepaths.append(savepath)
+            continue
+        frames = [Image.fromarray(f) for f in ((255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b])]
         frames[0].save(savepath, save_all=True, append_images=frames[1:], duration=int(round(1000.0 / fps)), loop=0)
         count += 1
         savepaths.append(savepath)
