@@ -6,10 +6,111 @@
 // single contiguous, fully coalesced C*2-byte burst and per-channel affine parameters live in registers.
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
 constexpr int kMaxCols = 5;    // C <= 2560
+
+// ------------------------------------------------------------------------------------------
+// the building blocks every GroupNorm kernel below is made of: one copy each
+// ------------------------------------------------------------------------------------------
+
+// sum += f, sq += f * f over one 16-byte granule (8 channels)
+__device__ __forceinline__ void moments_add(float (&sum)[8], float (&sq)[8], const bf16x8 v) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float f = bf2f(v[e]);
+        sum[e] += f;
+        sq[e] += f * f;
+    }
+}
+
+// Per-channel fold of a granule's moments into the 32 group slots of the calling wave (s_sum / s_sq are ITS rows of the LDS arrays).
+// Run-to-run reproducibility of the statistics: a wave accumulates into its OWN LDS slots (same-wave LDS atomics retire in
+// program / lane order), the waves' slots are added in a fixed order, and only the cross-workgroup sum of the spatial statistics
+// uses global atomics — in double, so that the arrival order moves the total by ~1e-16 relative, far below the fp32 rounding of
+// the mean / rstd derived from it.  (With fp32 atomics the order noise flipped bf16 roundings downstream and two runs of the same
+// clip differed by the full bf16 noise floor, ~2 % rel. RMS at 17x512x768.)
+__device__ __forceinline__ void fold_channels(float (&s_sum)[32], float (&s_sq)[32], int c0, int cpg, const float (&sum)[8],
+                                              const float (&sq)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int g = (c0 + e) / cpg;
+        atomicAdd(&s_sum[g], sum[e]);
+        atomicAdd(&s_sq[g], sq[e]);
+    }
+}
+
+// A granule of 8 aligned channels spans at most two groups when C / 32 >= 8: channels [0, split) of the granule at channel c0
+// belong to group g0, the others to g0 + 1.  Every kernel that treats a straddling granule takes the boundary from here.
+struct GroupSplit {
+    int g0, split;
+};
+__device__ __forceinline__ GroupSplit group_split(int c0, int cpg) {
+    const int g0 = c0 / cpg;
+    return {g0, (g0 + 1) * cpg - c0};
+}
+
+// (sum, sq) of the first group part of a granule, (sum, sq) of its second
+__device__ __forceinline__ f32x4 split_moments(const float (&sum)[8], const float (&sq)[8], int split) {
+    float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const bool first = e < split;
+        s0 += first ? sum[e] : 0.f;
+        q0 += first ? sq[e] : 0.f;
+        s1 += first ? 0.f : sum[e];
+        q1 += first ? 0.f : sq[e];
+    }
+    return f32x4{s0, q0, s1, q1};
+}
+
+// (mean, rstd) of a group from its raw moments
+__device__ __forceinline__ f32x2 mean_rstd(float sum, float sq, float inv_n, float eps) {
+    const float mean = sum * inv_n;
+    return f32x2{mean, rsqrtf(fmaxf(sq * inv_n - mean * mean, 0.f) + eps)};
+}
+
+// Affine coefficients y = x * a + b of channel c from the statistics of its own group: stat(g) -> (sum, sq) of group g, wherever
+// the kernel keeps them (double in global memory, float in LDS, float in global memory).  The form for any C / 32, and the only
+// one for the narrow configurations (C / 32 < 8), where a granule spans several groups.
+template <class Stat>
+__device__ __forceinline__ void affine_channel(float& a, float& b, int c, int cpg, float inv_n, float eps, float ga, float be, Stat stat) {
+    const f32x2 st = stat(c / cpg);
+    const f32x2 mr = mean_rstd(st[0], st[1], inv_n, eps);
+    a = mr[1] * ga;
+    b = be - mr[0] * a;
+}
+
+// The same for a granule that spans at most two groups (C / 32 >= 8): two statistics and four 16-byte gamma / beta loads per
+// granule.  gs = group_split(c0, cpg); mr(g) -> (mean, rstd) of group g.
+template <class MeanRstd>
+__device__ __forceinline__ void affine_two_groups(float (&a)[8], float (&b)[8], int c0, GroupSplit gs, const float* __restrict__ gamma,
+                                                  const float* __restrict__ beta, MeanRstd mr) {
+    const f32x2 st0 = mr(gs.g0), st1 = mr(min(gs.g0 + 1, 31));
+    const f32x4 ga0 = *(const f32x4*)(gamma + c0), ga1 = *(const f32x4*)(gamma + c0 + 4);
+    const f32x4 be0 = *(const f32x4*)(beta + c0), be1 = *(const f32x4*)(beta + c0 + 4);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float ga = e < 4 ? ga0[e & 3] : ga1[e & 3], be = e < 4 ? be0[e & 3] : be1[e & 3];
+        const bool first = e < gs.split;
+        a[e] = (first ? st0[1] : st1[1]) * ga;
+        b[e] = be - (first ? st0[0] : st1[0]) * a[e];
+    }
+}
+
+// o = bf16(silu?(x * a + b)) over one granule, one 16-byte store (the multiply-add contracts to one fma)
+__device__ __forceinline__ void affine_store(bf16* dst, const bf16x8 v, const float (&a)[8], const float (&b)[8], int silu) {
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float f = bf2f(v[e]) * a[e] + b[e];
+        if (silu) f = silu_f(f);
+        o[e] = f2bf(f);
+    }
+    *(bf16x8*)dst = o;
+}
 
 // ------------------------------------------------------------------------------------------
 // spatial GroupNorm: statistics over (C/32 channels x H*W pixels) of one frame
@@ -25,11 +126,7 @@ inline int gn_pix_per_block(int hw, int frames, int lo, int64_t want_blocks) {
     return ppb;
 }
 
-// Run-to-run reproducibility of the statistics: a wave accumulates into its OWN LDS slots (same-wave LDS atomics
-// retire in program / lane order), the waves' slots are added in a fixed order, and only the cross-workgroup sum uses
-// global atomics — in double, so that the arrival order moves the total by ~1e-16 relative, far below the fp32 rounding
-// of the mean / rstd derived from it.  (With fp32 atomics the order noise flipped bf16 roundings downstream and two runs
-// of the same clip differed by the full bf16 noise floor, ~2 % rel. RMS at 17x512x768.)
+// (reproducibility: see fold_channels)
 __global__ __launch_bounds__(256) void gn_spatial_stats_kernel(const bf16* __restrict__ x, double* __restrict__ stats,
                                                                int hw, int C, int pix_per_block) {
     __shared__ float s_sum[kGnWaves][32], s_sq[kGnWaves][32];
@@ -54,28 +151,13 @@ __global__ __launch_bounds__(256) void gn_spatial_stats_kernel(const bf16* __res
 #pragma unroll
         for (int k = 0; k < kMaxCols; ++k) {
             const int gc = lane + 64 * k;
-            if (gc < G8) {
-                const bf16x8 v = *(const bf16x8*)(row + gc * 8);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float f = bf2f(v[e]);
-                    sum[k][e] += f;
-                    sq[k][e] += f * f;
-                }
-            }
+            if (gc < G8) moments_add(sum[k], sq[k], *(const bf16x8*)(row + gc * 8));
         }
     }
 #pragma unroll
     for (int k = 0; k < kMaxCols; ++k) {
         const int gc = lane + 64 * k;
-        if (gc < G8) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int g = (gc * 8 + e) / cpg;
-                atomicAdd(&s_sum[wave][g], sum[k][e]);
-                atomicAdd(&s_sq[wave][g], sq[k][e]);
-            }
-        }
+        if (gc < G8) fold_channels(s_sum[wave], s_sq[wave], gc * 8, cpg, sum[k], sq[k]);
     }
     __syncthreads();
     if (threadIdx.x < 32) {
@@ -90,6 +172,12 @@ __global__ __launch_bounds__(256) void gn_spatial_stats_kernel(const bf16* __res
     }
 }
 
+// (sum, sq) of group g of a frame as the apply passes use them: the double totals rounded to fp32
+__device__ __forceinline__ f32x2 gn_frame_stat(const double* __restrict__ stats, int frame, int g) {
+    const double* sp = stats + (frame * 32 + g) * 2;
+    return f32x2{(float)sp[0], (float)sp[1]};
+}
+
 template <int COLS>      // 16-byte granules per lane: ceil(C / 512); fewer live coefficient registers -> more resident waves
 __global__ __launch_bounds__(256) void gn_spatial_apply_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
                                                                const double* __restrict__ stats,
@@ -100,9 +188,9 @@ __global__ __launch_bounds__(256) void gn_spatial_apply_kernel(const bf16* __res
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int G8 = C >> 3, cpg = C >> 5;
     const float inv_n = 1.0f / ((float)cpg * (float)hw);
-    // per-lane affine coefficients of its 8 * COLS channels.  A granule of 8 aligned channels spans at most two groups
-    // (C/32 >= 8): two statistics loads and four 16-byte gamma/beta loads per granule — this set-up is paid once per
-    // wave and would otherwise dominate at the small latent levels, where a wave normalises only a few pixel rows.
+    // per-lane affine coefficients of its 8 * COLS channels — this set-up is paid once per wave and would otherwise dominate at
+    // the small latent levels, where a wave normalises only a few pixel rows.
+    auto stat = [&](int g) { return gn_frame_stat(stats, frame, g); };
     float a[COLS][8], b[COLS][8];
 #pragma unroll
     for (int k = 0; k < COLS; ++k) {
@@ -113,30 +201,13 @@ __global__ __launch_bounds__(256) void gn_spatial_apply_kernel(const bf16* __res
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int c = gc * 8 + e;
-                const int g = c / cpg;
-                const float mean = (float)stats[(frame * 32 + g) * 2] * inv_n;
-                const float rstd = rsqrtf(fmaxf((float)stats[(frame * 32 + g) * 2 + 1] * inv_n - mean * mean, 0.f) + eps);
-                a[k][e] = rstd * gamma[c];
-                b[k][e] = beta[c] - mean * a[k][e];
+                affine_channel(a[k][e], b[k][e], c, cpg, inv_n, eps, gamma[c], beta[c], stat);
             }
         } else if (gc < G8) {
-            const int c0 = gc * 8;
-            const int g0 = c0 / cpg, g1 = min(g0 + 1, 31);
-            const int split = (g0 + 1) * cpg - c0;           // channels of this granule that belong to group g0
-            const double* sp0 = stats + (frame * 32 + g0) * 2;
-            const double* sp1 = stats + (frame * 32 + g1) * 2;
-            const f32x2 st0 = {(float)sp0[0], (float)sp0[1]}, st1 = {(float)sp1[0], (float)sp1[1]};
-            const f32x4 ga0 = *(const f32x4*)(gamma + c0), ga1 = *(const f32x4*)(gamma + c0 + 4);
-            const f32x4 be0 = *(const f32x4*)(beta + c0), be1 = *(const f32x4*)(beta + c0 + 4);
-            const float m0 = st0[0] * inv_n, m1 = st1[0] * inv_n;
-            const float r0 = rsqrtf(fmaxf(st0[1] * inv_n - m0 * m0, 0.f) + eps), r1 = rsqrtf(fmaxf(st1[1] * inv_n - m1 * m1, 0.f) + eps);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float ga = e < 4 ? ga0[e & 3] : ga1[e & 3], be = e < 4 ? be0[e & 3] : be1[e & 3];
-                const bool first = e < split;
-                a[k][e] = (first ? r0 : r1) * ga;
-                b[k][e] = be - (first ? m0 : m1) * a[k][e];
-            }
+            affine_two_groups(a[k], b[k], gc * 8, group_split(gc * 8, cpg), gamma, beta, [&](int g) {
+                const f32x2 st = stat(g);
+                return mean_rstd(st[0], st[1], inv_n, eps);
+            });
         }
     }
     const int p0 = blockIdx.x * pix_per_block;
@@ -147,17 +218,7 @@ __global__ __launch_bounds__(256) void gn_spatial_apply_kernel(const bf16* __res
 #pragma unroll
         for (int k = 0; k < COLS; ++k) {
             const int gc = lane + 64 * k;
-            if (gc < G8) {
-                const bf16x8 v = *(const bf16x8*)(xf + (size_t)pix * C + gc * 8);
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float f = bf2f(v[e]) * a[k][e] + b[k][e];
-                    if (silu) f = silu_f(f);
-                    o[e] = f2bf(f);
-                }
-                *(bf16x8*)(yf + (size_t)pix * C + gc * 8) = o;
-            }
+            if (gc < G8) affine_store(yf + (size_t)pix * C + gc * 8, *(const bf16x8*)(xf + (size_t)pix * C + gc * 8), a[k], b[k], silu);
         }
     }
 }
@@ -241,6 +302,59 @@ __global__ __launch_bounds__(256) void gn_spatial_onepass_kernel(const bf16* __r
 // ------------------------------------------------------------------------------------------
 constexpr int kGtCols = 3;     // temporal norms only see C in {320, 640, 1280} (<= 1536)
 
+// Statistics sweep of one wave over the T rows of its (clip, pixel): raw moments per channel in registers, then folded into the
+// wave's group slots (zeroed by the caller, a barrier before this and one before anybody reads them).
+__device__ __forceinline__ void gt_stats_sweep(const bf16* __restrict__ xb, size_t fstride, int T, int lane, int G8, int cpg,
+                                               float (&s_sum)[32], float (&s_sq)[32]) {
+    float sum[kGtCols][8], sq[kGtCols][8];
+#pragma unroll
+    for (int k = 0; k < kGtCols; ++k)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sum[k][e] = sq[k][e] = 0.f;
+    for (int t = 0; t < T; ++t) {
+#pragma unroll
+        for (int k = 0; k < kGtCols; ++k) {
+            const int gc = lane + 64 * k;
+            if (gc < G8) moments_add(sum[k], sq[k], *(const bf16x8*)(xb + t * fstride + gc * 8));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kGtCols; ++k) {
+        const int gc = lane + 64 * k;
+        if (gc < G8) fold_channels(s_sum, s_sq, gc * 8, cpg, sum[k], sq[k]);
+    }
+}
+
+// Coefficients of a lane's 8 * kGtCols channels from the (sum, sq) that stat(g) finds
+template <class Stat>
+__device__ __forceinline__ void gt_affine(float (&a)[kGtCols][8], float (&b)[kGtCols][8], int lane, int G8, int cpg, float inv_n, float eps,
+                                          const float* __restrict__ gamma, const float* __restrict__ beta, Stat stat) {
+#pragma unroll
+    for (int k = 0; k < kGtCols; ++k) {
+        const int gc = lane + 64 * k;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            a[k][e] = b[k][e] = 0.f;
+            if (gc < G8) {
+                const int c = gc * 8 + e;
+                affine_channel(a[k][e], b[k][e], c, cpg, inv_n, eps, gamma[c], beta[c], stat);
+            }
+        }
+    }
+}
+
+// Apply sweep of one wave over the T rows of its (clip, pixel)
+__device__ __forceinline__ void gt_apply_sweep(const bf16* __restrict__ xb, bf16* __restrict__ yb, size_t fstride, int T, int lane, int G8,
+                                               const float (&a)[kGtCols][8], const float (&b)[kGtCols][8], int silu) {
+    for (int t = 0; t < T; ++t) {
+#pragma unroll
+        for (int k = 0; k < kGtCols; ++k) {
+            const int gc = lane + 64 * k;
+            if (gc < G8) affine_store(yb + t * fstride + gc * 8, *(const bf16x8*)(xb + t * fstride + gc * 8), a[k], b[k], silu);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void gn_temporal_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
                                                           const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, int B, int T, int hw, int C,
@@ -260,79 +374,13 @@ __global__ __launch_bounds__(256) void gn_temporal_kernel(const bf16* __restrict
     const size_t fstride = (size_t)hw * C;
     const bf16* xb = x + ((size_t)b * T * hw + pix) * C;
     bf16* yb = y + ((size_t)b * T * hw + pix) * C;
-    float sum[kGtCols][8], sq[kGtCols][8];
-#pragma unroll
-    for (int k = 0; k < kGtCols; ++k)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sum[k][e] = sq[k][e] = 0.f;
-    if (active) {
-        for (int t = 0; t < T; ++t) {
-#pragma unroll
-            for (int k = 0; k < kGtCols; ++k) {
-                const int gc = lane + 64 * k;
-                if (gc < G8) {
-                    const bf16x8 v = *(const bf16x8*)(xb + t * fstride + gc * 8);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float f = bf2f(v[e]);
-                        sum[k][e] += f;
-                        sq[k][e] += f * f;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kGtCols; ++k) {
-            const int gc = lane + 64 * k;
-            if (gc < G8) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int g = (gc * 8 + e) / cpg;
-                    atomicAdd(&s_sum[wave][g], sum[k][e]);
-                    atomicAdd(&s_sq[wave][g], sq[k][e]);
-                }
-            }
-        }
-    }
+    if (active) gt_stats_sweep(xb, fstride, T, lane, G8, cpg, s_sum[wave], s_sq[wave]);
     __syncthreads();
     if (!active) return;
-    const float inv_n = 1.0f / ((float)cpg * (float)T);
     float a[kGtCols][8], bb[kGtCols][8];
-#pragma unroll
-    for (int k = 0; k < kGtCols; ++k) {
-        const int gc = lane + 64 * k;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            a[k][e] = 0.f;
-            bb[k][e] = 0.f;
-            if (gc < G8) {
-                const int c = gc * 8 + e;
-                const int g = c / cpg;
-                const float mean = s_sum[wave][g] * inv_n;
-                const float var = fmaxf(s_sq[wave][g] * inv_n - mean * mean, 0.f);
-                const float rstd = rsqrtf(var + eps);
-                a[k][e] = rstd * gamma[c];
-                bb[k][e] = beta[c] - mean * a[k][e];
-            }
-        }
-    }
-    for (int t = 0; t < T; ++t) {
-#pragma unroll
-        for (int k = 0; k < kGtCols; ++k) {
-            const int gc = lane + 64 * k;
-            if (gc < G8) {
-                const bf16x8 v = *(const bf16x8*)(xb + t * fstride + gc * 8);
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float f = bf2f(v[e]) * a[k][e] + bb[k][e];
-                    if (silu) f = silu_f(f);
-                    o[e] = f2bf(f);
-                }
-                *(bf16x8*)(yb + t * fstride + gc * 8) = o;
-            }
-        }
-    }
+    gt_affine(a, bb, lane, G8, cpg, 1.0f / ((float)cpg * (float)T), eps, gamma, beta,
+              [&](int g) { return f32x2{s_sum[wave][g], s_sq[wave][g]}; });
+    gt_apply_sweep(xb, yb, fstride, T, lane, G8, a, bb, silu);
 }
 
 // Single-sweep form for short clips (T <= kGtCacheT): a wave owns one (clip, pixel, channel slice) — a slice is a
@@ -341,6 +389,28 @@ __global__ __launch_bounds__(256) void gn_temporal_kernel(const bf16* __restrict
 // rows one frame apart, so it is bound by load latency: memory-level parallelism per wave and the number of
 // waves are what count (the 16x24 / 8x12 levels have 768 / 192 pixels).
 constexpr int kGtCacheT = 20;
+
+// A thread's granule over the T <= CT rows of its (clip, pixel): all loads issued back to back, then the raw moments
+template <int CT>
+__device__ __forceinline__ void gt_cache_rows(bf16x8 (&cache)[CT], float (&sum)[8], float (&sq)[8], const bf16* __restrict__ xb,
+                                              size_t fstride, int T) {
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+        if (t < T) cache[t] = *(const bf16x8*)(xb + t * fstride);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sum[e] = sq[e] = 0.f;
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+        if (t < T) moments_add(sum, sq, cache[t]);
+}
+
+template <int CT>
+__device__ __forceinline__ void gt_store_rows(bf16* __restrict__ yb, size_t fstride, int T, const bf16x8 (&cache)[CT],
+                                              const float (&a)[8], const float (&b)[8], int silu) {
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+        if (t < T) affine_store(yb + t * fstride, cache[t], a, b, silu);
+}
 
 __global__ __launch_bounds__(256) void gn_temporal_cached_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
                                                                  const float* __restrict__ gamma,
@@ -367,76 +437,32 @@ __global__ __launch_bounds__(256) void gn_temporal_cached_kernel(const bf16* __r
     bf16* yb = y + ((size_t)b * T * hw + pix) * C + gc * 8;
     bf16x8 cache[kGtCacheT];
     if (lane_on) {
-#pragma unroll
-        for (int t = 0; t < kGtCacheT; ++t)
-            if (t < T) cache[t] = *(const bf16x8*)(xb + t * fstride);
         float sum[8], sq[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sum[e] = sq[e] = 0.f;
-#pragma unroll
-        for (int t = 0; t < kGtCacheT; ++t)
-            if (t < T) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float f = bf2f(cache[t][e]);
-                    sum[e] += f;
-                    sq[e] += f * f;
-                }
-            }
+        gt_cache_rows(cache, sum, sq, xb, fstride, T);
         if (cpg >= 8) {           // a granule spans at most two groups: four LDS atomics per lane instead of sixteen
-            const int g0 = (gc * 8) / cpg, split = (g0 + 1) * cpg - gc * 8;
-            float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const bool first = e < split;
-                s0 += first ? sum[e] : 0.f;
-                q0 += first ? sq[e] : 0.f;
-                s1 += first ? 0.f : sum[e];
-                q1 += first ? 0.f : sq[e];
-            }
-            atomicAdd(&s_sum[wave][g0], s0);
-            atomicAdd(&s_sq[wave][g0], q0);
-            if (split < 8) {
-                atomicAdd(&s_sum[wave][g0 + 1], s1);
-                atomicAdd(&s_sq[wave][g0 + 1], q1);
+            const GroupSplit gs = group_split(gc * 8, cpg);
+            const f32x4 pt = split_moments(sum, sq, gs.split);
+            atomicAdd(&s_sum[wave][gs.g0], pt[0]);
+            atomicAdd(&s_sq[wave][gs.g0], pt[1]);
+            if (gs.split < 8) {
+                atomicAdd(&s_sum[wave][gs.g0 + 1], pt[2]);
+                atomicAdd(&s_sq[wave][gs.g0 + 1], pt[3]);
             }
         } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int g = (gc * 8 + e) / cpg;
-                atomicAdd(&s_sum[wave][g], sum[e]);
-                atomicAdd(&s_sq[wave][g], sq[e]);
-            }
+            fold_channels(s_sum[wave], s_sq[wave], gc * 8, cpg, sum, sq);
         }
     }
     __syncthreads();
     if (!lane_on) return;
     const float inv_n = 1.0f / ((float)cpg * (float)T);
+    const f32x4 ga0 = *(const f32x4*)(gamma + gc * 8), ga1 = *(const f32x4*)(gamma + gc * 8 + 4);
+    const f32x4 be0 = *(const f32x4*)(beta + gc * 8), be1 = *(const f32x4*)(beta + gc * 8 + 4);
     float a[8], bb[8];
-    {
-        const f32x4 ga0 = *(const f32x4*)(gamma + gc * 8), ga1 = *(const f32x4*)(gamma + gc * 8 + 4);
-        const f32x4 be0 = *(const f32x4*)(beta + gc * 8), be1 = *(const f32x4*)(beta + gc * 8 + 4);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int g = (gc * 8 + e) / cpg;
-            const float mean = s_sum[wave][g] * inv_n;
-            const float var = fmaxf(s_sq[wave][g] * inv_n - mean * mean, 0.f);
-            a[e] = rsqrtf(var + eps) * (e < 4 ? ga0[e & 3] : ga1[e & 3]);
-            bb[e] = (e < 4 ? be0[e & 3] : be1[e & 3]) - mean * a[e];
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < kGtCacheT; ++t)
-        if (t < T) {
-            bf16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float f = bf2f(cache[t][e]) * a[e] + bb[e];
-                if (silu) f = silu_f(f);
-                o[e] = f2bf(f);
-            }
-            *(bf16x8*)(yb + t * fstride) = o;
-        }
+    for (int e = 0; e < 8; ++e)
+        affine_channel(a[e], bb[e], gc * 8 + e, cpg, inv_n, eps, e < 4 ? ga0[e & 3] : ga1[e & 3], e < 4 ? be0[e & 3] : be1[e & 3],
+                       [&](int g) { return f32x2{s_sum[wave][g], s_sq[wave][g]}; });
+    gt_store_rows(yb, fstride, T, cache, a, bb, silu);
 }
 
 // The same single sweep with every lane busy: a THREAD owns one 16-byte granule of one pixel (all T rows of it in registers),
@@ -451,7 +477,7 @@ template <int CT>            // rows cached per thread (>= T): 17 for the 17-key
 __global__ __launch_bounds__(kGtFlatThreads) void gn_temporal_flat_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
                                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                           int64_t npix, int T, int hw, int C, float eps, int silu) {
-    __shared__ f32x4 s_part[kGtFlatThreads];                 // per granule: (sum, sq) of its first group part, (sum, sq) of its second
+    __shared__ f32x4 s_part[kGtFlatThreads];                 // per granule: split_moments
     __shared__ f32x2 s_stat[8 * 32];                         // per (pixel of the block, group): mean, rstd
     const int gpp = C >> 3, cpg = C >> 5;
     const int ppb = kGtFlatThreads / gpp;                    // pixels per block
@@ -464,34 +490,11 @@ __global__ __launch_bounds__(kGtFlatThreads) void gn_temporal_flat_kernel(const 
     const bf16* xb = x + ((size_t)b * T * hw + pix) * C + gc * 8;
     bf16* yb = y + ((size_t)b * T * hw + pix) * C + gc * 8;
     bf16x8 cache[CT];
-    const int g0 = (gc * 8) / cpg, split = (g0 + 1) * cpg - gc * 8;       // channels [0, split) of the granule belong to group g0
+    const GroupSplit gs = group_split(gc * 8, cpg);
     if (on) {
-#pragma unroll
-        for (int t = 0; t < CT; ++t)
-            if (t < T) cache[t] = *(const bf16x8*)(xb + t * fstride);
         float sum[8], sq[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sum[e] = sq[e] = 0.f;
-#pragma unroll
-        for (int t = 0; t < CT; ++t)
-            if (t < T) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float f = bf2f(cache[t][e]);
-                    sum[e] += f;
-                    sq[e] += f * f;
-                }
-            }
-        float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const bool first = e < split;
-            s0 += first ? sum[e] : 0.f;
-            q0 += first ? sq[e] : 0.f;
-            s1 += first ? 0.f : sum[e];
-            q1 += first ? 0.f : sq[e];
-        }
-        s_part[threadIdx.x] = f32x4{s0, q0, s1, q1};
+        gt_cache_rows(cache, sum, sq, xb, fstride, T);
+        s_part[threadIdx.x] = split_moments(sum, sq, gs.split);
     }
     __syncthreads();
     if (threadIdx.x < ppb * 32) {
@@ -504,39 +507,17 @@ __global__ __launch_bounds__(kGtFlatThreads) void gn_temporal_flat_kernel(const 
             ts += first ? pt[0] : pt[2];
             tq += first ? pt[1] : pt[3];
         }
-        const float inv_n = 1.0f / ((float)cpg * (float)T);
-        const float mean = ts * inv_n;
-        s_stat[p * 32 + g] = f32x2{mean, rsqrtf(fmaxf(tq * inv_n - mean * mean, 0.f) + eps)};
+        s_stat[p * 32 + g] = mean_rstd(ts, tq, 1.0f / ((float)cpg * (float)T), eps);
     }
     __syncthreads();
     if (!on) return;
     float a[8], bb[8];
-    {
-        const f32x4 ga0 = *(const f32x4*)(gamma + gc * 8), ga1 = *(const f32x4*)(gamma + gc * 8 + 4);
-        const f32x4 be0 = *(const f32x4*)(beta + gc * 8), be1 = *(const f32x4*)(beta + gc * 8 + 4);
-        const f32x2 st0 = s_stat[pl * 32 + g0], st1 = s_stat[pl * 32 + min(g0 + 1, 31)];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const bool first = e < split;
-            a[e] = (first ? st0[1] : st1[1]) * (e < 4 ? ga0[e & 3] : ga1[e & 3]);
-            bb[e] = (e < 4 ? be0[e & 3] : be1[e & 3]) - (first ? st0[0] : st1[0]) * a[e];
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < CT; ++t)
-        if (t < T) {
-            bf16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float f = bf2f(cache[t][e]) * a[e] + bb[e];
-                if (silu) f = silu_f(f);
-                o[e] = f2bf(f);
-            }
-            *(bf16x8*)(yb + t * fstride) = o;
-        }
+    affine_two_groups(a, bb, gc * 8, gs, gamma, beta, [&](int g) { return s_stat[pl * 32 + g]; });
+    gt_store_rows(yb, fstride, T, cache, a, bb, silu);
 }
 
-// Two-phase form for frame-sharded clips: local partial statistics, (all-reduce by the caller), apply.
+// Two-phase form for frame-sharded clips: local partial statistics, (all-reduce by the caller), apply — the two sweeps of
+// gn_temporal_kernel with the (sum, sq) of every (clip, pixel, group) passing through global memory.
 __global__ __launch_bounds__(256) void gn_temporal_stats_kernel(const bf16* __restrict__ x, float* __restrict__ stats, int B,
                                                                 int T, int hw, int C) {
     __shared__ float s_sum[4][32], s_sq[4][32];
@@ -551,42 +532,7 @@ __global__ __launch_bounds__(256) void gn_temporal_stats_kernel(const bf16* __re
         s_sq[wave][lane] = 0.f;
     }
     __syncthreads();
-    if (active) {
-        const size_t fstride = (size_t)hw * C;
-        const bf16* xb = x + ((size_t)b * T * hw + pix) * C;
-        float sum[kGtCols][8], sq[kGtCols][8];
-#pragma unroll
-        for (int k = 0; k < kGtCols; ++k)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sum[k][e] = sq[k][e] = 0.f;
-        for (int t = 0; t < T; ++t) {
-#pragma unroll
-            for (int k = 0; k < kGtCols; ++k) {
-                const int gc = lane + 64 * k;
-                if (gc < G8) {
-                    const bf16x8 v = *(const bf16x8*)(xb + t * fstride + gc * 8);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float f = bf2f(v[e]);
-                        sum[k][e] += f;
-                        sq[k][e] += f * f;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kGtCols; ++k) {
-            const int gc = lane + 64 * k;
-            if (gc < G8) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int g = (gc * 8 + e) / cpg;
-                    atomicAdd(&s_sum[wave][g], sum[k][e]);
-                    atomicAdd(&s_sq[wave][g], sq[k][e]);
-                }
-            }
-        }
-    }
+    if (active) gt_stats_sweep(x + ((size_t)b * T * hw + pix) * C, (size_t)hw * C, T, lane, G8, cpg, s_sum[wave], s_sq[wave]);
     __syncthreads();
     if (active && lane < 32) {
         stats[(wp * 32 + lane) * 2 + 0] = s_sum[wave][lane];
@@ -604,46 +550,12 @@ __global__ __launch_bounds__(256) void gn_temporal_apply_kernel(const bf16* __re
     const int b = (int)(wp / hw);
     const int pix = (int)(wp - (int64_t)b * hw);
     const int G8 = C >> 3, cpg = C >> 5;
-    const float inv_n = 1.0f / count;
     float a[kGtCols][8], bb[kGtCols][8];
-#pragma unroll
-    for (int k = 0; k < kGtCols; ++k) {
-        const int gc = lane + 64 * k;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            a[k][e] = 0.f;
-            bb[k][e] = 0.f;
-            if (gc < G8) {
-                const int c = gc * 8 + e;
-                const int g = c / cpg;
-                const float mean = stats[(wp * 32 + g) * 2] * inv_n;
-                const float var = fmaxf(stats[(wp * 32 + g) * 2 + 1] * inv_n - mean * mean, 0.f);
-                const float rstd = rsqrtf(var + eps);
-                a[k][e] = rstd * gamma[c];
-                bb[k][e] = beta[c] - mean * a[k][e];
-            }
-        }
-    }
-    const size_t fstride = (size_t)hw * C;
+    gt_affine(a, bb, lane, G8, cpg, 1.0f / count, eps, gamma, beta,
+              [&](int g) { return f32x2{stats[(wp * 32 + g) * 2], stats[(wp * 32 + g) * 2 + 1]}; });
     const bf16* xb = x + ((size_t)b * T * hw + pix) * C;
     bf16* yb = y + (((size_t)b * dst_frames + dst_off) * hw + pix) * C;
-    for (int t = 0; t < T; ++t) {
-#pragma unroll
-        for (int k = 0; k < kGtCols; ++k) {
-            const int gc = lane + 64 * k;
-            if (gc < G8) {
-                const bf16x8 v = *(const bf16x8*)(xb + t * fstride + gc * 8);
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float f = bf2f(v[e]) * a[k][e] + bb[k][e];
-                    if (silu) f = silu_f(f);
-                    o[e] = f2bf(f);
-                }
-                *(bf16x8*)(yb + t * fstride + gc * 8) = o;
-            }
-        }
-    }
+    gt_apply_sweep(xb, yb, (size_t)hw * C, T, lane, G8, a, bb, silu);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -654,6 +566,45 @@ constexpr int kLnCols = 3;     // C <= 1536
 // One wave normalises kLnRowsPerWave consecutive rows, two at a time (two independent 16-byte-per-lane row loads in
 // flight, the two reductions interleaved); gamma / beta live in registers for all of them.
 constexpr int kLnRowsPerWave = 8;   // upper bound; the launch picks 8 / 4 / 2 / 1 so that small inputs still fill the chip
+
+// Two rows into registers and the (mean, rstd) of each: the mean first, then the squared deviations from it.  The one summation
+// order of both kernels below, so a consumer of row_stats_kernel sees the numbers layernorm_kernel normalises with.
+template <int COLS>
+__device__ __forceinline__ void ln_two_row_stats(const bf16* __restrict__ x0, const bf16* __restrict__ x1, int lane, int G8, float inv_c,
+                                                 float eps, bf16x8 (&t0)[COLS], bf16x8 (&t1)[COLS], f32x2& st0, f32x2& st1) {
+#pragma unroll
+    for (int k = 0; k < COLS; ++k) {
+        const int gc = lane + 64 * k;
+        if (gc < G8) {
+            t0[k] = *(const bf16x8*)(x0 + gc * 8);
+            t1[k] = *(const bf16x8*)(x1 + gc * 8);
+        }
+    }
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < COLS; ++k)
+        if (lane + 64 * k < G8) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                s0 += bf2f(t0[k][e]);
+                s1 += bf2f(t1[k][e]);
+            }
+        }
+    const float m0 = wave_sum(s0) * inv_c, m1 = wave_sum(s1) * inv_c;
+    float q0 = 0.f, q1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < COLS; ++k)
+        if (lane + 64 * k < G8) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d0 = bf2f(t0[k][e]) - m0, d1 = bf2f(t1[k][e]) - m1;
+                q0 += d0 * d0;
+                q1 += d1 * d1;
+            }
+        }
+    st0 = f32x2{m0, rsqrtf(wave_sum(q0) * inv_c + eps)};
+    st1 = f32x2{m1, rsqrtf(wave_sum(q1) * inv_c + eps)};
+}
 
 template <int COLS>
 __global__ __launch_bounds__(256) void layernorm_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
@@ -687,39 +638,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16* __restrict__
     for (int r = 0; r < nr; r += 2) {
         const bool two = r + 1 < nr;
         const bf16* x0 = x + (size_t)(row0 + r) * C;
-        const bf16* x1 = x0 + (two ? C : 0);
         bf16x8 t0[COLS], t1[COLS];
-#pragma unroll
-        for (int k = 0; k < COLS; ++k) {
-            const int gc = lane + 64 * k;
-            if (gc < G8) {
-                t0[k] = *(const bf16x8*)(x0 + gc * 8);
-                t1[k] = *(const bf16x8*)(x1 + gc * 8);
-            }
-        }
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < COLS; ++k)
-            if (lane + 64 * k < G8) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    s0 += bf2f(t0[k][e]);
-                    s1 += bf2f(t1[k][e]);
-                }
-            }
-        const float m0 = wave_sum(s0) * inv_c, m1 = wave_sum(s1) * inv_c;
-        float q0 = 0.f, q1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < COLS; ++k)
-            if (lane + 64 * k < G8) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float d0 = bf2f(t0[k][e]) - m0, d1 = bf2f(t1[k][e]) - m1;
-                    q0 += d0 * d0;
-                    q1 += d1 * d1;
-                }
-            }
-        const float r0 = rsqrtf(wave_sum(q0) * inv_c + eps), r1 = rsqrtf(wave_sum(q1) * inv_c + eps);
+        f32x2 st0, st1;
+        ln_two_row_stats<COLS>(x0, x0 + (two ? C : 0), lane, G8, inv_c, eps, t0, t1, st0, st1);
+        const float m0 = st0[0], r0 = st0[1], m1 = st1[0], r1 = st1[1];
 #pragma unroll
         for (int k = 0; k < COLS; ++k) {
             const int gc = lane + 64 * k;
@@ -733,6 +655,27 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16* __restrict__
                 *(bf16x8*)(y + (size_t)(row0 + r) * C + gc * 8) = o0;
                 if (two) *(bf16x8*)(y + (size_t)(row0 + r + 1) * C + gc * 8) = o1;
             }
+        }
+    }
+}
+
+// The statistics half of layernorm_kernel: (mean, rstd) per row (a consumer that folds the LayerNorm into its GEMM —
+// CcGemmDesc.ln_stats — sees the numbers the normalising kernel would have used: both call ln_two_row_stats).
+template <int COLS>
+__global__ __launch_bounds__(256) void row_stats_kernel(const bf16* __restrict__ x, float* __restrict__ st, int64_t rows, int C, float eps, int rpw) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * rpw;
+    if (row0 >= rows) return;
+    const int nr = (int)min((int64_t)rpw, rows - row0);
+    for (int r = 0; r < nr; r += 2) {
+        const bool two = r + 1 < nr;
+        const bf16* x0 = x + (size_t)(row0 + r) * C;
+        bf16x8 t0[COLS], t1[COLS];
+        f32x2 st0, st1;
+        ln_two_row_stats<COLS>(x0, x0 + (two ? C : 0), lane, C >> 3, 1.0f / (float)C, eps, t0, t1, st0, st1);
+        if (lane == 0) {
+            *(f32x2*)(st + 2 * (row0 + r)) = st0;
+            if (two) *(f32x2*)(st + 2 * (row0 + r + 1)) = st1;
         }
     }
 }
@@ -752,47 +695,22 @@ __global__ __launch_bounds__(320) void gn_spatial_apply_flat_kernel(const bf16* 
     if (rs >= RS) return;
     const float inv_n = 1.0f / ((float)cpg * (float)hw);
     float a[8], b[8];
-    {
-        const int c0 = gc * 8;
-        const int g0 = c0 / cpg, g1 = min(g0 + 1, 31);
-        const int split = (g0 + 1) * cpg - c0;               // channels of this granule that belong to group g0 (cpg >= 8: at most two groups)
-        const double* sp0 = stats + (frame * 32 + g0) * 2;
-        const double* sp1 = stats + (frame * 32 + g1) * 2;
-        const float s00 = (float)sp0[0], s01 = (float)sp0[1], s10 = (float)sp1[0], s11 = (float)sp1[1];
-        const f32x4 ga0 = *(const f32x4*)(gamma + c0), ga1 = *(const f32x4*)(gamma + c0 + 4);
-        const f32x4 be0 = *(const f32x4*)(beta + c0), be1 = *(const f32x4*)(beta + c0 + 4);
-        const float m0 = s00 * inv_n, m1 = s10 * inv_n;
-        const float r0 = rsqrtf(fmaxf(s01 * inv_n - m0 * m0, 0.f) + eps), r1 = rsqrtf(fmaxf(s11 * inv_n - m1 * m1, 0.f) + eps);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float ga = e < 4 ? ga0[e & 3] : ga1[e & 3], be = e < 4 ? be0[e & 3] : be1[e & 3];
-            const bool first = e < split;
-            a[e] = (first ? r0 : r1) * ga;
-            b[e] = be - (first ? m0 : m1) * a[e];
-        }
-    }
+    affine_two_groups(a, b, gc * 8, group_split(gc * 8, cpg), gamma, beta, [&](int g) {           // (cpg >= 8: at most two groups)
+        const f32x2 st = gn_frame_stat(stats, frame, g);
+        return mean_rstd(st[0], st[1], inv_n, eps);
+    });
     const int p0 = blockIdx.x * rows_per_block, p1 = min(p0 + rows_per_block, hw);
     const bf16* xf = x + (size_t)frame * hw * C + gc * 8;
     bf16* yf = y + (size_t)frame * hw * C + gc * 8;
-    auto emit = [&](int pix, bf16x8 v) {
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float f = fmaf(bf2f(v[e]), a[e], b[e]);
-            if (silu) f = silu_f(f);
-            o[e] = f2bf(f);
-        }
-        *(bf16x8*)(yf + (size_t)pix * C) = o;
-    };
     int pix = p0 + rs;
     for (; pix + 3 * RS < p1; pix += 4 * RS) {
         bf16x8 v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = *(const bf16x8*)(xf + (size_t)(pix + k * RS) * C);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) emit(pix + k * RS, v[k]);
+        for (int k = 0; k < 4; ++k) affine_store(yf + (size_t)(pix + k * RS) * C, v[k], a, b, silu);
     }
-    for (; pix < p1; pix += RS) emit(pix, *(const bf16x8*)(xf + (size_t)pix * C));
+    for (; pix < p1; pix += RS) affine_store(yf + (size_t)pix * C, *(const bf16x8*)(xf + (size_t)pix * C), a, b, silu);
 }
 
 void launch_gn_apply(dim3 grid, hipStream_t s, const bf16* x, bf16* y, const double* stats, const float* gamma,
@@ -820,14 +738,39 @@ __global__ void zero_f64_kernel(double* p, int n) {
     if (i < n) p[i] = 0.0;
 }
 
+void launch_gn_stats(hipStream_t s, const bf16* x, double* stats, int frames, int hw, int C) {
+    // the per-block reduction tail (LDS + global atomics) costs about as much as reading 16 pixel rows per wave:
+    // give a stats block 256 pixels when the frame is large enough to still fill the chip
+    int spb = 256;
+    while (spb > 16 && (int64_t)((hw + spb - 1) / spb) * frames < 512) spb >>= 1;
+    hipLaunchKernelGGL(gn_spatial_stats_kernel, dim3((hw + spb - 1) / spb, frames), dim3(256), 0, s, x, stats, hw, C, spb);
+}
+
+// Grid, granules-per-lane template arm and label of the two LayerNorm entry points: launch(N, grid) starts instantiation <N> of
+// `kernel`.  (rpw is chosen by the entry point: tests/_norm_ref.py reads that loop from each of the two.)
+template <class Launch>
+void ln_launch(const char* kernel, int64_t rows, int C, int rpw, Launch launch) {
+    const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+    const int cols = (C / 8 + 63) / 64;
+    if (cols == 1) launch(std::integral_constant<int, 1>{}, grid);
+    else if (cols == 2) launch(std::integral_constant<int, 2>{}, grid);
+    else launch(std::integral_constant<int, kLnCols>{}, grid);
+    cc_note_kernel("%s<%d> rpw=%d", kernel, cols < kLnCols ? cols : kLnCols, rpw);
+}
+
 }  // namespace
+
+// A width the kernels of an entry point cannot take: C is not whole groups / granules (C % MOD), or a lane would own more than
+// COLS 16-byte granules of a row
+#define CC_REFUSE_C(name, MOD, COLS) \
+    CC_UNSUPPORTED(C % MOD != 0 || C > COLS * 512, name ": C=%d (need C%%" #MOD "==0, C<=%d)", C, COLS * 512)
+#define CC_REFUSE_C_TERSE(name, MOD, COLS) CC_UNSUPPORTED(C % MOD != 0 || C > COLS * 512, name ": C=%d", C)
 
 extern "C" int ccedit_groupnorm_spatial(const void* x, void* y, const float* gamma, const float* beta, double* stats_ws,
                                         int32_t frames, int32_t hw, int32_t C, float eps, int32_t silu, void* stream) {
     CC_CHECK_ARG(x && y && gamma && beta && stats_ws, "ccedit_groupnorm_spatial: null pointer");
     CC_CHECK_ARG(frames > 0 && hw > 0 && C > 0, "ccedit_groupnorm_spatial: bad sizes");
-    CC_UNSUPPORTED(C % 32 != 0 || C > kMaxCols * 512, "ccedit_groupnorm_spatial: C=%d (need C%%32==0, C<=%d)", C,
-                   kMaxCols * 512);
+    CC_REFUSE_C("ccedit_groupnorm_spatial", 32, kMaxCols);
     hipStream_t s = (hipStream_t)stream;
     if (C % 256 == 0 && (int64_t)hw * (C / 256) <= 256 * kGnOneUnits) {       // small frames: one pass, one launch
         hipLaunchKernelGGL(gn_spatial_onepass_kernel, dim3(32, frames), dim3(256), 0, s, (const bf16*)x, (bf16*)y, gamma, beta, hw, C, eps, silu);
@@ -838,22 +781,15 @@ extern "C" int ccedit_groupnorm_spatial(const void* x, void* y, const float* gam
     hipLaunchKernelGGL(zero_f64_kernel, dim3((unsigned)((64 * frames + 255) / 256)), dim3(256), 0, s, stats_ws, 64 * frames);
     const int apb = gn_pix_per_block(hw, frames, 4, 2048);
     dim3 grid((hw + apb - 1) / apb, frames);
-    // the per-block reduction tail (LDS + global atomics) costs about as much as reading 16 pixel rows per wave:
-    // give a stats block 256 pixels when the frame is large enough to still fill the chip
-    int spb = 256;
-    while (spb > 16 && (int64_t)((hw + spb - 1) / spb) * frames < 512) spb >>= 1;
-    dim3 sgrid((hw + spb - 1) / spb, frames);
-    hipLaunchKernelGGL(gn_spatial_stats_kernel, sgrid, dim3(256), 0, s, (const bf16*)x, stats_ws, hw, C, spb);
+    launch_gn_stats(s, (const bf16*)x, stats_ws, frames, hw, C);
     launch_gn_apply(grid, s, (const bf16*)x, (bf16*)y, stats_ws, gamma, beta, hw, C, eps, silu, apb);
     return cc_launch_status("groupnorm_spatial");
 }
 
 extern "C" int ccedit_groupnorm_spatial_stats(const void* x, double* stats, int32_t frames, int32_t hw, int32_t C, void* stream) {
     CC_CHECK_ARG(x && stats && frames > 0 && hw > 0 && C > 0, "ccedit_groupnorm_spatial_stats: bad args");
-    CC_UNSUPPORTED(C % 32 != 0 || C > kMaxCols * 512, "ccedit_groupnorm_spatial_stats: C=%d (need C%%32==0, C<=%d)", C, kMaxCols * 512);
-    int spb = 256;
-    while (spb > 16 && (int64_t)((hw + spb - 1) / spb) * frames < 512) spb >>= 1;
-    hipLaunchKernelGGL(gn_spatial_stats_kernel, dim3((hw + spb - 1) / spb, frames), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, stats, hw, C, spb);
+    CC_REFUSE_C("ccedit_groupnorm_spatial_stats", 32, kMaxCols);
+    launch_gn_stats((hipStream_t)stream, (const bf16*)x, stats, frames, hw, C);
     return cc_launch_status("groupnorm_spatial_stats");
 }
 
@@ -862,8 +798,7 @@ extern "C" int ccedit_groupnorm_spatial_apply(const void* x, void* y, const floa
                                               int32_t silu, void* stream) {
     CC_CHECK_ARG(x && y && gamma && beta && stats, "ccedit_groupnorm_spatial_apply: null pointer");
     CC_CHECK_ARG(frames > 0 && hw > 0 && C > 0, "ccedit_groupnorm_spatial_apply: bad sizes");
-    CC_UNSUPPORTED(C % 32 != 0 || C > kMaxCols * 512, "ccedit_groupnorm_spatial_apply: C=%d (need C%%32==0, C<=%d)", C,
-                   kMaxCols * 512);
+    CC_REFUSE_C("ccedit_groupnorm_spatial_apply", 32, kMaxCols);
     const int apb = gn_pix_per_block(hw, frames, 4, 2048);
     dim3 grid((hw + apb - 1) / apb, frames);
     launch_gn_apply(grid, (hipStream_t)stream, (const bf16*)x, (bf16*)y, stats, gamma, beta, hw, C, eps, silu, apb);
@@ -874,8 +809,7 @@ extern "C" int ccedit_groupnorm_temporal(const void* x, void* y, const float* ga
                                          int32_t T, int32_t hw, int32_t C, float eps, int32_t silu, void* stream) {
     CC_CHECK_ARG(x && y && gamma && beta, "ccedit_groupnorm_temporal: null pointer");
     CC_CHECK_ARG(B > 0 && T > 0 && hw > 0 && C > 0, "ccedit_groupnorm_temporal: bad sizes");
-    CC_UNSUPPORTED(C % 32 != 0 || C > kGtCols * 512, "ccedit_groupnorm_temporal: C=%d (need C%%32==0, C<=%d)", C,
-                   kGtCols * 512);
+    CC_REFUSE_C("ccedit_groupnorm_temporal", 32, kGtCols);
     const int64_t waves = (int64_t)B * hw;
     dim3 grid((unsigned)((waves + 3) / 4));
     int nsl = 1;                                   // channel slices: whole groups, at most 512 channels each
@@ -910,7 +844,7 @@ extern "C" int ccedit_groupnorm_temporal(const void* x, void* y, const float* ga
 extern "C" int ccedit_groupnorm_temporal_stats(const void* x, float* stats, int32_t B, int32_t T, int32_t hw, int32_t C,
                                                void* stream) {
     CC_CHECK_ARG(x && stats && B > 0 && T > 0 && hw > 0 && C > 0, "ccedit_groupnorm_temporal_stats: bad args");
-    CC_UNSUPPORTED(C % 32 != 0 || C > kGtCols * 512, "ccedit_groupnorm_temporal_stats: C=%d", C);
+    CC_REFUSE_C_TERSE("ccedit_groupnorm_temporal_stats", 32, kGtCols);
     const int64_t waves = (int64_t)B * hw;
     hipLaunchKernelGGL(gn_temporal_stats_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16*)x, stats, B, T, hw, C);
@@ -924,7 +858,7 @@ extern "C" int ccedit_groupnorm_temporal_apply(const void* x, void* y, const flo
     CC_CHECK_ARG(x && y && gamma && beta && stats && B > 0 && T > 0 && hw > 0 && C > 0 && count > 0,
                  "ccedit_groupnorm_temporal_apply: bad args");
     CC_CHECK_ARG(dst_frames >= T + dst_off && dst_off >= 0, "ccedit_groupnorm_temporal_apply: bad destination geometry");
-    CC_UNSUPPORTED(C % 32 != 0 || C > kGtCols * 512, "ccedit_groupnorm_temporal_apply: C=%d", C);
+    CC_REFUSE_C_TERSE("ccedit_groupnorm_temporal_apply", 32, kGtCols);
     const int64_t waves = (int64_t)B * hw;
     hipLaunchKernelGGL(gn_temporal_apply_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16*)x, (bf16*)y, gamma, beta, stats, B, T, hw, C, count, eps, silu, dst_frames, dst_off);
@@ -932,71 +866,16 @@ extern "C" int ccedit_groupnorm_temporal_apply(const void* x, void* y, const flo
     return cc_launch_status("groupnorm_temporal_apply");
 }
 
-// The statistics half of layernorm_kernel: (mean, rstd) per row, same summation order (a consumer that folds the LayerNorm into
-// its GEMM — CcGemmDesc.ln_stats — sees the numbers the normalising kernel would have used).
-template <int COLS>
-__global__ __launch_bounds__(256) void row_stats_kernel(const bf16* __restrict__ x, float* __restrict__ st, int64_t rows, int C, float eps, int rpw) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * rpw;
-    if (row0 >= rows) return;
-    const int G8 = C >> 3;
-    const float inv_c = 1.0f / (float)C;
-    const int nr = (int)min((int64_t)rpw, rows - row0);
-    for (int r = 0; r < nr; r += 2) {
-        const bool two = r + 1 < nr;
-        const bf16* x0 = x + (size_t)(row0 + r) * C;
-        const bf16* x1 = x0 + (two ? C : 0);
-        bf16x8 t0[COLS], t1[COLS];
-#pragma unroll
-        for (int k = 0; k < COLS; ++k) {
-            const int gc = lane + 64 * k;
-            if (gc < G8) {
-                t0[k] = *(const bf16x8*)(x0 + gc * 8);
-                t1[k] = *(const bf16x8*)(x1 + gc * 8);
-            }
-        }
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < COLS; ++k)
-            if (lane + 64 * k < G8) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    s0 += bf2f(t0[k][e]);
-                    s1 += bf2f(t1[k][e]);
-                }
-            }
-        const float m0 = wave_sum(s0) * inv_c, m1 = wave_sum(s1) * inv_c;
-        float q0 = 0.f, q1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < COLS; ++k)
-            if (lane + 64 * k < G8) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float d0 = bf2f(t0[k][e]) - m0, d1 = bf2f(t1[k][e]) - m1;
-                    q0 += d0 * d0;
-                    q1 += d1 * d1;
-                }
-            }
-        const float r0 = rsqrtf(wave_sum(q0) * inv_c + eps), r1 = rsqrtf(wave_sum(q1) * inv_c + eps);
-        if (lane == 0) {
-            *(f32x2*)(st + 2 * (row0 + r)) = f32x2{m0, r0};
-            if (two) *(f32x2*)(st + 2 * (row0 + r + 1)) = f32x2{m1, r1};
-        }
-    }
-}
-
 extern "C" int ccedit_row_stats(const void* x, float* stats, int64_t rows, int32_t C, float eps, void* stream) {
     CC_CHECK_ARG(x && stats, "ccedit_row_stats: null pointer");
     CC_CHECK_ARG(rows > 0 && C > 0, "ccedit_row_stats: bad sizes");
-    CC_UNSUPPORTED(C % 8 != 0 || C > kLnCols * 512, "ccedit_row_stats: C=%d (need C%%8==0, C<=%d)", C, kLnCols * 512);
+    CC_REFUSE_C("ccedit_row_stats", 8, kLnCols);
     int rpw = kLnRowsPerWave;
     while (rpw > 1 && (rows + 4 * rpw - 1) / (4 * rpw) < 4096) rpw >>= 1;
-    dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
-    const int cols = (C / 8 + 63) / 64;
-#define CC_RS(N) hipLaunchKernelGGL(row_stats_kernel<N>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, stats, rows, C, eps, rpw)
-    if (cols == 1) CC_RS(1); else if (cols == 2) CC_RS(2); else CC_RS(kLnCols);
-#undef CC_RS
-    cc_note_kernel("row_stats_kernel<%d> rpw=%d", cols < kLnCols ? cols : kLnCols, rpw);
+    ln_launch("row_stats_kernel", rows, C, rpw, [&](auto n, dim3 grid) {
+        hipLaunchKernelGGL(row_stats_kernel<decltype(n)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, stats, rows, C, eps,
+                           rpw);
+    });
     return cc_launch_status("row_stats");
 }
 
@@ -1004,14 +883,15 @@ extern "C" int ccedit_layernorm(const void* x, void* y, const float* gamma, cons
                                 float eps, void* stream) {
     CC_CHECK_ARG(x && y && gamma && beta, "ccedit_layernorm: null pointer");
     CC_CHECK_ARG(rows > 0 && C > 0, "ccedit_layernorm: bad sizes");
-    CC_UNSUPPORTED(C % 8 != 0 || C > kLnCols * 512, "ccedit_layernorm: C=%d (need C%%8==0, C<=%d)", C, kLnCols * 512);
+    CC_REFUSE_C("ccedit_layernorm", 8, kLnCols);
     int rpw = kLnRowsPerWave;
     while (rpw > 1 && (rows + 4 * rpw - 1) / (4 * rpw) < 4096) rpw >>= 1;
-    dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
-    const int cols = (C / 8 + 63) / 64;
-#define CC_LN(N) hipLaunchKernelGGL(layernorm_kernel<N>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, gamma, beta, rows, C, eps, rpw)
-    if (cols == 1) CC_LN(1); else if (cols == 2) CC_LN(2); else CC_LN(kLnCols);
-#undef CC_LN
-    cc_note_kernel("layernorm_kernel<%d> rpw=%d", cols < kLnCols ? cols : kLnCols, rpw);
+    ln_launch("layernorm_kernel", rows, C, rpw, [&](auto n, dim3 grid) {
+        hipLaunchKernelGGL(layernorm_kernel<decltype(n)::value>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, gamma, beta,
+                           rows, C, eps, rpw);
+    });
     return cc_launch_status("layernorm");
 }
+
+#undef CC_REFUSE_C
+#undef CC_REFUSE_C_TERSE

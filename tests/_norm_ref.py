@@ -23,6 +23,14 @@ with a fixed summation order — a second launch gives the same bits.
 
 Arm prediction (`predict`).  The dispatch arithmetic of norm.hip restated in Python, with every threshold READ from the literals of
 norm.hip (`thresholds`): a retune that moves a case to another arm fails tests/test_norm_ref.py on the CPU.
+
+What the arms share.  The kernels of norm.hip are assembled from one copy of each building block: the group boundary inside a
+16-byte granule (`group_split`, behind every arm that meets a straddling granule: gn_temporal_flat, gn_temporal_cached,
+gn_spatial_apply, gn_spatial_apply_flat), the affine coefficients (`affine_channel`, `affine_two_groups`), the multiply-add + SiLU +
+store (`affine_store`), the temporal sweeps (`gt_stats_sweep`, `gt_affine`, `gt_apply_sweep`: gn_temporal_kernel and its sharded
+halves) and the two-row LayerNorm statistics (`ln_two_row_stats`: layernorm_kernel and row_stats_kernel).  A mistake in one of
+them shows on every arm that calls it; the cases still reach every arm, because each arm keeps its own mapping and source of
+statistics.  The rows-per-wave loop is read from both LayerNorm entry points, which share only `ln_launch` (grid, template arm, label).
 """
 import math
 import os

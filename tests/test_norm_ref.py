@@ -211,7 +211,8 @@ def test_defect_table_covers_every_form():
                      ("gt2", "group+1 group-1 pixel+1 pixel-1 clip+1 clip-1 count+1 count-1 eps affine+8 nosilu dst_off0"),
                      ("gs", "group+1 group-1 frame+1 frame-1 eps affine+8 nosilu"), ("ln", "partner eps affine+8")):
         assert {(op, df) for df in want.split()} <= seen
-    # the straddling-granule logic exists in four kernels: each has a case with cpg % 8 != 0
+    # the straddling-granule logic is one function (group_split of norm.hip) that four kernels call, each with its own source of
+    # statistics: each has a case with cpg % 8 != 0
     straddle = {arm[-1].split(" ")[0].split("<")[0] for cs in structured if (cs.c // 32) % 8 for arm in cs.arms}
     assert {"gn_temporal_flat_kernel", "gn_temporal_cached_kernel", "gn_spatial_apply_flat_kernel", "gn_spatial_apply_kernel"} <= straddle
 
