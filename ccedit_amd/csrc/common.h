@@ -204,3 +204,16 @@ int cc_gif_lzw(const uint8_t* indices, uint8_t* slots, int32_t* chunk_bits, int3
 int cc_gif_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t* frame_bytes, int32_t N, int32_t H, int32_t W, int32_t chunk, hipStream_t s);
 int cc_gif_pack(const uint8_t* slots, const int32_t* chunk_bits, const int64_t* chunk_off, uint8_t* out, int32_t N, int32_t H, int32_t W, int32_t chunk,
                 int64_t out_bytes, hipStream_t s);
+
+// PNG launchers (png.hip); entry points and argument checks in core.cpp
+int64_t cc_png_slot_bytes();
+int64_t cc_png_chunk_bytes();
+int cc_png_filter(const uint8_t* frames, uint8_t* filtered, int32_t N, int32_t H, int32_t W, hipStream_t s);
+int cc_png_tokens(const uint8_t* filtered, uint32_t* tokens, int32_t* ntok, uint32_t* hist, int32_t N, int64_t L, hipStream_t s);
+int cc_png_codes(const uint32_t* hist, uint32_t* codes, uint32_t* header, int32_t* header_bits, int32_t* chunk_bits, int32_t N, int32_t C, hipStream_t s);
+int cc_png_emit(const uint32_t* tokens, const int32_t* ntok, const uint32_t* codes, const uint32_t* header, const int32_t* header_bits, uint8_t* slots,
+                int64_t total, hipStream_t s);
+int cc_png_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t* frame_bytes, int32_t N, int32_t C, hipStream_t s);
+int cc_png_pack(const uint8_t* slots, const int32_t* chunk_bits, const int64_t* chunk_off, uint8_t* out, int32_t N, int32_t C, int64_t out_bytes,
+                hipStream_t s);
+int cc_png_adler(const uint8_t* filtered, uint32_t* partials, uint32_t* adler, int32_t N, int64_t L, hipStream_t s);

@@ -458,3 +458,81 @@ extern "C" int ccedit_gif_pack(const void* slots, const int32_t* chunk_bits, con
                  "ccedit_gif_pack: slots, chunk_bits and out must be 4-byte aligned, chunk_off 8-byte");
     return cc_gif_pack((const uint8_t*)slots, chunk_bits, chunk_off, (uint8_t*)out, N, H, W, chunk, out_bytes, (hipStream_t)stream);
 }
+
+// ---- PNG (kernels and launchers: png.hip).  Everything the host can see is checked here, before any HIP call; token words, histograms
+// and bit lengths are device data, which the kernels mask and clamp themselves.
+static const int64_t kPngMaxLength = 65535 + 3 * kGifMaxPixels;          // H * (1 + 3 W) with H <= 65535 and H * W <= 2^24
+
+static int png_streams_ok(const char* fn, int32_t N, int64_t L) {
+    CC_CHECK_ARG(N >= 1 && N <= kGifMaxFrames, "%s: N=%d streams (1 ... 65535)", fn, N);
+    CC_CHECK_ARG(L >= 1 && L <= kPngMaxLength, "%s: L=%lld bytes per stream (1 ... 65535 + 3 * 2^24)", fn, (long long)L);
+    CC_CHECK_ARG((int64_t)N * ((L + cc_png_chunk_bytes() - 1) / cc_png_chunk_bytes()) <= kGifMaxChunks,
+                 "%s: N=%d streams of %lld bytes are more than 2^22 chunks: encode fewer at a time", fn, N, (long long)L);
+    return 0;
+}
+
+static int png_chunks_ok(const char* fn, int32_t N, int32_t C) {
+    CC_CHECK_ARG(N >= 1 && N <= kGifMaxFrames, "%s: N=%d streams (1 ... 65535)", fn, N);
+    CC_CHECK_ARG(C >= 1 && (int64_t)N * C <= kGifMaxChunks, "%s: C=%d chunks per stream (>= 1, N * C <= 2^22)", fn, C);
+    return 0;
+}
+
+extern "C" int64_t ccedit_png_chunk_bytes(void) { return cc_png_chunk_bytes(); }
+extern "C" int64_t ccedit_png_slot_bytes(void) { return cc_png_slot_bytes(); }
+
+extern "C" int ccedit_png_filter(const void* frames, void* filtered, int32_t N, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(frames && filtered, "ccedit_png_filter: null pointer (frames and filtered are required)");
+    if (int rc = gif_shape_ok("ccedit_png_filter", N, H, W)) return rc;
+    return cc_png_filter((const uint8_t*)frames, (uint8_t*)filtered, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_png_tokens(const void* filtered, uint32_t* tokens, int32_t* ntok, uint32_t* hist, int32_t N, int64_t L, void* stream) {
+    CC_CHECK_ARG(filtered && tokens && ntok && hist, "ccedit_png_tokens: null pointer (filtered, tokens, ntok and hist are required)");
+    if (int rc = png_streams_ok("ccedit_png_tokens", N, L)) return rc;
+    CC_CHECK_ARG((((uintptr_t)tokens | (uintptr_t)ntok | (uintptr_t)hist) & 3) == 0, "ccedit_png_tokens: tokens, ntok and hist must be 4-byte aligned");
+    return cc_png_tokens((const uint8_t*)filtered, tokens, ntok, hist, N, L, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_png_codes(const uint32_t* hist, uint32_t* codes, uint32_t* header, int32_t* header_bits, int32_t* chunk_bits, int32_t N, int32_t C,
+                                void* stream) {
+    CC_CHECK_ARG(hist && codes && header && header_bits && chunk_bits, "ccedit_png_codes: null pointer");
+    if (int rc = png_chunks_ok("ccedit_png_codes", N, C)) return rc;
+    CC_CHECK_ARG((((uintptr_t)hist | (uintptr_t)codes | (uintptr_t)header | (uintptr_t)header_bits | (uintptr_t)chunk_bits) & 3) == 0,
+                 "ccedit_png_codes: every buffer must be 4-byte aligned");
+    return cc_png_codes(hist, codes, header, header_bits, chunk_bits, N, C, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_png_emit(const uint32_t* tokens, const int32_t* ntok, const uint32_t* codes, const uint32_t* header, const int32_t* header_bits,
+                               void* slots, int64_t chunks, void* stream) {
+    CC_CHECK_ARG(tokens && ntok && codes && header && header_bits && slots, "ccedit_png_emit: null pointer");
+    CC_CHECK_ARG(chunks >= 1 && chunks <= kGifMaxChunks, "ccedit_png_emit: chunks=%lld (1 ... 2^22)", (long long)chunks);
+    CC_CHECK_ARG((((uintptr_t)tokens | (uintptr_t)ntok | (uintptr_t)codes | (uintptr_t)header | (uintptr_t)header_bits | (uintptr_t)slots) & 3) == 0,
+                 "ccedit_png_emit: every buffer must be 4-byte aligned");
+    return cc_png_emit(tokens, ntok, codes, header, header_bits, (uint8_t*)slots, chunks, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_png_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t* frame_bytes, int32_t N, int32_t C, void* stream) {
+    CC_CHECK_ARG(chunk_bits && chunk_off && frame_bytes, "ccedit_png_pack_scan: null pointer");
+    if (int rc = png_chunks_ok("ccedit_png_pack_scan", N, C)) return rc;
+    CC_CHECK_ARG((((uintptr_t)chunk_bits | (uintptr_t)frame_bytes) & 3) == 0 && ((uintptr_t)chunk_off & 7) == 0,
+                 "ccedit_png_pack_scan: chunk_bits and frame_bytes must be 4-byte aligned, chunk_off 8-byte");
+    return cc_png_pack_scan(chunk_bits, chunk_off, frame_bytes, N, C, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_png_pack(const void* slots, const int32_t* chunk_bits, const int64_t* chunk_off, void* out, int32_t N, int32_t C, int64_t out_bytes,
+                               void* stream) {
+    CC_CHECK_ARG(slots && chunk_bits && chunk_off && out, "ccedit_png_pack: null pointer");
+    if (int rc = png_chunks_ok("ccedit_png_pack", N, C)) return rc;
+    CC_CHECK_ARG(out_bytes >= 1 && out_bytes < kPixelMax * 4, "ccedit_png_pack: out_bytes=%lld (1 ... 2^33: the sum of frame_bytes)",
+                 (long long)out_bytes);
+    CC_CHECK_ARG((((uintptr_t)slots | (uintptr_t)chunk_bits | (uintptr_t)out) & 3) == 0 && ((uintptr_t)chunk_off & 7) == 0,
+                 "ccedit_png_pack: slots, chunk_bits and out must be 4-byte aligned, chunk_off 8-byte");
+    return cc_png_pack((const uint8_t*)slots, chunk_bits, chunk_off, (uint8_t*)out, N, C, out_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_png_adler(const void* filtered, uint32_t* partials, uint32_t* adler, int32_t N, int64_t L, void* stream) {
+    CC_CHECK_ARG(filtered && partials && adler, "ccedit_png_adler: null pointer (filtered, partials and adler are required)");
+    if (int rc = png_streams_ok("ccedit_png_adler", N, L)) return rc;
+    CC_CHECK_ARG((((uintptr_t)partials | (uintptr_t)adler) & 3) == 0, "ccedit_png_adler: partials and adler must be 4-byte aligned");
+    return cc_png_adler((const uint8_t*)filtered, partials, adler, N, L, (hipStream_t)stream);
+}

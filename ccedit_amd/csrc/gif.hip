@@ -25,6 +25,7 @@
 // are clamped into the slot, and a chunk whose bits would leave the output is skipped.  The argument checks live with the exported entry
 // points in core.cpp.
 #include "common.h"
+#include "bitpack.h"
 
 namespace {
 
@@ -38,8 +39,6 @@ constexpr int kSlotBits = kSlotWords * 32;
 constexpr int kHashWords = 4096;
 constexpr int kLzwChunks = 4;                    // chunks (= live lanes) per workgroup of the LZW stage: 4 x 16 KB of LDS
 constexpr uint32_t kEmpty = 0xffffffffu;         // prefix 4095 is never a code
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll
@@ -315,72 +314,15 @@ __global__ __launch_bounds__(64) void gif_lzw_kernel(const uint8_t* __restrict__
     chunk_bits[id] = (int32_t)out.bits;
 }
 
-// ---- pack: where every chunk's bits go (a workgroup per frame), then the shifted copy (a workgroup per chunk)
+// ---- pack: where every chunk's bits go (a workgroup per frame), then the shifted copy (a workgroup per chunk): bitpack.h, shared with png.hip
 __global__ __launch_bounds__(kThreads) void gif_pack_scan_kernel(const int32_t* __restrict__ chunk_bits, int64_t* __restrict__ chunk_off,
                                                                  int32_t* __restrict__ frame_bytes, int C) {
-    __shared__ int64_t s_part[kThreads];
-    const int tid = threadIdx.x;
-    const int64_t f = blockIdx.x;
-    int64_t sum = 0;
-    for (int64_t g = tid; g < f; g += kThreads) {                                // the bytes of the frames before this one
-        int64_t bits = 0;
-        for (int c = 0; c < C; ++c) bits += clampi(chunk_bits[g * C + c], 0, kSlotBits);
-        sum += (bits + 7) >> 3;
-    }
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if (tid < o) s_part[tid] += s_part[tid + o];
-        __syncthreads();
-    }
-    const int64_t start = s_part[0] * 8;
-    __syncthreads();
-    const int per = (C + kThreads - 1) / kThreads;                               // chunks per thread, consecutive
-    const int c0 = tid * per < C ? tid * per : C, c1 = c0 + per < C ? c0 + per : C;
-    int64_t mine = 0;
-    for (int c = c0; c < c1; ++c) mine += clampi(chunk_bits[f * C + c], 0, kSlotBits);
-    s_part[tid] = mine;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t acc = 0;
-        for (int i = 0; i < kThreads; ++i) {
-            const int64_t v = s_part[i];
-            s_part[i] = acc;
-            acc += v;
-        }
-        const int64_t bytes = (acc + 7) >> 3;
-        frame_bytes[f] = (int32_t)(bytes < 0x7fffffff ? bytes : 0x7fffffff);
-    }
-    __syncthreads();
-    int64_t at = start + s_part[tid];
-    for (int c = c0; c < c1; ++c) {
-        chunk_off[f * C + c] = at;
-        at += clampi(chunk_bits[f * C + c], 0, kSlotBits);
-    }
+    cc_pack_scan<kThreads, kSlotBits>(chunk_bits, chunk_off, frame_bytes, C);
 }
 
 __global__ __launch_bounds__(kThreads) void gif_pack_kernel(const uint32_t* __restrict__ slots, const int32_t* __restrict__ chunk_bits,
                                                             const int64_t* __restrict__ chunk_off, uint32_t* __restrict__ out, int64_t out_bits) {
-    const int64_t id = blockIdx.x;
-    const int len = clampi(chunk_bits[id], 0, kSlotBits);
-    const int64_t off = chunk_off[id];
-    if (len == 0 || off < 0 || off > out_bits - len) return;                      // (cannot happen with the offsets of gif_pack_scan)
-    const uint32_t* src = slots + id * kSlotWords;
-    const int nsrc = (len + 31) >> 5;
-    const uint32_t tail = (len & 31) ? (1u << (len & 31)) - 1u : 0xffffffffu;       // what the last source word holds
-    const uint32_t sh = (uint32_t)(off & 31);
-    const int64_t w0 = off >> 5;
-    const int nout = (int)(((off + len - 1) >> 5) - w0) + 1;
-    for (int j = threadIdx.x; j < nout; j += kThreads) {
-        uint32_t lo = 0, hi = 0;                                                  // source words j - 1 and j
-        if (j < nsrc) hi = src[j] & (j == nsrc - 1 ? tail : 0xffffffffu);
-        if (j >= 1 && j - 1 < nsrc) lo = src[j - 1] & (j - 1 == nsrc - 1 ? tail : 0xffffffffu);
-        const uint32_t v = sh ? (hi << sh) | (lo >> (32u - sh)) : hi;
-        if (j == 0 || j == nout - 1)
-            atomicOr(out + w0 + j, v);
-        else
-            out[w0 + j] = v;
-    }
+    cc_pack_chunk<kThreads, kSlotWords>(slots, chunk_bits, chunk_off, out, out_bits);
 }
 
 }  // namespace

@@ -1300,3 +1300,130 @@ def gif_pack(slots: torch.Tensor, chunk_bits: torch.Tensor, chunk_off: torch.Ten
     hip.check(hip.lib().ccedit_gif_pack(slots.data_ptr(), chunk_bits.data_ptr(), chunk_off.data_ptr(), out.data_ptr(), int(frames), int(h), int(w),
                                         int(chunk), int(out_bytes), _stream()), "ccedit_gif_pack")
     return out[:int(out_bytes)]
+
+
+# ------------------------------------------------------------------------------------------
+# PNG output (csrc/png.hip; constants, the frame loop and the container: ccedit_amd/png.py).  32-bit words (tokens, histograms, code
+# tables, header bits) travel as int32 tensors holding the uint32 bit patterns.
+# ------------------------------------------------------------------------------------------
+def png_slot_bytes() -> int:
+    from . import png
+    n, c = int(hip.lib().ccedit_png_slot_bytes()), int(hip.lib().ccedit_png_chunk_bytes())
+    if n != png.SLOT_BYTES or c != png.CHUNK:
+        raise hip.HipLibraryError(f"ccedit_png_slot_bytes / ccedit_png_chunk_bytes: the library codes chunks of {c} bytes into slots of {n}, "
+                                  f"ccedit_amd/png.py says {png.CHUNK} and {png.SLOT_BYTES}")
+    return n
+
+
+def _png_chunks(name: str, t: torch.Tensor, streams: int, width: int) -> int:
+    """A per-chunk int32 table (streams * C, width) -> C."""
+    if (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != width or int(streams) < 1
+            or t.shape[0] < 1 or t.shape[0] % int(streams)):
+        raise ValueError(f"{name}: expected a contiguous cuda int32 tensor (streams * C, {width}) for {streams} streams, got {t.dtype} {t.device} "
+                         f"{tuple(t.shape)}")
+    return t.shape[0] // int(streams)
+
+
+def png_filter(frames: torch.Tensor) -> torch.Tensor:
+    """uint8 frames (N, H, W, 3) -> filtered uint8 (N, H, 1 + 3 W): per row the filter byte and the filtered bytes."""
+    from . import png
+    _chk_u8(frames, "png_filter", 4)
+    n, h, w, c = frames.shape
+    if c != 3 or n < 1:
+        raise ValueError(f"png_filter: RGB frames (N, H, W, 3), N >= 1, got {tuple(frames.shape)}")
+    png.check_size(h, w)
+    out = torch.empty((n, h, png.row_bytes(w)), dtype=torch.uint8, device=frames.device)
+    hip.check(hip.lib().ccedit_png_filter(frames.data_ptr(), out.data_ptr(), n, h, w, _stream()), "ccedit_png_filter")
+    return out
+
+
+def _png_streams(filtered: torch.Tensor, name: str):
+    from . import png
+    _chk_u8(filtered, name, 2)
+    n, length = filtered.shape
+    if n < 1 or length < 1:
+        raise ValueError(f"{name}: byte streams (N, L) with N >= 1 and L >= 1, got {tuple(filtered.shape)}")
+    png_slot_bytes()
+    return n, length, png.chunks_of(length)
+
+
+def png_tokens(filtered: torch.Tensor):
+    """Byte streams uint8 (N, L) -> (tokens int32 (N * C, CHUNK), ntok int32 (N * C,), hist int32 (N * C, HIST_WORDS)): every chunk of
+    png.CHUNK bytes walked on its own."""
+    from . import png
+    n, length, c = _png_streams(filtered, "png_tokens")
+    tokens = torch.empty((n * c, png.CHUNK), dtype=torch.int32, device=filtered.device)
+    ntok = torch.empty((n * c,), dtype=torch.int32, device=filtered.device)
+    hist = torch.empty((n * c, png.HIST_WORDS), dtype=torch.int32, device=filtered.device)
+    hip.check(hip.lib().ccedit_png_tokens(filtered.data_ptr(), tokens.data_ptr(), ntok.data_ptr(), hist.data_ptr(), n, length, _stream()),
+              "ccedit_png_tokens")
+    return tokens, ntok, hist
+
+
+def png_codes(hist: torch.Tensor, streams: int):
+    """hist (streams * C, HIST_WORDS) -> (codes int32 (streams * C, HIST_WORDS), header int32 (streams * C, HEADER_WORDS), header_bits and
+    chunk_bits int32 (streams * C,)); a stream's last chunk gets BFINAL."""
+    from . import png
+    c = _png_chunks("png_codes: hist", hist, streams, png.HIST_WORDS)
+    png_slot_bytes()
+    total = hist.shape[0]
+    codes = torch.empty((total, png.HIST_WORDS), dtype=torch.int32, device=hist.device)
+    header = torch.empty((total, png.HEADER_WORDS), dtype=torch.int32, device=hist.device)
+    header_bits = torch.empty((total,), dtype=torch.int32, device=hist.device)
+    chunk_bits = torch.empty((total,), dtype=torch.int32, device=hist.device)
+    hip.check(hip.lib().ccedit_png_codes(hist.data_ptr(), codes.data_ptr(), header.data_ptr(), header_bits.data_ptr(), chunk_bits.data_ptr(),
+                                         int(streams), c, _stream()), "ccedit_png_codes")
+    return codes, header, header_bits, chunk_bits
+
+
+def png_emit(tokens: torch.Tensor, ntok: torch.Tensor, codes: torch.Tensor, header: torch.Tensor, header_bits: torch.Tensor) -> torch.Tensor:
+    """-> slots uint8 (chunks, slot_bytes): every chunk's header, tokens and end-of-block, LSB first."""
+    from . import png
+    total = _png_chunks("png_emit: tokens", tokens, 1, png.CHUNK)
+    _png_chunks("png_emit: codes", codes, total, png.HIST_WORDS)
+    _png_chunks("png_emit: header", header, total, png.HEADER_WORDS)
+    _chk_i32(ntok, "png_emit: ntok", (total,))
+    _chk_i32(header_bits, "png_emit: header_bits", (total,))
+    slots = torch.empty((total, png_slot_bytes()), dtype=torch.uint8, device=tokens.device)
+    hip.check(hip.lib().ccedit_png_emit(tokens.data_ptr(), ntok.data_ptr(), codes.data_ptr(), header.data_ptr(), header_bits.data_ptr(),
+                                        slots.data_ptr(), total, _stream()), "ccedit_png_emit")
+    return slots
+
+
+def png_pack_scan(chunk_bits: torch.Tensor, streams: int):
+    """-> (chunk_off int64 (streams * C,): every chunk's bit offset in the packed output, frame_bytes int32 (streams,))."""
+    if chunk_bits.dim() != 1 or int(streams) < 1 or chunk_bits.shape[0] < 1 or chunk_bits.shape[0] % int(streams):
+        raise ValueError(f"png_pack_scan: chunk_bits (streams * C,) for {streams} streams, got {tuple(chunk_bits.shape)}")
+    _chk_i32(chunk_bits, "png_pack_scan: chunk_bits", chunk_bits.shape)
+    total = chunk_bits.shape[0]
+    chunk_off = torch.empty((total,), dtype=torch.int64, device=chunk_bits.device)
+    frame_bytes = torch.empty((int(streams),), dtype=torch.int32, device=chunk_bits.device)
+    hip.check(hip.lib().ccedit_png_pack_scan(chunk_bits.data_ptr(), chunk_off.data_ptr(), frame_bytes.data_ptr(), int(streams), total // int(streams),
+                                             _stream()), "ccedit_png_pack_scan")
+    return chunk_off, frame_bytes
+
+
+def png_pack(slots: torch.Tensor, chunk_bits: torch.Tensor, chunk_off: torch.Tensor, streams: int, out_bytes: int) -> torch.Tensor:
+    """-> uint8 (out_bytes,): the streams' deflate bytes back to back, each its chunks' bits back to back, zero-padded to a byte."""
+    _chk_u8(slots, "png_pack: slots", 2)
+    total = slots.shape[0]
+    if int(streams) < 1 or total < 1 or total % int(streams) or slots.shape[1] != png_slot_bytes():
+        raise ValueError(f"png_pack: slots {tuple(slots.shape)} for {streams} streams: expected (streams * C, {png_slot_bytes()})")
+    _chk_i32(chunk_bits, "png_pack: chunk_bits", (total,))
+    if chunk_off.dtype != torch.int64 or not chunk_off.is_cuda or not chunk_off.is_contiguous() or tuple(chunk_off.shape) != (total,):
+        raise ValueError(f"png_pack: chunk_off: expected a contiguous cuda int64 tensor {(total,)}, got {chunk_off.dtype} {tuple(chunk_off.shape)}")
+    if int(out_bytes) < 1:
+        raise ValueError(f"png_pack: out_bytes={out_bytes} (the sum of frame_bytes, >= 1)")
+    out = torch.empty(((int(out_bytes) + 3) // 4 * 4,), dtype=torch.uint8, device=slots.device)
+    hip.check(hip.lib().ccedit_png_pack(slots.data_ptr(), chunk_bits.data_ptr(), chunk_off.data_ptr(), out.data_ptr(), int(streams),
+                                        total // int(streams), int(out_bytes), _stream()), "ccedit_png_pack")
+    return out[:int(out_bytes)]
+
+
+def png_adler(filtered: torch.Tensor) -> torch.Tensor:
+    """Byte streams uint8 (N, L) -> their Adler-32 words, int64 (N,) (0 ... 2^32 - 1)."""
+    n, length, c = _png_streams(filtered, "png_adler")
+    partials = torch.empty((n * c, 2), dtype=torch.int32, device=filtered.device)
+    adler = torch.empty((n,), dtype=torch.int32, device=filtered.device)
+    hip.check(hip.lib().ccedit_png_adler(filtered.data_ptr(), partials.data_ptr(), adler.data_ptr(), n, length, _stream()), "ccedit_png_adler")
+    return adler.to(torch.int64) & 0xffffffff

@@ -647,6 +647,47 @@ int ccedit_gif_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t*
 int ccedit_gif_pack(const void* slots, const int32_t* chunk_bits, const int64_t* chunk_off, void* out, int32_t N, int32_t H, int32_t W,
                     int32_t chunk, int64_t out_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PNG (added without an ABI bump: nine new functions, CCEDIT_ABI_VERSION stays 12).  `--save_type png`: uint8 frames [N][H][W][3] on the
+ * device (what ccedit_frames_to_u8 writes) -> per frame the deflate bits and the Adler-32 of its filtered rows; ccedit_amd/png.py:
+ * constants, the frame loop, the zlib wrapper (78 01 ... Adler) and the PNG / APNG container.  Kernels: csrc/png.hip, csrc/png_huff.h.
+ * Every byte equals tests/_png_numpy.py, which states the rules in full.  H and W are 1 ... 65535 with H * W <= 2^24; N <= 65535.
+ *
+ * The stages after the filter take N byte streams of L bytes each (L = H * (1 + 3 W) for frames; 1 ... 65535 + 3 * 2^24), cut into
+ * C = ceil(L / chunk) chunks of ccedit_png_chunk_bytes() bytes, N * C <= 2^22; chunk i = stream * C + chunk number.  Each chunk becomes
+ * ONE dynamic-Huffman deflate block; BFINAL is set on a stream's last chunk.
+ *
+ * ccedit_png_chunk_bytes / ccedit_png_slot_bytes: bytes of a chunk (16384), and of one chunk's slot in `slots` (the worst-case header,
+ *   16 bits per byte, end-of-block; a multiple of 16).
+ * ccedit_png_filter: frames -> filtered uint8 [N][H][1 + 3 W]: per row the filter byte (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth: the
+ *   smallest sum of min(v, 256 - v) over the row, the lowest number on a tie) and the filtered bytes; the row above row 0 is zeros.
+ * ccedit_png_tokens: filtered [N][L] -> tokens uint32 [N * C][chunk] (a literal's byte, or 1 << 31 | (length - 3) << 16 | (distance - 1)),
+ *   ntok int32 [N * C] and hist uint32 [N * C][320] (literal/length symbols at 0, end-of-block counted once; distance symbols at 288).
+ *   Greedy LZ77 inside the chunk over a single-entry hash table of 4096 positions; matches of 3 ... 258 bytes.
+ * ccedit_png_codes: hist -> codes uint32 [N * C][320] (length << 16 | the canonical code, bits reversed; lengths <= 15), header uint32
+ *   [N * C][144] (the block header's bits, LSB first: BFINAL, BTYPE = 2, HLIT, HDIST, HCLEN, the code-length code (<= 7 bits), the
+ *   run-coded lengths), header_bits and chunk_bits int32 [N * C] (header + tokens + end-of-block).
+ * ccedit_png_emit: tokens, ntok, codes, header, header_bits -> chunk i's bits at slots + i * slot_bytes (4-byte aligned, zeroed by the
+ *   call itself); `chunks` = N * C.
+ * ccedit_png_pack_scan / ccedit_png_pack: as the GIF pair: chunk_bits (clamped into the slot) -> chunk_off int64 [N * C] and frame_bytes
+ *   int32 [N] (a stream's bits zero-padded to a byte); the chunks' bits shifted to their offsets in out (out_bytes = the sum of
+ *   frame_bytes; the buffer holds out_bytes rounded up to a multiple of 4, 4-byte aligned, zeroed by the call itself).
+ * ccedit_png_adler: filtered [N][L] -> adler uint32 [N] (s2 << 16 | s1); partials: uint32 [N * C][2] of scratch (per chunk the sums
+ *   of d[k] and of (n - k) d[k] mod 65521).
+ */
+int64_t ccedit_png_chunk_bytes(void);
+int64_t ccedit_png_slot_bytes(void);
+int ccedit_png_filter(const void* frames, void* filtered, int32_t N, int32_t H, int32_t W, void* stream);
+int ccedit_png_tokens(const void* filtered, uint32_t* tokens, int32_t* ntok, uint32_t* hist, int32_t N, int64_t L, void* stream);
+int ccedit_png_codes(const uint32_t* hist, uint32_t* codes, uint32_t* header, int32_t* header_bits, int32_t* chunk_bits, int32_t N, int32_t C,
+                     void* stream);
+int ccedit_png_emit(const uint32_t* tokens, const int32_t* ntok, const uint32_t* codes, const uint32_t* header, const int32_t* header_bits,
+                    void* slots, int64_t chunks, void* stream);
+int ccedit_png_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t* frame_bytes, int32_t N, int32_t C, void* stream);
+int ccedit_png_pack(const void* slots, const int32_t* chunk_bits, const int64_t* chunk_off, void* out, int32_t N, int32_t C, int64_t out_bytes,
+                    void* stream);
+int ccedit_png_adler(const void* filtered, uint32_t* partials, uint32_t* adler, int32_t N, int64_t L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

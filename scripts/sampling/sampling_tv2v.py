@@ -29,11 +29,13 @@ one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everyt
 --noise_seed, --gpu_io — runs on the long latent as on a short one, first-stage encode / decode in groups of at most T frames.
 Launched under torch.distributed (RANK / WORLD_SIZE), the chunks are dealt round-robin to the ranks (BASELINE.json config 5:
 independent clips, one per GPU, no collective — ccedit_amd.parallel.shard_clips).
-`--propagate` (job mode, --save_type gif or mjpeg) adds the frames BETWEEN the keyframes: every source frame from the first to the last keyframe
+`--propagate` (job mode, --save_type gif, mjpeg or png) adds the frames BETWEEN the keyframes: every source frame from the first to the last keyframe
 gets an edited frame, the two neighbouring edited keyframes carried along motion estimated on the source (ccedit_amd/propagate.py,
-csrc/propagate.hip), written to <save_path>/<basemodel>/result_full/gif/ (or mjpeg/) at --original_fps; log_info.json gains `fullrate_paths`.
+csrc/propagate.hip), written to <save_path>/<basemodel>/result_full/gif/ (or mjpeg/, png/) at --original_fps; log_info.json gains `fullrate_paths`.
 `--save_type mjpeg` writes true-colour video: Motion-JPEG in an .avi, every frame encoded on the GPU (ccedit_amd/mjpeg.py, csrc/mjpeg.hip) at
 --video_quality; such an .avi is also a video SOURCE wherever a .gif is.
+`--save_type png` writes lossless true-colour video: one animated PNG per clip, filtered and deflate-coded on the GPU (ccedit_amd/png.py,
+csrc/png.hip); any H and W; an animated .png is also a video SOURCE wherever a .gif is.
 `--gif_encoder device` (with --save_type gif) quantises and LZW-codes every .gif a job writes on the GPU (ccedit_amd/gif.py, csrc/gif.hip);
 the default, `pillow`, writes them on the host as before.
 """
@@ -78,10 +80,12 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--batch_size", type=int, default=4)
     p.add_argument("--original_fps", type=int, default=20)
     p.add_argument("--target_fps", type=int, default=3)
-    p.add_argument("--save_type", type=str, default="npy", choices=["npy", "gif", "mp4", "mjpeg"],
+    p.add_argument("--save_type", type=str, default="npy", choices=["npy", "gif", "mp4", "mjpeg", "png"],
                    help="reference: gif | mp4 (default mp4).  mp4 needs a codec library (none offline: raises, as decoding does); npy = raw frames; "
                         "mjpeg (not in the reference script) = true-colour Motion-JPEG in an .avi, baseline JPEG frames encoded on the GPU "
-                        "(ccedit_amd/mjpeg.py, csrc/mjpeg.hip) at --video_quality; H and W must be multiples of 16")
+                        "(ccedit_amd/mjpeg.py, csrc/mjpeg.hip) at --video_quality; H and W must be multiples of 16; png (not in the reference script) = "
+                        "lossless true-colour animated PNG, one file per clip, rows filtered and deflate-coded on the GPU (ccedit_amd/png.py, "
+                        "csrc/png.hip), any H and W")
     p.add_argument("--video_quality", type=int, default=90,
                    help="(not in the reference script) JPEG quality of --save_type mjpeg, 1 ... 100: the Annex K tables scaled by the usual rule")
     p.add_argument("--save_path", type=str, default="outputs/demo/tv2v")
@@ -123,7 +127,7 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="(not in the reference script) full-frame-rate output: after a clip's keyframes are saved, every source frame from the "
                         "first to the last keyframe gets an edited frame — the two neighbouring edited keyframes carried along the source's "
                         "motion (ccedit_amd/propagate.py, csrc/propagate.hip) — written to <save_path>/result_full/ at --original_fps.  "
-                        "Needs a video source (job mode) and --save_type gif or --save_type mjpeg")
+                        "Needs a video source (job mode) and --save_type gif, --save_type mjpeg or --save_type png")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(not in the reference script) draw the samplers' per-step noise from a CPU generator with this seed instead of "
@@ -131,7 +135,7 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--disable_check_repeat", action="store_true")
     p.add_argument("--gpu_io", action="store_true",
                    help="pixel I/O on the GPU (ccedit_amd/csrc/pixel.hip): frame / depth resize, depth hint normalisation and the uint8 "
-                        "frames of --save_type gif; decoding and file writing stay on the host.  Default off: everything as before")
+                        "frames of --save_type gif / mjpeg / png; decoding and file writing stay on the host.  Default off: everything as before")
     p.add_argument("--gif_encoder", type=str, default="pillow", choices=["pillow", "device"],
                    help="(not in the reference script) who encodes the files of --save_type gif, result_full/gif/ of --propagate included.  "
                         "pillow (default): Pillow on the host, byte for byte as before.  device: colour quantisation (Wu's quantiser, a local "
@@ -159,8 +163,9 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         if not job_mode(args):
             p.error("--propagate carries the edit to the frames between the keyframes of a video: give --prompt with --video_path "
                     "(or --prompt_listpath / --videos_directory / --json_path)")
-        if args.save_type not in ("gif", "mjpeg"):
-            p.error(f"--propagate writes result_full/ as gif or as Motion-JPEG: add --save_type gif or --save_type mjpeg (got {args.save_type})")
+        if args.save_type not in ("gif", "mjpeg", "png"):
+            p.error(f"--propagate writes result_full/ as gif, as Motion-JPEG or as animated PNG: add --save_type gif, --save_type mjpeg or "
+                    f"--save_type png (got {args.save_type})")
     if getattr(args, "gif_encoder", "pillow") == "device" and args.save_type != "gif":
         p.error(f"--gif_encoder device encodes the files of --save_type gif (got --save_type {args.save_type})")
     if not 1 <= getattr(args, "video_quality", 90) <= 100:
@@ -208,11 +213,11 @@ def check_propagate(args, video_paths) -> None:
 def propagate_chunk(args, cvideos, samples, dev, save_path):
     """--propagate for one chunk: per clip all source frames on the device, the edited keyframes as the uint8 frames result/ holds
     (frames_to_u8 without rounding of the decoder output), propagate_clip, <save_path>/result_full/gif/animation-XXXX.gif (--save_type
-    mjpeg: result_full/mjpeg/animation-XXXX.avi, encoded from the frames where they are, on the device; so is the gif with --gif_encoder
-    device) at --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
+    mjpeg: result_full/mjpeg/animation-XXXX.avi, --save_type png: result_full/png/animation-XXXX.png, encoded from the frames where they
+    are, on the device; so is the gif with --gif_encoder device) at --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
     from ccedit_amd import ops
     from ccedit_amd.propagate import propagate_clip
-    from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask, save_avi_u8, save_gif_u8
+    from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask, save_avi_u8, save_gif_u8, save_png_u8
     edited = ops.frames_to_u8(samples.float().contiguous(), rounding=False, unit_range=False)           # (bs, T, H, W, 3)
     paths = []
     for b, v in enumerate(cvideos):
@@ -226,6 +231,8 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
         full = propagate_clip(source, idx, edited[b], masks=masks)
         if args.save_type == "mjpeg":
             paths.append(save_avi_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps, args.video_quality))
+        elif args.save_type == "png":
+            paths.append(save_png_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps))
         elif getattr(args, "gif_encoder", "pillow") == "device":        # encoded from the frames where they are, on the device
             paths.append(save_gif_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps, gif_encoder="device"))
         else:
@@ -319,15 +326,15 @@ def text_inputs(cond, dev, args=None):
 
 
 def save_result(args, tag, x):
-    """sampling_tv2v.py:473-515: clamp to [0,1]; .npy frames (default) or an animated gif / a Motion-JPEG .avi + frame grid."""
+    """sampling_tv2v.py:473-515: clamp to [0,1]; .npy frames (default) or an animated gif / a Motion-JPEG .avi / an animated PNG + frame grid."""
     from scripts.sampling.util import perform_save_locally_video, save_frames
     quality = dict(video_quality=args.video_quality) if args.save_type == "mjpeg" else {}
     if getattr(args, "gif_encoder", "pillow") == "device":
         quality["gif_encoder"] = "device"
-    if args.save_type in ("gif", "mjpeg") and getattr(args, "gpu_io", False):
+    if args.save_type in ("gif", "mjpeg", "png") and getattr(args, "gpu_io", False):
         perform_save_locally_video(os.path.join(args.save_path, "result"), x, fps=args.target_fps, savetype=args.save_type, gpu_io=True, signed=True,
                                    **quality)
-    elif args.save_type in ("gif", "mjpeg"):
+    elif args.save_type in ("gif", "mjpeg", "png"):
         perform_save_locally_video(os.path.join(args.save_path, "result"), torch.clamp((x + 1.0) / 2.0, 0.0, 1.0),
                                    fps=args.target_fps, savetype=args.save_type, **quality)
     save_frames(args.save_path, tag, x)
@@ -696,7 +703,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
             print(f"chunk {idx}: {bs} clip(s) of {T} frames {H}x{W} in {time.time() - t0:.2f}s")
             to01 = lambda v: (torch.clamp(v.float(), -1.0, 1.0) + 1.0) / 2.0
             save_path = video_save_paths[idx] if video_save_paths else os.path.join(args.save_path, base_tag)
-            if args.gpu_io and args.save_type in ("gif", "mjpeg"):       # uint8 frames made on the device: clamp((x + 1) / 2) is in the kernel
+            if args.gpu_io and args.save_type in ("gif", "mjpeg", "png"):       # uint8 frames made on the device: clamp((x + 1) / 2) is in the kernel
                 to01, io = (lambda v: v), dict(gpu_io=True, signed=True)
             else:                                                         # (.npy keeps fp32 frames: the host route)
                 io = {}

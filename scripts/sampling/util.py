@@ -408,19 +408,32 @@ def HWC3(x: np.ndarray) -> np.ndarray:
 
 
 def _decode_gif_u8(video_path: str) -> np.ndarray:
-    """All frames of a .gif -> uint8 (N, h, w, 3) on the host (transparency blended on white, as HWC3)."""
+    """All frames of a .gif or an animated .png -> uint8 (N, h, w, 3) on the host (transparency blended on white, as HWC3)."""
     from PIL import Image, ImageSequence
     return np.stack([HWC3(np.array(fr.convert("RGBA") if fr.mode == "P" and "transparency" in fr.info else fr.convert("RGB")))
                      for fr in ImageSequence.Iterator(Image.open(video_path))], axis=0)
 
 
+def _is_apng(path: str) -> bool:
+    """An animated PNG: a .png file with more than one frame (what --save_type png writes for a clip).  A still .png is not a video:
+    it stays what it was at every place that asks (an unsupported video format; ONE mask image)."""
+    if not path.lower().endswith(".png") or not os.path.isfile(path):
+        return False
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            return int(getattr(im, "n_frames", 1)) > 1
+    except Exception:
+        return False
+
+
 def _is_frame_file(video_path: str) -> bool:
-    """A video held in ONE file whose frames Pillow decodes: an animated .gif or a Motion-JPEG .avi."""
-    return video_path.endswith((".gif", ".avi"))
+    """A video held in ONE file whose frames Pillow decodes: an animated .gif, a Motion-JPEG .avi or an animated .png."""
+    return video_path.endswith((".gif", ".avi")) or _is_apng(video_path)
 
 
 def _decode_video_u8(video_path: str) -> np.ndarray:
-    """All frames of a .gif or an MJPG .avi -> uint8 (N, h, w, 3) on the host; from here on both are treated alike.  An .avi that is
+    """All frames of a .gif, an animated .png or an MJPG .avi -> uint8 (N, h, w, 3) on the host; from here on all are treated alike.  An .avi that is
     missing, truncated or holds another codec is a ValueError that says so (ccedit_amd.mjpeg.read_avi)."""
     if video_path.endswith(".avi"):
         from ccedit_amd.mjpeg import decode_avi_u8
@@ -506,6 +519,21 @@ def save_avi_u8(save_path: str, frames, fps: int, quality: int = 90) -> str:
     return mjpeg.write_avi(savepath, mjpeg.encode_frames(frames, quality), fps, frames.shape[1], frames.shape[2])
 
 
+def save_png_u8(save_path: str, frames, fps: int) -> str:
+    """uint8 frames (T, H, W, 3), on the device or on the host (then uploaded) -> <save_path>/png/animation-XXXX.png, numbered like
+    save_gif_u8's files: an animated PNG (one frame: a plain PNG) holding exactly these bytes, rows filtered and deflate-coded on the device
+    (ccedit_amd/png.py, csrc/png.hip); only the compressed streams come back, the container is written on the host."""
+    from ccedit_amd import png
+    if not torch.is_tensor(frames):
+        frames = torch.from_numpy(np.ascontiguousarray(frames))
+    if not frames.is_cuda:
+        frames = frames.to(torch.device("cuda", torch.cuda.current_device()))
+    os.makedirs(os.path.join(save_path, "png"), exist_ok=True)
+    count = len(os.listdir(os.path.join(save_path, "png")))
+    savepath = os.path.join(save_path, "png", f"animation-{count:04}.png")
+    return png.write_apng(savepath, png.encode_frames(frames.contiguous()), png.duration_ms(fps), frames.shape[2], frames.shape[1])
+
+
 def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None,
                          device=None) -> torch.Tensor:
     """util.py:689-762: directory of frame images, a .gif or a Motion-JPEG .avi -> keyframes (T, 3, H, W) in [-1, 1].
@@ -555,7 +583,7 @@ def count_video_frames(video_path: str) -> int:
     """Number of frames of what load_video_keyframes reads: files of a directory, frames of a .gif or of a Motion-JPEG .avi."""
     if os.path.isdir(video_path):
         return len(os.listdir(video_path))
-    if video_path.endswith(".gif"):
+    if video_path.endswith(".gif") or _is_apng(video_path):
         from PIL import Image
         return int(getattr(Image.open(video_path), "n_frames", 1))
     if video_path.endswith(".avi"):
@@ -590,7 +618,7 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
     if os.path.isdir(mask_path):
         files = sorted(os.listdir(mask_path))
         n, pick = len(files), lambda i: lum(Image.open(os.path.join(mask_path, files[i])))
-    elif mask_path.endswith(".gif"):
+    elif mask_path.endswith(".gif") or _is_apng(mask_path):
         frames = [lum(fr) for fr in ImageSequence.Iterator(Image.open(mask_path))]
         n, pick = len(frames), lambda i: frames[i]
     elif mask_path.endswith(".avi"):
@@ -636,7 +664,9 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
     savetype='mjpeg' (not in the reference): <save_path>/mjpeg/animation-XXXX.avi, Motion-JPEG at `video_quality` (1 ... 100), numbered and
     returned like the gifs; the uint8 frames are the gif branch's — made on the host and uploaded, or on the device with gpu_io: the same
     bytes either way — and every frame is encoded on the device (ccedit_amd/mjpeg.py, csrc/mjpeg.hip).
-    gpu_io (savetype='gif' or 'mjpeg', device tensor): the uint8 frames are made on the device (ccedit_frames_to_u8) and 3 bytes per pixel
+    savetype='png' (not in the reference): <save_path>/png/animation-XXXX.png, a lossless animated PNG of the same uint8 frames, numbered and
+    returned like the gifs, coded on the device (ccedit_amd/png.py, csrc/png.hip); any H and W; `video_quality` is ignored.
+    gpu_io (savetype='gif', 'mjpeg' or 'png', device tensor): the uint8 frames are made on the device (ccedit_frames_to_u8) and 3 bytes per pixel
     instead of 12 come to the host; the files are byte-identical.  `signed` (with gpu_io only): samples are the decoder's output in
     [-1, 1] and clamp((x + 1) / 2, 0, 1) is part of the same kernel.
     gif_encoder='device' (savetype='gif' only, not in the reference): the gif is quantised and LZW-coded on the device (ccedit_amd/gif.py,
@@ -644,7 +674,7 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
     are uploaded once: the same bytes either way.  File names, numbering, returned paths and the grid PNG are those of 'pillow'."""
     from PIL import Image
     assert samples.dim() == 5, "Expected samples to have shape (B, C, T, H, W)"
-    assert savetype in ["gif", "mp4", "npy", "mjpeg"]
+    assert savetype in ["gif", "mp4", "npy", "mjpeg", "png"]
     if gif_encoder not in GIF_ENCODERS:
         raise ValueError(f"gif_encoder {gif_encoder!r}: one of {GIF_ENCODERS}")
     if gif_encoder == "device" and savetype != "gif":
@@ -655,11 +685,11 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
     u8 = u8_grid = None
     if gpu_io:
         from ccedit_amd import ops
-        if savetype not in ("gif", "mjpeg") or not samples.is_cuda:
+        if savetype not in ("gif", "mjpeg", "png") or not samples.is_cuda:
             raise ValueError("gpu_io saves uint8 frames (savetype='gif') of a device tensor")
         x = samples.detach().float().contiguous()
         u8 = ops.frames_to_u8(x, rounding=False, unit_range=not signed)                                # (B, T, H, W, 3)
-        u8 = u8 if savetype == "mjpeg" or gif_encoder == "device" else u8.cpu().numpy()               # (mjpeg, device gif: the frames stay on the device)
+        u8 = u8 if savetype in ("mjpeg", "png") or gif_encoder == "device" else u8.cpu().numpy()      # (mjpeg, png, device gif: the frames stay on the device)
         u8_grid = ops.frames_to_u8(x, rounding=True, unit_range=not signed).cpu().numpy() if save_grid else None
     if savetype == "npy":          # (not in the reference) the frames themselves: <save_path>/npy/frames-XXXX.npy, (T, H, W, C) float32 in [0, 1]
         os.makedirs(os.path.join(save_path, "npy"), exist_ok=True)
@@ -687,6 +717,11 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
             count_grid += 1
         if savetype == "mjpeg":
             savepath = save_avi_u8(save_path, (255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b], fps, video_quality)
+            count += 1
+            savepaths.append(savepath)
+            continue
+        if savetype == "png":
+            savepath = save_png_u8(save_path, (255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b], fps)
             count += 1
             savepaths.append(savepath)
             continue
