@@ -217,3 +217,8 @@ int cc_png_pack_scan(const int32_t* chunk_bits, int64_t* chunk_off, int32_t* fra
 int cc_png_pack(const uint8_t* slots, const int32_t* chunk_bits, const int64_t* chunk_off, uint8_t* out, int32_t N, int32_t C, int64_t out_bytes,
                 hipStream_t s);
 int cc_png_adler(const uint8_t* filtered, uint32_t* partials, uint32_t* adler, int32_t N, int64_t L, hipStream_t s);
+
+// PNG decoding launchers (pngdec.hip); entry points and argument checks in core.cpp
+int cc_pngdec_inflate(const uint8_t* data, int64_t data_bytes, const int64_t* streams, uint8_t* filtered, int32_t* status, int32_t N, int32_t H,
+                      int32_t W, hipStream_t s);
+int cc_pngdec_unfilter(const uint8_t* filtered, uint8_t* rgb, int32_t* status, int32_t N, int32_t H, int32_t W, hipStream_t s);

@@ -536,3 +536,22 @@ extern "C" int ccedit_png_adler(const void* filtered, uint32_t* partials, uint32
     CC_CHECK_ARG((((uintptr_t)partials | (uintptr_t)adler) & 3) == 0, "ccedit_png_adler: partials and adler must be 4-byte aligned");
     return cc_png_adler((const uint8_t*)filtered, partials, adler, N, L, (hipStream_t)stream);
 }
+
+// ---- PNG decoding (kernels and launchers: pngdec.hip).  Geometry and buffers are checked here, before any HIP call; the stream table
+// is device data and is clamped into [0, data_bytes] by the kernel, the streams' content is checked by the decoder itself.
+extern "C" int ccedit_pngdec_inflate(const void* data, int64_t data_bytes, const int64_t* streams, void* filtered, int32_t* status, int32_t N,
+                                     int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(data && streams && filtered && status, "ccedit_pngdec_inflate: null pointer (data, streams, filtered and status are required)");
+    if (int rc = gif_shape_ok("ccedit_pngdec_inflate", N, H, W)) return rc;
+    CC_CHECK_ARG(data_bytes >= 1 && data_bytes < kPixelMax * 4, "ccedit_pngdec_inflate: data_bytes=%lld (1 ... 2^33)", (long long)data_bytes);
+    CC_CHECK_ARG(((uintptr_t)streams & 7) == 0 && ((uintptr_t)status & 3) == 0,
+                 "ccedit_pngdec_inflate: streams must be 8-byte aligned, status 4-byte");
+    return cc_pngdec_inflate((const uint8_t*)data, data_bytes, streams, (uint8_t*)filtered, status, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_pngdec_unfilter(const void* filtered, void* rgb, int32_t* status, int32_t N, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(filtered && rgb && status, "ccedit_pngdec_unfilter: null pointer (filtered, rgb and status are required)");
+    if (int rc = gif_shape_ok("ccedit_pngdec_unfilter", N, H, W)) return rc;
+    CC_CHECK_ARG(((uintptr_t)status & 3) == 0, "ccedit_pngdec_unfilter: status must be 4-byte aligned");
+    return cc_pngdec_unfilter((const uint8_t*)filtered, (uint8_t*)rgb, status, N, H, W, (hipStream_t)stream);
+}

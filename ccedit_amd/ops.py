@@ -1427,3 +1427,40 @@ def png_adler(filtered: torch.Tensor) -> torch.Tensor:
     adler = torch.empty((n,), dtype=torch.int32, device=filtered.device)
     hip.check(hip.lib().ccedit_png_adler(filtered.data_ptr(), partials.data_ptr(), adler.data_ptr(), n, length, _stream()), "ccedit_png_adler")
     return adler.to(torch.int64) & 0xffffffff
+
+
+# ------------------------------------------------------------------------------------------
+# PNG decoding (csrc/pngdec.hip; the chunk parser and the frame loop: ccedit_amd/pngdec.py)
+# ------------------------------------------------------------------------------------------
+def pngdec_inflate(data: torch.Tensor, streams: torch.Tensor, h: int, w: int):
+    """zlib streams (uint8 (B,): their bytes; int64 (N, 2): offset and length of each in them) of images of h x w -> (filtered uint8
+    (N, h * (1 + 3 w)), status int32 (N, 2): code (0: decoded) and input byte position)."""
+    from . import png
+    _chk_u8(data, "pngdec_inflate: data", 1)
+    png.check_size(h, w)
+    if (streams.dtype != torch.int64 or not streams.is_cuda or not streams.is_contiguous() or streams.dim() != 2 or streams.shape[1] != 2
+            or streams.shape[0] < 1 or data.numel() < 1):
+        raise ValueError(f"pngdec_inflate: streams: expected a contiguous cuda int64 tensor (N, 2), N >= 1, and at least one byte of data, "
+                         f"got {streams.dtype} {tuple(streams.shape)}, {data.numel()} bytes")
+    n = streams.shape[0]
+    filtered = torch.empty((n, png.filtered_bytes(h, w)), dtype=torch.uint8, device=data.device)
+    status = torch.empty((n, 2), dtype=torch.int32, device=data.device)
+    hip.check(hip.lib().ccedit_pngdec_inflate(data.data_ptr(), data.numel(), streams.data_ptr(), filtered.data_ptr(), status.data_ptr(), n, int(h),
+                                              int(w), _stream()), "ccedit_pngdec_inflate")
+    return filtered, status
+
+
+def pngdec_unfilter(filtered: torch.Tensor, h: int, w: int):
+    """filtered uint8 (N, h * (1 + 3 w)) -> (uint8 frames (N, h, w, 3), status int32 (N, 2): code (0, or 12: a filter byte above 4) and
+    that byte's offset)."""
+    from . import png
+    _chk_u8(filtered, "pngdec_unfilter: filtered", 2)
+    png.check_size(h, w)
+    if filtered.shape[0] < 1 or filtered.shape[1] != png.filtered_bytes(h, w):
+        raise ValueError(f"pngdec_unfilter: filtered {tuple(filtered.shape)}, an image of {h}x{w} has {png.filtered_bytes(h, w)} filtered bytes")
+    n = filtered.shape[0]
+    out = torch.empty((n, int(h), int(w), 3), dtype=torch.uint8, device=filtered.device)
+    status = torch.empty((n, 2), dtype=torch.int32, device=filtered.device)
+    hip.check(hip.lib().ccedit_pngdec_unfilter(filtered.data_ptr(), out.data_ptr(), status.data_ptr(), n, int(h), int(w), _stream()),
+              "ccedit_pngdec_unfilter")
+    return out, status

@@ -688,6 +688,31 @@ int ccedit_png_pack(const void* slots, const int32_t* chunk_bits, const int64_t*
                     void* stream);
 int ccedit_png_adler(const void* filtered, uint32_t* partials, uint32_t* adler, int32_t N, int64_t L, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PNG decoding (added without an ABI bump: two new functions, CCEDIT_ABI_VERSION stays 12).  PNG sources (frame files, the frames of an
+ * animated .png) -> uint8 frames [N][H][W][3] on the device; only the compressed bytes go up.  ccedit_amd/pngdec.py: the chunk parser
+ * (signature, CRCs, IHDR, IDAT / fdAT) and the frame loop.  Kernels: csrc/pngdec.hip, csrc/pngdec_core.h.  The subset: bit depth 8,
+ * colour type 2, no interlace; H and W 1 ... 65535 with H * W <= 2^24; N <= 65535.  L = H * (1 + 3 W).
+ *
+ * Both calls write one int32 pair per image to `status`: a code (0: decoded; the codes are pngdec_core.h's Status) and the byte
+ * position that goes with it.  An image with a non-zero code is not complete; nothing outside the buffers below is read or written.
+ *
+ * ccedit_pngdec_inflate: N zlib streams -> N filtered images of exactly L bytes each.  data: uint8 [data_bytes], every stream's bytes;
+ *   streams: int64 [N][2] on the device, (offset, length) of each stream in data (clamped into it); filtered: uint8 [N][L].  The full
+ *   format: zlib header (CM 8, window <= 32 KiB, no FDICT, FCHECK), stored, fixed and dynamic blocks in any sequence, distances up to
+ *   32768, lengths up to 258, overlapping copies, the trailing Adler-32 (verified).  Codes: 1 bad zlib header, 2 the stream runs past
+ *   its input, 3 block type 3, 4 a stored block's LEN / NLEN disagree, 5 an over-subscribed or incomplete code (or too many symbols, or
+ *   no end-of-block code), 6 bad code-length runs, 7 bits that are no code / symbol 286, 287 / distance code 30, 31, 8 a distance that
+ *   reaches before the start, 9 the output would pass L, 10 the output ends short of L, 11 Adler-32 mismatch.  Position: the stream's
+ *   input bytes touched when it stopped (code 2: its length; code 11: where the trailer begins; code 1: 0).  One wave per stream.
+ * ccedit_pngdec_unfilter: filtered [N][L] -> rgb uint8 [N][H][W][3]: per row the filter byte (0 None, 1 Sub, 2 Up, 3 Average with
+ *   floor, 4 Paeth with the specification's tie order; bpp 3; the row above row 0 is zeros) undone.  Code 12: a filter byte above 4,
+ *   position: that byte's offset in the image's L bytes; the image's rows from the 64-row band that holds it on are not written.
+ */
+int ccedit_pngdec_inflate(const void* data, int64_t data_bytes, const int64_t* streams, void* filtered, int32_t* status, int32_t N, int32_t H,
+                          int32_t W, void* stream);
+int ccedit_pngdec_unfilter(const void* filtered, void* rgb, int32_t* status, int32_t N, int32_t H, int32_t W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

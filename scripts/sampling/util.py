@@ -275,7 +275,8 @@ def load_vae_file(model, vae_path: str) -> None:
 # frame / video I/O: reference scripts/sampling/util.py:288-382, 689-762
 # Image files, GIFs and the JPEG frames of a Motion-JPEG .avi (ccedit_amd/mjpeg.py: read_avi walks the container) go through Pillow on
 # the host route.  With a device, .jpg / .jpeg files and .avi frames are decoded THERE (ccedit_amd/jpegdec.py: the same bytes as Pillow's);
-# a file outside the subset the device decodes goes through Pillow as before, with one line on stderr per clip.
+# a file outside the subset the device decodes goes through Pillow as before, with one line on stderr per clip.  The same holds for
+# .png files and the frames of an animated .png (ccedit_amd/pngdec.py: 8-bit RGB, not interlaced).
 # mp4 needs a codec library (decord / cv2 / imageio-ffmpeg) that is not installed here and raises.
 # ------------------------------------------------------------------------------------------
 _JPEG_EXT = (".jpg", ".jpeg")
@@ -324,6 +325,65 @@ def _avi_u8_device(video_path: str, device, select=None):
         return None
 
 
+def _png_files_u8_device(paths, device, what: str):
+    """The image files `paths` -> list of uint8 (1, h, w, 3) tensors on `device` (one (n, h, w, 3) tensor when they share a size), or None
+    when they go through Pillow as before: not all of them are .png, or the parser does not take one (one line on stderr names it).
+    Each file is parsed once; only the compressed bytes go up (ccedit_amd/pngdec.py: the same bytes as Pillow's).  A stream the device
+    stops in, which Pillow reports as an OSError, is a ValueError here, naming file, frame, code and byte position."""
+    import sys
+    from ccedit_amd import pngdec
+    if not paths or not all(p.lower().endswith(".png") for p in paths):
+        return None
+    datas, infos = [], []
+    for p in paths:
+        with open(p, "rb") as f:
+            datas.append(f.read())
+        try:
+            infos.append(pngdec.parse(datas[-1]))
+        except ValueError as e:                                  # (PngUnsupported is one)
+            sys.stderr.write(f"[pngdec] {what}: {os.path.basename(p)}: {e}; this clip is decoded by Pillow on the host\n")
+            return None
+    same, k = len({(i.height, i.width) for i in infos}) == 1, 0
+    try:
+        if same:
+            return [pngdec.decode(datas, device, infos=infos)]
+        out = []
+        for k in range(len(datas)):
+            out.append(pngdec.decode([datas[k]], device, infos=[infos[k]]))
+        return out
+    except ValueError as e:
+        m = re.match(r"frame (\d+): (.*)", str(e))                 # (the decoder's "frame i" counts inside its call)
+        if m:
+            k = int(m.group(1)) if same else k
+            raise ValueError(f"{what}: {os.path.basename(paths[k])}: frame {k}: {m.group(2)}") from e
+        raise ValueError(f"{what}: {e}") from e
+
+
+def _image_files_u8_device(paths, device, what: str):
+    """Frame files decoded on the device where a decoder takes the whole clip: JPEG (.jpg / .jpeg) or PNG; None: Pillow, as before."""
+    on_device = _jpeg_files_u8_device(paths, device, what)
+    return on_device if on_device is not None else _png_files_u8_device(paths, device, what)
+
+
+def _apng_u8_device(video_path: str, device, select=None):
+    """The frames of an animated .png (all, or those at the indices select(number of frames)) -> uint8 (N, h, w, 3) on `device`, decoded
+    there; only they are decoded, but the whole file is parsed, so that a clip goes ONE way as a whole: None when the parser does not
+    take the file (one line on stderr names why), and the clip then goes through Pillow as before."""
+    import sys
+    from ccedit_amd import pngdec
+    with open(video_path, "rb") as f:
+        data = f.read()
+    try:
+        info = pngdec.parse(data)
+    except ValueError as e:
+        sys.stderr.write(f"[pngdec] {video_path}: {e}; this clip is decoded by Pillow on the host\n")
+        return None
+    try:
+        return pngdec.decode_apng(data, device, select, info=info)
+    except ValueError as e:
+        raise ValueError(f"{video_path}: {e}") from e
+
+
 def _u8_to_float_device(groups, size) -> torch.Tensor:
     """uint8 (n, h, w, 3) tensors on the device -> fp32 (T, 3, H, W) in [-1, 1]: what _frames_to_device does after its upload."""
     from ccedit_amd import ops
@@ -363,7 +423,7 @@ def load_img(p_cond_img: str, size: tuple = None, device=None) -> torch.Tensor:
     if device is not None:
         if size:
             assert len(size) == 2, "size should be (H, W)"
-        on_device = _jpeg_files_u8_device([p_cond_img], device, p_cond_img)
+        on_device = _image_files_u8_device([p_cond_img], device, p_cond_img)
         if on_device is not None:
             return _u8_to_float_device(on_device, size)
         return _frames_to_device([_decode_rgb_u8(p_cond_img)], size, device)
@@ -452,7 +512,7 @@ def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
     assert device is not None and size and len(size) == 2, "load_video_frames_u8 works on a device, size should be (H, W)"
     if os.path.isdir(video_path):
         files = sorted(os.listdir(video_path))
-        on_device = _jpeg_files_u8_device([os.path.join(video_path, f) for f in files], device, video_path)
+        on_device = _image_files_u8_device([os.path.join(video_path, f) for f in files], device, video_path)
         if on_device is not None:
             out = [ops.resize_u8_pil(g.contiguous(), size) for g in on_device]
             return out[0] if len(out) == 1 else torch.cat(out, dim=0)
@@ -461,7 +521,8 @@ def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
         out = [ops.resize_u8_pil(torch.from_numpy(np.ascontiguousarray(g)).to(device), size) for g in groups]
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
     if _is_frame_file(video_path):
-        on_device = _avi_u8_device(video_path, device) if video_path.endswith(".avi") else None
+        on_device = _avi_u8_device(video_path, device) if video_path.endswith(".avi") else (
+            _apng_u8_device(video_path, device) if video_path.lower().endswith(".png") else None)
         if on_device is not None:
             x = _u8_to_float_device([on_device], None).contiguous()
         else:
@@ -548,15 +609,16 @@ def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, nu
         files = sorted(os.listdir(video_path))
         idx = keyframe_indices(len(files), original_fps, target_fps, num_keyframes)
         if device is not None:
-            on_device = _jpeg_files_u8_device([os.path.join(video_path, files[i]) for i in idx], device, video_path)
+            on_device = _image_files_u8_device([os.path.join(video_path, files[i]) for i in idx], device, video_path)
             if on_device is not None:
                 return _u8_to_float_device(on_device, size)
             return _frames_to_device([_decode_rgb_u8(os.path.join(video_path, files[i])) for i in idx], size, device)
         return torch.cat([load_img(os.path.join(video_path, files[i]), size) for i in idx], dim=0)
     if _is_frame_file(video_path):
-        if device is not None and video_path.endswith(".avi"):
+        if device is not None and (video_path.endswith(".avi") or video_path.lower().endswith(".png")):
             from ccedit_amd import ops
-            on_device = _avi_u8_device(video_path, device, lambda n: keyframe_indices(n, original_fps, target_fps, num_keyframes))
+            select = lambda n: keyframe_indices(n, original_fps, target_fps, num_keyframes)      # noqa: E731
+            on_device = _avi_u8_device(video_path, device, select) if video_path.endswith(".avi") else _apng_u8_device(video_path, device, select)
             if on_device is not None:
                 x = _u8_to_float_device([on_device], None).contiguous()
                 return ops.resize_bicubic(x, size) if size else x
