@@ -22,6 +22,8 @@ from __future__ import annotations
 import struct
 from typing import List, Sequence, Tuple
 
+from .codec_common import check_frames, duration_ms, launch_groups, per_launch, split_bytes      # noqa: F401  (duration_ms: gif.duration_ms, as the Pillow route hands it over)
+
 # ---- the constants of the format: this is their one place
 GRID = 32                   # cells per colour axis: cell = value >> SHIFT
 SHIFT = 3
@@ -49,11 +51,6 @@ def chunks_of(h: int, w: int, chunk: int = CHUNK) -> int:
     return -(-(int(h) * int(w)) // int(chunk))
 
 
-def duration_ms(fps) -> int:
-    """The frame duration as the Pillow route hands it over: int(round(1000 / fps)); the file holds duration // 10 centiseconds."""
-    return int(round(1000.0 / fps))
-
-
 # ------------------------------------------------------------------------------------------
 # the encoder: the stages on the device (ops.gif_*), only palettes and LZW bytes come to the host
 # ------------------------------------------------------------------------------------------
@@ -61,19 +58,9 @@ MAX_FRAMES_PER_LAUNCH = 64
 SCRATCH_BYTES = 256 << 20         # frames per launch are chosen so that moment tables, indices and chunk slots stay below this; results do not depend on it
 
 
-def _check_frames(frames, what: str):
-    import torch
-    if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda \
-            or frames.shape[0] < 1:
-        raise ValueError(f"{what}: uint8 frames (N, H, W, 3) on the device, N >= 1, got "
-                         f"{getattr(frames, 'dtype', type(frames))} {tuple(getattr(frames, 'shape', ()))} {getattr(frames, 'device', '')}")
-    check_size(frames.shape[1], frames.shape[2])
-    return frames.contiguous()
-
-
 def frames_per_launch(h: int, w: int) -> int:
     per_frame = MOMENT_WORDS * 8 + GRID ** 3 + COLORS * 3 + h * w + chunks_of(h, w) * (SLOT_BYTES + 16) + (h * w * 3 + 1) // 2
-    return max(1, min(int(MAX_FRAMES_PER_LAUNCH), int(SCRATCH_BYTES) // per_frame))
+    return per_launch(MAX_FRAMES_PER_LAUNCH, SCRATCH_BYTES, per_frame)
 
 
 def _quantize_launch(frames):
@@ -85,9 +72,8 @@ def _quantize_launch(frames):
 def quantize(frames):
     """uint8 frames (N, H, W, 3) on the device -> (palettes uint8 (N, 256, 3), indices uint8 (N, H, W)), both on the device."""
     import torch
-    frames = _check_frames(frames, "quantize")
-    per = frames_per_launch(frames.shape[1], frames.shape[2])
-    parts = [_quantize_launch(frames[s:s + per]) for s in range(0, frames.shape[0], per)]
+    frames = check_frames(frames, "quantize", check_size)
+    parts = [_quantize_launch(frames[g]) for g in launch_groups(frames.shape[0], frames_per_launch(frames.shape[1], frames.shape[2]))]
     return torch.cat([p for p, _ in parts], dim=0), torch.cat([i for _, i in parts], dim=0)
 
 
@@ -98,21 +84,15 @@ def encode_indices(indices, chunk: int = CHUNK) -> List[bytes]:
     slots, chunk_bits = ops.gif_lzw(indices, chunk)
     chunk_off, frame_bytes = ops.gif_pack_scan(chunk_bits, n, h, w, chunk)
     sizes = frame_bytes.cpu().tolist()                              # the byte counts: what lets the host take exactly the coded bytes
-    packed = ops.gif_pack(slots, chunk_bits, chunk_off, n, h, w, chunk, sum(sizes)).cpu().numpy().tobytes()
-    out, at = [], 0
-    for b in sizes:
-        out.append(packed[at:at + b])
-        at += b
-    return out
+    return split_bytes(ops.gif_pack(slots, chunk_bits, chunk_off, n, h, w, chunk, sum(sizes)).cpu().numpy().tobytes(), sizes)
 
 
 def encode_frames(frames) -> List[Tuple[bytes, bytes]]:
     """uint8 frames (N, H, W, 3) on the device -> per frame (palette: 768 bytes, the frame's LZW byte stream)."""
-    frames = _check_frames(frames, "encode_frames")
-    per = frames_per_launch(frames.shape[1], frames.shape[2])
+    frames = check_frames(frames, "encode_frames", check_size)
     out: List[Tuple[bytes, bytes]] = []
-    for s in range(0, frames.shape[0], per):
-        palettes, indices = _quantize_launch(frames[s:s + per])
+    for g in launch_groups(frames.shape[0], frames_per_launch(frames.shape[1], frames.shape[2])):
+        palettes, indices = _quantize_launch(frames[g])
         streams = encode_indices(indices)
         pal = palettes.cpu().numpy()
         out.extend((pal[i].tobytes(), streams[i]) for i in range(len(streams)))

@@ -21,6 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .codec_common import launch_groups, parsed, per_launch
 from .mjpeg import ZIGZAG
 
 MAX_DIM = 65520
@@ -324,9 +325,8 @@ def _groups(infos: Sequence[JpegInfo]):
     for i, info in enumerate(infos):
         by_key.setdefault(info.key(), []).append(i)
     for idx in by_key.values():
-        per = max(1, min(MAX_FRAMES_PER_LAUNCH, SCRATCH_BYTES // frame_scratch_bytes(infos[idx[0]])))
-        for s in range(0, len(idx), per):
-            yield idx[s:s + per]
+        for g in launch_groups(len(idx), per_launch(MAX_FRAMES_PER_LAUNCH, SCRATCH_BYTES, frame_scratch_bytes(infos[idx[0]]))):
+            yield idx[g]
 
 
 def _entropy(infos, jpegs, idx, device):
@@ -353,19 +353,10 @@ def _raise_status(status, idx) -> None:
         raise ValueError(f"frame {idx[f]}, restart interval {j}: {STATUS_TEXT.get(code, f'status {code}')}")
 
 
-def _parsed(jpegs: Sequence[bytes], infos: Optional[Sequence[JpegInfo]]) -> Sequence[JpegInfo]:
-    """The JpegInfo of every file: the caller's (a reader that had to parse anyway hands them on), or parsed here."""
-    if infos is None:
-        return [parse(j) for j in jpegs]
-    if len(infos) != len(jpegs):
-        raise ValueError(f"decode: {len(infos)} parsed headers for {len(jpegs)} files")
-    return infos
-
-
 def decode_coefficients(jpegs: Sequence[bytes], device, check: bool = True, infos: Optional[Sequence[JpegInfo]] = None):
     """The entropy stage alone -> per frame (coef int16 (blocks, 64) in MCU order, natural order inside a block; status int32 (I,)),
     both on the host.  check=False hands the status words back instead of raising."""
-    infos = _parsed(jpegs, infos)
+    infos = parsed(jpegs, infos, parse)
     out = [None] * len(jpegs)
     for idx in _groups(infos):
         coef, status, _ = _entropy(infos, jpegs, idx, device)
@@ -386,7 +377,7 @@ def decode(jpegs: Sequence[bytes], device, infos: Optional[Sequence[JpegInfo]] =
     from . import ops
     if len(jpegs) < 1:
         raise ValueError("decode: no frames")
-    infos = _parsed(jpegs, infos)
+    infos = parsed(jpegs, infos, parse)
     sizes = {(i.height, i.width) for i in infos}
     if len(sizes) != 1:
         raise ValueError(f"decode: frames of different sizes {sorted(sizes)}")

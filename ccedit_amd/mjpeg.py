@@ -19,6 +19,8 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
+from .codec_common import launch_groups, per_launch, split_bytes
+
 # ---- the constants of the format: this is their one place
 MCU = 16                    # 4:2:0: four Y blocks, one Cb, one Cr per 16 x 16 pixels
 BLOCKS_PER_MCU = 6
@@ -183,19 +185,14 @@ def encode_frames(frames, quality: int = DEFAULT_QUALITY) -> List[bytes]:
     frames = frames.contiguous()
     tables = device_tables(frames.device)
     header = torch.frombuffer(bytearray(frame_header(h, w, q)), dtype=torch.uint8).to(frames.device)
-    per = max(1, min(MAX_FRAMES_PER_LAUNCH, SCRATCH_BYTES // ((h // MCU) * segment_capacity(w))))
     out: List[bytes] = []
-    for s in range(0, n, per):
-        chunk = frames[s:s + per]
+    for g in launch_groups(n, per_launch(MAX_FRAMES_PER_LAUNCH, SCRATCH_BYTES, (h // MCU) * segment_capacity(w))):
+        chunk = frames[g]
         coef = ops.mjpeg_transform(chunk, tables, q)
         scratch, seg_len = ops.mjpeg_entropy(coef, tables)
         seg_off, frame_bytes = ops.mjpeg_pack_scan(seg_len, chunk.shape[0], h, w, header.numel())
         sizes = frame_bytes.cpu().tolist()                       # the byte counts: what lets the host take exactly the compressed bytes
-        packed = ops.mjpeg_pack(scratch, seg_len, seg_off, header, chunk.shape[0], h, w, sum(sizes)).cpu().numpy().tobytes()
-        at = 0
-        for b in sizes:
-            out.append(packed[at:at + b])
-            at += b
+        out.extend(split_bytes(ops.mjpeg_pack(scratch, seg_len, seg_off, header, chunk.shape[0], h, w, sum(sizes)).cpu().numpy().tobytes(), sizes))
     return out
 
 
@@ -322,13 +319,14 @@ def parse_avi(path: str):
     return jpegs, infos, h, w
 
 
-def decode_avi_device(path: str, device, select=None):
+def decode_avi_device(path: str, device, select=None, parsed=None):
     """All frames of an MJPG .avi -> uint8 (N, H, W, 3) on `device`, decoded there (ccedit_amd/jpegdec.py): only the compressed bytes go
     up.  The frames equal decode_avi_u8's byte for byte.  `select`: number of frames -> the indices to decode (every frame is still
-    parsed, so that a file goes one way as a whole).  jpegdec.JpegUnsupported: a frame outside the subset the device decodes.
+    parsed, so that a file goes one way as a whole).  `parsed`: parse_avi(path), when the caller has it already.
+    jpegdec.JpegUnsupported: a frame outside the subset the device decodes.
     Corrupt entropy-coded data, which Pillow decodes with a warning, is a ValueError naming file, frame and restart interval."""
     from . import jpegdec
-    jpegs, infos, _, _ = parse_avi(path)
+    jpegs, infos, _, _ = parse_avi(path) if parsed is None else parsed
     pick = range(len(jpegs)) if select is None else [int(i) for i in select(len(jpegs))]
     try:
         return jpegdec.decode([jpegs[i] for i in pick], device, infos=[infos[i] for i in pick])

@@ -30,6 +30,8 @@ import struct
 import zlib
 from typing import List, Sequence
 
+from .codec_common import check_frames, duration_ms, launch_groups, per_launch, split_bytes      # noqa: F401  (duration_ms: png.duration_ms, as the gif route hands it over)
+
 # ---- the constants of the format: this is their one place
 FILTERS = 5                     # None, Sub, Up, Average, Paeth
 CHUNK = 16384                   # filtered bytes per independently coded chunk (= deflate block)
@@ -88,11 +90,6 @@ def check_size(h: int, w: int) -> None:
         raise ValueError(f"frames of {h}x{w}: a frame's stream could exceed the 2^31 - 1 bytes a PNG chunk holds")
 
 
-def duration_ms(fps) -> int:
-    """The frame duration as the gif route hands it over: int(round(1000 / fps)); the file holds it as the fraction duration / 1000 s."""
-    return int(round(1000.0 / fps))
-
-
 # ------------------------------------------------------------------------------------------
 # the encoder: the stages on the device (ops.png_*); packed streams, their byte counts and the Adler words come to the host
 # ------------------------------------------------------------------------------------------
@@ -100,20 +97,10 @@ MAX_FRAMES_PER_LAUNCH = 64
 SCRATCH_BYTES = 256 << 20         # frames per launch are chosen so that filtered bytes, tokens, tables and slots stay below this; results do not depend on it
 
 
-def _check_frames(frames, what: str):
-    import torch
-    if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_cuda \
-            or frames.shape[0] < 1:
-        raise ValueError(f"{what}: uint8 frames (N, H, W, 3) on the device, N >= 1, got "
-                         f"{getattr(frames, 'dtype', type(frames))} {tuple(getattr(frames, 'shape', ()))} {getattr(frames, 'device', '')}")
-    check_size(frames.shape[1], frames.shape[2])
-    return frames.contiguous()
-
-
 def frames_per_launch(h: int, w: int) -> int:
     length = filtered_bytes(h, w)
     per_frame = length + chunks_of(length) * (4 * CHUNK + 2 * 4 * HIST_WORDS + 4 * HEADER_WORDS + SLOT_BYTES + 32) + (length + 1) // 2
-    return max(1, min(int(MAX_FRAMES_PER_LAUNCH), int(SCRATCH_BYTES) // per_frame))
+    return per_launch(MAX_FRAMES_PER_LAUNCH, SCRATCH_BYTES, per_frame)
 
 
 def encode_filtered(filtered) -> List[bytes]:
@@ -127,22 +114,17 @@ def encode_filtered(filtered) -> List[bytes]:
     adler = ops.png_adler(filtered).cpu().tolist()
     sizes = frame_bytes.cpu().tolist()                              # the byte counts: what lets the host take exactly the coded bytes
     packed = ops.png_pack(slots, chunk_bits, chunk_off, n, sum(sizes)).cpu().numpy().tobytes()
-    out, at = [], 0
-    for b, a in zip(sizes, adler):
-        out.append(b"\x78\x01" + packed[at:at + b] + struct.pack(">I", a & 0xffffffff))
-        at += b
-    return out
+    return [b"\x78\x01" + body + struct.pack(">I", a & 0xffffffff) for body, a in zip(split_bytes(packed, sizes), adler)]
 
 
 def encode_frames(frames) -> List[bytes]:
     """uint8 frames (N, H, W, 3) on the device -> per frame its zlib stream (what IDAT / fdAT carry)."""
     from . import ops
-    frames = _check_frames(frames, "encode_frames")
+    frames = check_frames(frames, "encode_frames", check_size)
     n, h, w, _ = frames.shape
-    per = frames_per_launch(h, w)
     out: List[bytes] = []
-    for s in range(0, n, per):
-        out.extend(encode_filtered(ops.png_filter(frames[s:s + per]).reshape(-1, filtered_bytes(h, w))))
+    for g in launch_groups(n, frames_per_launch(h, w)):
+        out.extend(encode_filtered(ops.png_filter(frames[g]).reshape(-1, filtered_bytes(h, w))))
     return out
 
 

@@ -25,6 +25,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import png
+from .codec_common import launch_groups, parsed, per_launch
 
 STATUS_TEXT = {1: "bad zlib header", 2: "the stream runs past its input", 3: "block type 3", 4: "a stored block's LEN and NLEN disagree",
                5: "an over-subscribed or incomplete Huffman code", 6: "bad code-length runs", 7: "invalid code or symbol",
@@ -169,7 +170,7 @@ def parse(data: bytes) -> PngInfo:
 # the decoder: two stages on the device (ops.pngdec_*), only the compressed bytes and the offset table go up
 # ------------------------------------------------------------------------------------------
 def frames_per_launch(h: int, w: int) -> int:
-    return max(1, min(int(MAX_FRAMES_PER_LAUNCH), int(SCRATCH_BYTES) // png.filtered_bytes(h, w)))
+    return per_launch(MAX_FRAMES_PER_LAUNCH, SCRATCH_BYTES, png.filtered_bytes(h, w))
 
 
 def pack_streams(streams: Sequence[bytes]):
@@ -195,11 +196,10 @@ def decode_streams(streams: Sequence[bytes], h: int, w: int, device, check: bool
     if len(streams) < 1:
         raise ValueError("decode: no frames")
     png.check_size(h, w)
-    per = frames_per_launch(h, w)
     out = None
     status = np.zeros((len(streams), 2), np.int32)
-    for s in range(0, len(streams), per):
-        part = streams[s:s + per]
+    for g in launch_groups(len(streams), frames_per_launch(h, w)):
+        s, part = g.start, streams[g]
         data, table = pack_streams(part)
         filtered, st_inflate = ops.pngdec_inflate(torch.from_numpy(data).to(device), torch.from_numpy(table).to(device), h, w)
         rgb, st_unfilter = ops.pngdec_unfilter(filtered, h, w)
@@ -218,21 +218,13 @@ def decode_streams(streams: Sequence[bytes], h: int, w: int, device, check: bool
     return out, status
 
 
-def _parsed(datas: Sequence[bytes], infos: Optional[Sequence[PngInfo]]) -> Sequence[PngInfo]:
-    if infos is None:
-        return [parse(d) for d in datas]
-    if len(infos) != len(datas):
-        raise ValueError(f"decode: {len(infos)} parsed headers for {len(datas)} files")
-    return infos
-
-
 def decode(datas: Sequence[bytes], device, infos: Optional[Sequence[PngInfo]] = None):
     """N PNG files (bytes) of one size -> uint8 (N, H, W, 3) on `device`: each file's first frame, as Image.open gives it.  `infos`: their
     parse() results, when the caller has them.  PngUnsupported / ValueError from the parser: nothing was launched;
     ValueError("frame i: ... (code c at byte p)"): the device stopped in that file's stream.  Pillow raises OSError on such a file."""
     if len(datas) < 1:
         raise ValueError("decode: no frames")
-    infos = _parsed(datas, infos)
+    infos = parsed(datas, infos, parse)
     sizes = {(i.height, i.width) for i in infos}
     if len(sizes) != 1:
         raise ValueError(f"decode: frames of different sizes {sorted(sizes)}")

@@ -210,6 +210,15 @@ def check_propagate(args, video_paths) -> None:
                 raise ValueError(f"--propagate: {video}: {e}") from e
 
 
+def video_writer(args):
+    """The ONE place that reads --save_type, --gif_encoder and --video_quality -> (the writer's entry in ccedit_amd/video_io.py, None
+    where the save type is no movie of uint8 frames (npy); its options: perform_save_locally_video takes them by keyword, the save
+    function of scripts/sampling/util.py the entry names by position after fps)."""
+    from ccedit_amd.video_io import writer_of
+    writer = writer_of(args.save_type, getattr(args, "gif_encoder", "pillow"))
+    return writer, {k: getattr(args, k) for k in (writer.options if writer else ())}
+
+
 def propagate_chunk(args, cvideos, samples, dev, save_path):
     """--propagate for one chunk: per clip all source frames on the device, the edited keyframes as the uint8 frames result/ holds
     (frames_to_u8 without rounding of the decoder output), propagate_clip, <save_path>/result_full/gif/animation-XXXX.gif (--save_type
@@ -217,7 +226,9 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
     are, on the device; so is the gif with --gif_encoder device) at --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
     from ccedit_amd import ops
     from ccedit_amd.propagate import propagate_clip
-    from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask, save_avi_u8, save_gif_u8, save_png_u8
+    from scripts.sampling import util
+    from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask
+    writer, options = video_writer(args)
     edited = ops.frames_to_u8(samples.float().contiguous(), rounding=False, unit_range=False)           # (bs, T, H, W, 3)
     paths = []
     for b, v in enumerate(cvideos):
@@ -229,14 +240,9 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
                                     device=dev, all_frames=True).contiguous()
         idx = keyframe_indices(n_all, args.original_fps, args.target_fps, args.num_keyframes)
         full = propagate_clip(source, idx, edited[b], masks=masks)
-        if args.save_type == "mjpeg":
-            paths.append(save_avi_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps, args.video_quality))
-        elif args.save_type == "png":
-            paths.append(save_png_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps))
-        elif getattr(args, "gif_encoder", "pillow") == "device":        # encoded from the frames where they are, on the device
-            paths.append(save_gif_u8(os.path.join(save_path, "result_full"), full.contiguous(), args.original_fps, gif_encoder="device"))
-        else:
-            paths.append(save_gif_u8(os.path.join(save_path, "result_full"), full.cpu().numpy(), args.original_fps))
+        frames = full.contiguous() if writer.on_device else full.cpu().numpy()      # (a device writer encodes the frames where they are)
+        save = getattr(util, writer.saver)                                         # (found on the module now: save_gif_u8(path, host frames, fps) for Pillow's gif)
+        paths.append(save(os.path.join(save_path, "result_full"), frames, args.original_fps, *options.values()))
     return paths
 
 
@@ -328,15 +334,13 @@ def text_inputs(cond, dev, args=None):
 def save_result(args, tag, x):
     """sampling_tv2v.py:473-515: clamp to [0,1]; .npy frames (default) or an animated gif / a Motion-JPEG .avi / an animated PNG + frame grid."""
     from scripts.sampling.util import perform_save_locally_video, save_frames
-    quality = dict(video_quality=args.video_quality) if args.save_type == "mjpeg" else {}
-    if getattr(args, "gif_encoder", "pillow") == "device":
-        quality["gif_encoder"] = "device"
-    if args.save_type in ("gif", "mjpeg", "png") and getattr(args, "gpu_io", False):
+    writer, options = video_writer(args)
+    if writer and getattr(args, "gpu_io", False):
         perform_save_locally_video(os.path.join(args.save_path, "result"), x, fps=args.target_fps, savetype=args.save_type, gpu_io=True, signed=True,
-                                   **quality)
-    elif args.save_type in ("gif", "mjpeg", "png"):
+                                   **options)
+    elif writer:
         perform_save_locally_video(os.path.join(args.save_path, "result"), torch.clamp((x + 1.0) / 2.0, 0.0, 1.0),
-                                   fps=args.target_fps, savetype=args.save_type, **quality)
+                                   fps=args.target_fps, savetype=args.save_type, **options)
     save_frames(args.save_path, tag, x)
 
 
@@ -703,14 +707,9 @@ def run_jobs(args, with_ref: bool = False) -> None:
             print(f"chunk {idx}: {bs} clip(s) of {T} frames {H}x{W} in {time.time() - t0:.2f}s")
             to01 = lambda v: (torch.clamp(v.float(), -1.0, 1.0) + 1.0) / 2.0
             save_path = video_save_paths[idx] if video_save_paths else os.path.join(args.save_path, base_tag)
-            if args.gpu_io and args.save_type in ("gif", "mjpeg", "png"):       # uint8 frames made on the device: clamp((x + 1) / 2) is in the kernel
-                to01, io = (lambda v: v), dict(gpu_io=True, signed=True)
-            else:                                                         # (.npy keeps fp32 frames: the host route)
-                io = {}
-            if args.save_type == "mjpeg":
-                io["video_quality"] = args.video_quality
-            if getattr(args, "gif_encoder", "pillow") == "device":
-                io["gif_encoder"] = "device"
+            writer, io = video_writer(args)
+            if args.gpu_io and writer:                                    # uint8 frames made on the device: clamp((x + 1) / 2) is in the kernel
+                to01, io = (lambda v: v), dict(io, gpu_io=True, signed=True)          # (.npy keeps fp32 frames: the host route)
             perform_save_locally_video(os.path.join(save_path, "original"), to01(keyframes), args.target_fps, args.save_type, save_grid=False, **io)
             keyframes_paths = perform_save_locally_video(os.path.join(save_path, "result"), to01(samples), args.target_fps, args.save_type,
                                                          return_savepaths=True, save_grid=False, **io)

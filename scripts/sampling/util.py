@@ -273,124 +273,12 @@ def load_vae_file(model, vae_path: str) -> None:
 
 # ------------------------------------------------------------------------------------------
 # frame / video I/O: reference scripts/sampling/util.py:288-382, 689-762
-# Image files, GIFs and the JPEG frames of a Motion-JPEG .avi (ccedit_amd/mjpeg.py: read_avi walks the container) go through Pillow on
-# the host route.  With a device, .jpg / .jpeg files and .avi frames are decoded THERE (ccedit_amd/jpegdec.py: the same bytes as Pillow's);
-# a file outside the subset the device decodes goes through Pillow as before, with one line on stderr per clip.  The same holds for
-# .png files and the frames of an animated .png (ccedit_amd/pngdec.py: 8-bit RGB, not interlaced).
-# mp4 needs a codec library (decord / cv2 / imageio-ffmpeg) that is not installed here and raises.
+# Which way a source or a file goes is data: ccedit_amd/video_io.py holds the table of source kinds (directory of frame files, .gif,
+# Motion-JPEG .avi, animated .png) with their device decoders, and the table of writers.  The functions here keep the reference's names,
+# arguments and arithmetic, and ask there.
 # ------------------------------------------------------------------------------------------
-_JPEG_EXT = (".jpg", ".jpeg")
-
-
-def _jpeg_files_u8_device(paths, device, what: str):
-    """The image files `paths` -> list of uint8 (1, h, w, 3) tensors on `device`, or None when they go through Pillow as before: not all
-    of them are .jpg / .jpeg, or the parser refuses one (one line on stderr names it), or one is not a three-component JPEG
-    (_decode_rgb_u8 takes RGB images only, and says so).  Each file is parsed once.  Corrupt entropy-coded data, which Pillow decodes
-    with a warning, is a ValueError here, naming file, frame and interval."""
-    import sys
-    from ccedit_amd import jpegdec
-    if not paths or not all(p.lower().endswith(_JPEG_EXT) for p in paths):
-        return None
-    datas, infos = [], []
-    for p in paths:
-        with open(p, "rb") as f:
-            datas.append(f.read())
-        try:
-            infos.append(jpegdec.parse(datas[-1]))
-        except jpegdec.JpegUnsupported as e:
-            sys.stderr.write(f"[jpegdec] {what}: {os.path.basename(p)}: {e}; this clip is decoded by Pillow on the host\n")
-            return None
-        if infos[-1].ncomp != 3:
-            return None
-    try:
-        if len({(i.height, i.width) for i in infos}) == 1:
-            return [jpegdec.decode(datas, device, infos=infos)]
-        return [jpegdec.decode([d], device, infos=[i]) for d, i in zip(datas, infos)]
-    except jpegdec.JpegUnsupported:
-        raise
-    except ValueError as e:
-        raise ValueError(f"{what}: {e}") from e
-
-
-def _avi_u8_device(video_path: str, device, select=None):
-    """The frames of an MJPG .avi (all, or those at the indices select(number of frames)) -> uint8 (N, h, w, 3) on `device`, decoded
-    there; only they are decoded, but every frame is parsed, so that a clip goes ONE way as a whole: None when the parser refuses
-    any frame (one line on stderr names it), and the clip then goes through Pillow as before."""
-    import sys
-    from ccedit_amd import jpegdec, mjpeg
-    try:
-        return mjpeg.decode_avi_device(video_path, device, select)
-    except jpegdec.JpegUnsupported as e:
-        sys.stderr.write(f"[jpegdec] {e}; this clip is decoded by Pillow on the host\n")
-        return None
-
-
-def _png_files_u8_device(paths, device, what: str):
-    """The image files `paths` -> list of uint8 (1, h, w, 3) tensors on `device` (one (n, h, w, 3) tensor when they share a size), or None
-    when they go through Pillow as before: not all of them are .png, or the parser does not take one (one line on stderr names it).
-    Each file is parsed once; only the compressed bytes go up (ccedit_amd/pngdec.py: the same bytes as Pillow's).  A stream the device
-    stops in, which Pillow reports as an OSError, is a ValueError here, naming file, frame, code and byte position."""
-    import sys
-    from ccedit_amd import pngdec
-    if not paths or not all(p.lower().endswith(".png") for p in paths):
-        return None
-    datas, infos = [], []
-    for p in paths:
-        with open(p, "rb") as f:
-            datas.append(f.read())
-        try:
-            infos.append(pngdec.parse(datas[-1]))
-        except ValueError as e:                                  # (PngUnsupported is one)
-            sys.stderr.write(f"[pngdec] {what}: {os.path.basename(p)}: {e}; this clip is decoded by Pillow on the host\n")
-            return None
-    same, k = len({(i.height, i.width) for i in infos}) == 1, 0
-    try:
-        if same:
-            return [pngdec.decode(datas, device, infos=infos)]
-        out = []
-        for k in range(len(datas)):
-            out.append(pngdec.decode([datas[k]], device, infos=[infos[k]]))
-        return out
-    except ValueError as e:
-        m = re.match(r"frame (\d+): (.*)", str(e))                 # (the decoder's "frame i" counts inside its call)
-        if m:
-            k = int(m.group(1)) if same else k
-            raise ValueError(f"{what}: {os.path.basename(paths[k])}: frame {k}: {m.group(2)}") from e
-        raise ValueError(f"{what}: {e}") from e
-
-
-def _image_files_u8_device(paths, device, what: str):
-    """Frame files decoded on the device where a decoder takes the whole clip: JPEG (.jpg / .jpeg) or PNG; None: Pillow, as before."""
-    on_device = _jpeg_files_u8_device(paths, device, what)
-    return on_device if on_device is not None else _png_files_u8_device(paths, device, what)
-
-
-def _apng_u8_device(video_path: str, device, select=None):
-    """The frames of an animated .png (all, or those at the indices select(number of frames)) -> uint8 (N, h, w, 3) on `device`, decoded
-    there; only they are decoded, but the whole file is parsed, so that a clip goes ONE way as a whole: None when the parser does not
-    take the file (one line on stderr names why), and the clip then goes through Pillow as before."""
-    import sys
-    from ccedit_amd import pngdec
-    with open(video_path, "rb") as f:
-        data = f.read()
-    try:
-        info = pngdec.parse(data)
-    except ValueError as e:
-        sys.stderr.write(f"[pngdec] {video_path}: {e}; this clip is decoded by Pillow on the host\n")
-        return None
-    try:
-        return pngdec.decode_apng(data, device, select, info=info)
-    except ValueError as e:
-        raise ValueError(f"{video_path}: {e}") from e
-
-
-def _u8_to_float_device(groups, size) -> torch.Tensor:
-    """uint8 (n, h, w, 3) tensors on the device -> fp32 (T, 3, H, W) in [-1, 1]: what _frames_to_device does after its upload."""
-    from ccedit_amd import ops
-    if len(groups) > 1:
-        assert size, "frames of different sizes need a target size"
-    out = [ops.resize_u8_pil(g.contiguous(), size or tuple(g.shape[1:3]), to_float=True) for g in groups]
-    return (out[0] if len(out) == 1 else torch.cat(out, dim=1)).permute(1, 0, 2, 3)
+from ccedit_amd import video_io                                                    # noqa: E402
+from ccedit_amd.video_io import GIF_ENCODERS, HWC3                                 # noqa: E402, F401  (util.py:559-576 is HWC3)
 
 
 def _decode_rgb_u8(path: str) -> np.ndarray:
@@ -402,31 +290,49 @@ def _decode_rgb_u8(path: str) -> np.ndarray:
     return a
 
 
-def _frames_to_device(frames, size, device) -> torch.Tensor:
-    """uint8 frames (list of (h, w, 3) arrays) -> fp32 (T, 3, H, W) in [-1, 1] on `device`: ONE upload of the uint8 frames and one
-    launch per resize pass for the whole clip when they share a size (else per frame), Pillow's 8-bit bicubic + x / 255 * 2 - 1 in
-    ccedit_amd/csrc/pixel.hip — bit-identical to load_img on the host."""
+def _upload(frames, device):
+    """uint8 frames (list of (h, w, 3) arrays) -> uint8 tensors on `device`: ONE upload of the whole clip when the frames share a size,
+    else one (1, h, w, 3) tensor per frame."""
+    groups = [np.stack(frames, axis=0)] if len({f.shape for f in frames}) == 1 else [f[None] for f in frames]
+    return [torch.from_numpy(np.ascontiguousarray(g)).to(device) for g in groups]
+
+
+def _files_u8(paths, device, what: str):
+    """Image files -> uint8 (n, h, w, 3) tensors on `device`: decoded there where a decoder takes the whole clip, else Pillow's frames."""
+    on_device = video_io.files_u8_device(video_io.FILES.device, paths, device, what)
+    return on_device if on_device is not None else _upload([_decode_rgb_u8(p) for p in paths], device)
+
+
+def _clip_u8(kind, video_path: str, device, select=None):
+    """A video in one file (all frames, or those at select(number of frames)) -> [uint8 (N, h, w, 3) on `device`]: decoded there where a
+    decoder takes the whole clip, else Pillow's frames, selected before the upload."""
+    on_device = video_io.clip_u8_device(kind.device, video_path, device, select)
+    if on_device is not None:
+        return [on_device]
+    frames = kind.u8(video_path)
+    return _upload(list(frames if select is None else frames[select(frames.shape[0])]), device)
+
+
+def _u8_to_float(groups, size) -> torch.Tensor:
+    """uint8 (n, h, w, 3) tensors on the device -> fp32 (T, 3, H, W) in [-1, 1]: one launch per resize pass for the whole clip when the
+    frames share a size (else per frame), Pillow's 8-bit bicubic + x / 255 * 2 - 1 in ccedit_amd/csrc/pixel.hip — bit-identical to
+    load_img on the host."""
     from ccedit_amd import ops
-    if len({f.shape for f in frames}) == 1:
-        groups = [np.stack(frames, axis=0)]
-    else:
+    if len(groups) > 1:
         assert size, "frames of different sizes need a target size"
-        groups = [f[None] for f in frames]
-    out = [ops.resize_u8_pil(torch.from_numpy(np.ascontiguousarray(g)).to(device), size or g.shape[1:3], to_float=True) for g in groups]
+    out = [ops.resize_u8_pil(g.contiguous(), size or tuple(g.shape[1:3]), to_float=True) for g in groups]
     return (out[0] if len(out) == 1 else torch.cat(out, dim=1)).permute(1, 0, 2, 3)
 
 
 def load_img(p_cond_img: str, size: tuple = None, device=None) -> torch.Tensor:
     """util.py:360-382: image file -> (1, 3, H, W) in [-1, 1], optional bicubic resize to size = (H, W).
-    device=None: Pillow and torch on the host, as the reference.  With a device a .jpg / .jpeg file is decoded there (ccedit_amd/jpegdec.py),
-    any other image is decoded by Pillow and uploaded as uint8; either is resized / scaled there (same values, bit for bit)."""
+    device=None: Pillow and torch on the host, as the reference.  With a device a .jpg / .jpeg / .png file is decoded there
+    (ccedit_amd/jpegdec.py, pngdec.py), any other image is decoded by Pillow and uploaded as uint8; either is resized / scaled there
+    (same values, bit for bit)."""
     if device is not None:
         if size:
             assert len(size) == 2, "size should be (H, W)"
-        on_device = _image_files_u8_device([p_cond_img], device, p_cond_img)
-        if on_device is not None:
-            return _u8_to_float_device(on_device, size)
-        return _frames_to_device([_decode_rgb_u8(p_cond_img)], size, device)
+        return _u8_to_float(_files_u8([p_cond_img], device, p_cond_img), size)
     from PIL import Image
     img = Image.open(p_cond_img)
     if size:
@@ -450,208 +356,58 @@ def keyframe_indices(num_allframes: int, original_fps: int, target_fps: int, num
     return np.asarray(idx[:num_keyframes])
 
 
-def HWC3(x: np.ndarray) -> np.ndarray:
-    """util.py:559-576: uint8 image with 1 / 3 / 4 channels (or none) -> 3 channels (alpha blended on white)."""
-    assert x.dtype == np.uint8
-    if x.ndim == 2:
-        x = x[:, :, None]
-    assert x.ndim == 3
-    c = x.shape[2]
-    assert c in (1, 3, 4)
-    if c == 3:
-        return x
-    if c == 1:
-        return np.concatenate([x, x, x], axis=2)
-    color = x[:, :, 0:3].astype(np.float32)
-    alpha = x[:, :, 3:4].astype(np.float32) / 255.0
-    return (color * alpha + 255.0 * (1.0 - alpha)).clip(0, 255).astype(np.uint8)
-
-
-def _decode_gif_u8(video_path: str) -> np.ndarray:
-    """All frames of a .gif or an animated .png -> uint8 (N, h, w, 3) on the host (transparency blended on white, as HWC3)."""
-    from PIL import Image, ImageSequence
-    return np.stack([HWC3(np.array(fr.convert("RGBA") if fr.mode == "P" and "transparency" in fr.info else fr.convert("RGB")))
-                     for fr in ImageSequence.Iterator(Image.open(video_path))], axis=0)
-
-
-def _is_apng(path: str) -> bool:
-    """An animated PNG: a .png file with more than one frame (what --save_type png writes for a clip).  A still .png is not a video:
-    it stays what it was at every place that asks (an unsupported video format; ONE mask image)."""
-    if not path.lower().endswith(".png") or not os.path.isfile(path):
-        return False
-    from PIL import Image
-    try:
-        with Image.open(path) as im:
-            return int(getattr(im, "n_frames", 1)) > 1
-    except Exception:
-        return False
-
-
-def _is_frame_file(video_path: str) -> bool:
-    """A video held in ONE file whose frames Pillow decodes: an animated .gif, a Motion-JPEG .avi or an animated .png."""
-    return video_path.endswith((".gif", ".avi")) or _is_apng(video_path)
-
-
-def _decode_video_u8(video_path: str) -> np.ndarray:
-    """All frames of a .gif, an animated .png or an MJPG .avi -> uint8 (N, h, w, 3) on the host; from here on all are treated alike.  An .avi that is
-    missing, truncated or holds another codec is a ValueError that says so (ccedit_amd.mjpeg.read_avi)."""
-    if video_path.endswith(".avi"):
-        from ccedit_amd.mjpeg import decode_avi_u8
-        return decode_avi_u8(video_path)
-    return _decode_gif_u8(video_path)
-
-
 def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
     """(not in the reference) ALL frames of what load_video_keyframes reads -> uint8 (F, H, W, 3) on `device` at size = (H, W): the
-    source side of --propagate.  JPEG sources (a directory of .jpg / .jpeg files, the frames of an .avi) are decoded on the device
-    (ccedit_amd/jpegdec.py: only the compressed bytes go up; Pillow's bytes exactly); everything else, and a JPEG the device decoder
-    refuses, is decoded by Pillow on the host and uploaded.  The frames reach the output size by the routes of the keyframes —
-    image files by Pillow's 8-bit bicubic (ops.resize_u8_pil), .gif and .avi frames by the fp32 bicubic of F.interpolate and then the
-    nearest byte (ops.resize_bicubic, ops.frames_to_u8 with rounding)."""
+    source side of --propagate.  JPEG and PNG sources (a directory of such files, the frames of an .avi or of an animated .png) are
+    decoded on the device (ccedit_amd/jpegdec.py, pngdec.py: only the compressed bytes go up; Pillow's bytes exactly); everything else,
+    and a clip the device decoder declines, is decoded by Pillow on the host and uploaded.  The frames reach the output size by the
+    routes of the keyframes — image files by Pillow's 8-bit bicubic (ops.resize_u8_pil), the frames of a video in one file by the fp32
+    bicubic of F.interpolate and then the nearest byte (ops.resize_bicubic, ops.frames_to_u8 with rounding)."""
     from ccedit_amd import ops
     assert device is not None and size and len(size) == 2, "load_video_frames_u8 works on a device, size should be (H, W)"
-    if os.path.isdir(video_path):
-        files = sorted(os.listdir(video_path))
-        on_device = _image_files_u8_device([os.path.join(video_path, f) for f in files], device, video_path)
-        if on_device is not None:
-            out = [ops.resize_u8_pil(g.contiguous(), size) for g in on_device]
-            return out[0] if len(out) == 1 else torch.cat(out, dim=0)
-        frames = [_decode_rgb_u8(os.path.join(video_path, f)) for f in files]
-        groups = [np.stack(frames, axis=0)] if len({f.shape for f in frames}) == 1 else [f[None] for f in frames]
-        out = [ops.resize_u8_pil(torch.from_numpy(np.ascontiguousarray(g)).to(device), size) for g in groups]
+    kind = video_io.kind_of(video_path)
+    if kind is video_io.FILES:
+        groups = _files_u8([os.path.join(video_path, f) for f in sorted(os.listdir(video_path))], device, video_path)
+        out = [ops.resize_u8_pil(g.contiguous(), size) for g in groups]
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
-    if _is_frame_file(video_path):
-        on_device = _avi_u8_device(video_path, device) if video_path.endswith(".avi") else (
-            _apng_u8_device(video_path, device) if video_path.lower().endswith(".png") else None)
-        if on_device is not None:
-            x = _u8_to_float_device([on_device], None).contiguous()
-        else:
-            x = _frames_to_device(list(_decode_video_u8(video_path)), None, device).contiguous()     # (F, 3, h, w) in [-1, 1]
-        x = ops.resize_bicubic(x, size)
-        return ops.frames_to_u8(x.permute(1, 0, 2, 3)[None].contiguous(), rounding=True)[0]
-    if video_path.endswith(".mp4"):
-        raise NotImplementedError("mp4 decoding needs decord / cv2 / imageio-ffmpeg, none of which is installed; "
-                                  "extract the frames to a directory of images (or a .gif) instead")
-    raise ValueError("Unsupported video format. Only support dirctory, .mp4, .gif and .avi (Motion-JPEG).")
-
-
-GIF_ENCODERS = ("pillow", "device")
-
-
-def _write_gif_device(savepath: str, frames, fps: int) -> str:
-    """uint8 frames (T, H, W, 3), on the device or on the host (then uploaded once) -> `savepath`: palettes and LZW streams come from the
-    device (ccedit_amd/gif.py, csrc/gif.hip), only they come back; the container is written here on the host."""
-    from ccedit_amd import gif
-    if not torch.is_tensor(frames):
-        frames = torch.from_numpy(np.ascontiguousarray(frames))
-    if not frames.is_cuda:
-        frames = frames.to(torch.device("cuda", torch.cuda.current_device()))
-    return gif.write_gif(savepath, gif.encode_frames(frames.contiguous()), gif.duration_ms(fps), frames.shape[2], frames.shape[1])
-
-
-def save_gif_u8(save_path: str, frames, fps: int, gif_encoder: str = "pillow") -> str:
-    """uint8 frames (T, H, W, 3) -> <save_path>/gif/animation-XXXX.gif, numbered and written like perform_save_locally_video's.
-    gif_encoder='device' (not in the reference): the frames, a device tensor or a host array that is uploaded once, are quantised and
-    LZW-coded on the device; 'pillow' (the default) writes the file with Pillow, byte for byte as before."""
-    if gif_encoder not in GIF_ENCODERS:
-        raise ValueError(f"gif_encoder {gif_encoder!r}: one of {GIF_ENCODERS}")
-    os.makedirs(os.path.join(save_path, "gif"), exist_ok=True)
-    count = len(os.listdir(os.path.join(save_path, "gif")))
-    savepath = os.path.join(save_path, "gif", f"animation-{count:04}.gif")
-    if gif_encoder == "device":
-        return _write_gif_device(savepath, frames, fps)
-    from PIL import Image
-    imgs = [Image.fromarray(f) for f in frames]
-    imgs[0].save(savepath, save_all=True, append_images=imgs[1:], duration=int(round(1000.0 / fps)), loop=0)
-    return savepath
-
-
-def save_avi_u8(save_path: str, frames, fps: int, quality: int = 90) -> str:
-    """uint8 frames (T, H, W, 3), on the device or on the host (then uploaded) -> <save_path>/mjpeg/animation-XXXX.avi, numbered like
-    save_gif_u8's files: Motion-JPEG, every frame encoded on the device (ccedit_amd/mjpeg.py), only the compressed bytes come back."""
-    from ccedit_amd import mjpeg
-    if not torch.is_tensor(frames):
-        frames = torch.from_numpy(np.ascontiguousarray(frames))
-    if not frames.is_cuda:
-        frames = frames.to(torch.device("cuda", torch.cuda.current_device()))
-    os.makedirs(os.path.join(save_path, "mjpeg"), exist_ok=True)
-    count = len(os.listdir(os.path.join(save_path, "mjpeg")))
-    savepath = os.path.join(save_path, "mjpeg", f"animation-{count:04}.avi")
-    return mjpeg.write_avi(savepath, mjpeg.encode_frames(frames, quality), fps, frames.shape[1], frames.shape[2])
-
-
-def save_png_u8(save_path: str, frames, fps: int) -> str:
-    """uint8 frames (T, H, W, 3), on the device or on the host (then uploaded) -> <save_path>/png/animation-XXXX.png, numbered like
-    save_gif_u8's files: an animated PNG (one frame: a plain PNG) holding exactly these bytes, rows filtered and deflate-coded on the device
-    (ccedit_amd/png.py, csrc/png.hip); only the compressed streams come back, the container is written on the host."""
-    from ccedit_amd import png
-    if not torch.is_tensor(frames):
-        frames = torch.from_numpy(np.ascontiguousarray(frames))
-    if not frames.is_cuda:
-        frames = frames.to(torch.device("cuda", torch.cuda.current_device()))
-    os.makedirs(os.path.join(save_path, "png"), exist_ok=True)
-    count = len(os.listdir(os.path.join(save_path, "png")))
-    savepath = os.path.join(save_path, "png", f"animation-{count:04}.png")
-    return png.write_apng(savepath, png.encode_frames(frames.contiguous()), png.duration_ms(fps), frames.shape[2], frames.shape[1])
+    x = ops.resize_bicubic(_u8_to_float(_clip_u8(kind, video_path, device), None).contiguous(), size)      # (F, 3, h, w) in [-1, 1] -> (F, 3, H, W)
+    return ops.frames_to_u8(x.permute(1, 0, 2, 3)[None].contiguous(), rounding=True)[0]
 
 
 def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None,
                          device=None) -> torch.Tensor:
-    """util.py:689-762: directory of frame images, a .gif or a Motion-JPEG .avi -> keyframes (T, 3, H, W) in [-1, 1].
-    device=None: everything on the host, as the reference.  With a device, JPEG sources (.jpg / .jpeg files, the frames of an .avi) are
-    decoded there (ccedit_amd/jpegdec.py: only the compressed bytes go up, the frames are Pillow's byte for byte); everything else, and
-    a JPEG the device decoder refuses, is decoded by Pillow on the host and uploaded once as uint8.  Either way the keyframes are
-    resized / scaled by the kernels of ccedit_amd/csrc/pixel.hip: image files exactly as on the host (Pillow's 8-bit bicubic), .gif
-    and .avi frames by the fp32 bicubic of F.interpolate (equal to fp32 rounding)."""
+    """util.py:689-762: directory of frame images, a .gif, a Motion-JPEG .avi or an animated .png -> keyframes (T, 3, H, W) in [-1, 1].
+    device=None: everything on the host, as the reference.  With a device, JPEG and PNG sources (such files, the frames of an .avi or
+    of an animated .png) are decoded there (ccedit_amd/jpegdec.py, pngdec.py: only the compressed bytes go up, the frames are Pillow's
+    byte for byte); everything else, and a clip the device decoder declines, is decoded by Pillow on the host and uploaded once as
+    uint8.  Either way the keyframes are resized / scaled by the kernels of ccedit_amd/csrc/pixel.hip: image files exactly as on the
+    host (Pillow's 8-bit bicubic), the frames of a video in one file by the fp32 bicubic of F.interpolate (equal to fp32 rounding)."""
     if device is not None and size:
         assert len(size) == 2, "size should be (H, W)"
-    if os.path.isdir(video_path):
+    select = lambda n: keyframe_indices(n, original_fps, target_fps, num_keyframes)      # noqa: E731
+    kind = video_io.kind_of(video_path)
+    if kind is video_io.FILES:
         files = sorted(os.listdir(video_path))
-        idx = keyframe_indices(len(files), original_fps, target_fps, num_keyframes)
+        paths = [os.path.join(video_path, files[i]) for i in select(len(files))]
         if device is not None:
-            on_device = _image_files_u8_device([os.path.join(video_path, files[i]) for i in idx], device, video_path)
-            if on_device is not None:
-                return _u8_to_float_device(on_device, size)
-            return _frames_to_device([_decode_rgb_u8(os.path.join(video_path, files[i])) for i in idx], size, device)
-        return torch.cat([load_img(os.path.join(video_path, files[i]), size) for i in idx], dim=0)
-    if _is_frame_file(video_path):
-        if device is not None and (video_path.endswith(".avi") or video_path.lower().endswith(".png")):
-            from ccedit_amd import ops
-            select = lambda n: keyframe_indices(n, original_fps, target_fps, num_keyframes)      # noqa: E731
-            on_device = _avi_u8_device(video_path, device, select) if video_path.endswith(".avi") else _apng_u8_device(video_path, device, select)
-            if on_device is not None:
-                x = _u8_to_float_device([on_device], None).contiguous()
-                return ops.resize_bicubic(x, size) if size else x
-        frames = _decode_video_u8(video_path)
-        if device is not None:
-            from ccedit_amd import ops
-            frames = frames[keyframe_indices(frames.shape[0], original_fps, target_fps, num_keyframes)]
-            x = _frames_to_device(list(frames), None, device).contiguous()                # uint8 -> x / 255 * 2 - 1, (T, 3, h, w)
-            return ops.resize_bicubic(x, size) if size else x
-        frames = torch.from_numpy(frames).permute(0, 3, 1, 2).float() / 255.0
-        frames = frames[keyframe_indices(frames.shape[0], original_fps, target_fps, num_keyframes)]
-        frames = torch.clamp(frames * 2.0 - 1.0, -1.0, 1.0)
-        if size:
-            assert len(size) == 2, "size should be (H, W)"
-            frames = torch.nn.functional.interpolate(frames, size=size, mode="bicubic", align_corners=False)
-        return frames
-    if video_path.endswith(".mp4"):
-        raise NotImplementedError("mp4 decoding needs decord / cv2 / imageio-ffmpeg, none of which is installed; "
-                                  "extract the frames to a directory of images (or a .gif) instead")
-    raise ValueError("Unsupported video format. Only support dirctory, .mp4, .gif and .avi (Motion-JPEG).")
+            return _u8_to_float(_files_u8(paths, device, video_path), size)
+        return torch.cat([load_img(p, size) for p in paths], dim=0)
+    if device is not None:
+        from ccedit_amd import ops
+        x = _u8_to_float(_clip_u8(kind, video_path, device, select), None).contiguous()       # uint8 -> x / 255 * 2 - 1, (T, 3, h, w)
+        return ops.resize_bicubic(x, size) if size else x
+    frames = torch.from_numpy(kind.u8(video_path)).permute(0, 3, 1, 2).float() / 255.0
+    frames = frames[select(frames.shape[0])]
+    frames = torch.clamp(frames * 2.0 - 1.0, -1.0, 1.0)
+    if size:
+        assert len(size) == 2, "size should be (H, W)"
+        frames = torch.nn.functional.interpolate(frames, size=size, mode="bicubic", align_corners=False)
+    return frames
 
 
 def count_video_frames(video_path: str) -> int:
-    """Number of frames of what load_video_keyframes reads: files of a directory, frames of a .gif or of a Motion-JPEG .avi."""
-    if os.path.isdir(video_path):
-        return len(os.listdir(video_path))
-    if video_path.endswith(".gif") or _is_apng(video_path):
-        from PIL import Image
-        return int(getattr(Image.open(video_path), "n_frames", 1))
-    if video_path.endswith(".avi"):
-        from ccedit_amd.mjpeg import read_avi
-        return len(read_avi(video_path)[0])
-    raise ValueError("Unsupported video format. Only support dirctory, .mp4, .gif and .avi (Motion-JPEG).")
+    """Number of frames of what load_video_keyframes reads: files of a directory, frames of a .gif, a Motion-JPEG .avi or an animated .png."""
+    return video_io.kind_of(video_path, mp4_hint=False).count(video_path)
 
 
 _MASK_IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".tif", ".tiff")
@@ -664,12 +420,13 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
     mask_path: what load_video_keyframes accepts — a directory of images, a .gif or a Motion-JPEG .avi, one mask per frame of the VIDEO: `num_allframes`
     (None: not checked) must equal its frame count, the keyframes are selected by the same `keyframe_indices` rule as the frames — or
     ONE image file, used for every keyframe.  Any image mode is taken through its luminance (`convert("L")`); a value >= 128 is white.
+    Every kind is decoded by Pillow on the host (an .avi through ccedit_amd.mjpeg.decode_avi_u8).
     Resize to size = (H, W) is nearest-neighbour on the binarised mask, src = floor((dst + 0.5) * in / out) (Pillow's NEAREST, its
     running sum in double included: ccedit_amd/packing.py pil_nearest_index).  device=None: Pillow on the host.  With a device the
     binarised keyframe masks are uploaded once and gathered there (ccedit_mask_resize_nearest): identical bytes.
     all_frames (--propagate): the masks of ALL frames of the video, (num_allframes, H, W), instead of the keyframes'; one image file is
     repeated num_allframes times (which must then be given)."""
-    from PIL import Image, ImageSequence
+    from PIL import Image
     if size:
         assert len(size) == 2, "size should be (H, W)"
 
@@ -677,16 +434,9 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
         a = np.array(img.convert("L"))
         return np.where(a >= 128, 255, 0).astype(np.uint8)
 
-    if os.path.isdir(mask_path):
-        files = sorted(os.listdir(mask_path))
-        n, pick = len(files), lambda i: lum(Image.open(os.path.join(mask_path, files[i])))
-    elif mask_path.endswith(".gif") or _is_apng(mask_path):
-        frames = [lum(fr) for fr in ImageSequence.Iterator(Image.open(mask_path))]
-        n, pick = len(frames), lambda i: frames[i]
-    elif mask_path.endswith(".avi"):
-        from ccedit_amd.mjpeg import decode_avi_u8
-        frames = [lum(Image.fromarray(fr)) for fr in decode_avi_u8(mask_path)]
-        n, pick = len(frames), lambda i: frames[i]
+    kind = video_io.kind_of(mask_path, missing_ok=True)
+    if kind is not None:
+        n, pick = kind.pil(mask_path, lum)
     elif mask_path.lower().endswith(_MASK_IMAGE_EXT):
         one = lum(Image.open(mask_path))
         n, pick = None, lambda i: one
@@ -694,18 +444,13 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
         raise ValueError(f"Unsupported mask format: {mask_path}. Only support directory, .gif, .avi (Motion-JPEG) and one image file {_MASK_IMAGE_EXT}.")
     if all_frames and n is None and num_allframes is None:
         raise ValueError("load_video_mask(all_frames=True) of one image needs num_allframes")
+    if n is not None and num_allframes is not None and n != num_allframes:
+        raise ValueError(f"mask {mask_path} has {n} frames, the video has {num_allframes}: a mask sequence needs one mask per frame "
+                         "(or give one image for all frames)")
     if n is None:
         masks = [pick(0)] * (num_allframes if all_frames else num_keyframes)
-    elif all_frames:
-        if num_allframes is not None and n != num_allframes:
-            raise ValueError(f"mask {mask_path} has {n} frames, the video has {num_allframes}: a mask sequence needs one mask per frame "
-                             "(or give one image for all frames)")
-        masks = [pick(i) for i in range(n)]
     else:
-        if num_allframes is not None and n != num_allframes:
-            raise ValueError(f"mask {mask_path} has {n} frames, the video has {num_allframes}: a mask sequence needs one mask per frame "
-                             "(or give one image for all frames)")
-        masks = [pick(int(i)) for i in keyframe_indices(n, original_fps, target_fps, num_keyframes)]
+        masks = [pick(int(i)) for i in (range(n) if all_frames else keyframe_indices(n, original_fps, target_fps, num_keyframes))]
     if len({m.shape for m in masks}) != 1:
         raise ValueError(f"mask {mask_path}: frames of different sizes {sorted({m.shape for m in masks})}")
     if device is not None:
@@ -716,6 +461,26 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
         h, w = size
         masks = [np.array(Image.fromarray(m).resize((w, h), Image.NEAREST)) for m in masks]
     return torch.from_numpy(np.ascontiguousarray(np.stack(masks, axis=0)))
+
+
+def save_gif_u8(save_path: str, frames, fps: int, gif_encoder: str = "pillow") -> str:
+    """uint8 frames (T, H, W, 3) -> <save_path>/gif/animation-XXXX.gif, numbered and written like perform_save_locally_video's.
+    gif_encoder='device' (not in the reference): the frames, a device tensor or a host array that is uploaded once, are quantised and
+    LZW-coded on the device; 'pillow' (the default) writes the file with Pillow, byte for byte as before."""
+    return video_io.save_u8(save_path, video_io.writer_of("gif", gif_encoder), frames, fps)
+
+
+def save_avi_u8(save_path: str, frames, fps: int, quality: int = 90) -> str:
+    """uint8 frames (T, H, W, 3), on the device or on the host (then uploaded) -> <save_path>/mjpeg/animation-XXXX.avi, numbered like
+    save_gif_u8's files: Motion-JPEG, every frame encoded on the device (ccedit_amd/mjpeg.py), only the compressed bytes come back."""
+    return video_io.save_u8(save_path, video_io.writer_of("mjpeg"), frames, fps, video_quality=quality)
+
+
+def save_png_u8(save_path: str, frames, fps: int) -> str:
+    """uint8 frames (T, H, W, 3), on the device or on the host (then uploaded) -> <save_path>/png/animation-XXXX.png, numbered like
+    save_gif_u8's files: an animated PNG (one frame: a plain PNG) holding exactly these bytes, rows filtered and deflate-coded on the device
+    (ccedit_amd/png.py, csrc/png.hip); only the compressed streams come back, the container is written on the host."""
+    return video_io.save_u8(save_path, video_io.writer_of("png"), frames, fps)
 
 
 def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, savetype: str = "gif",
@@ -737,64 +502,33 @@ def perform_save_locally_video(save_path: str, samples: torch.Tensor, fps: int, 
     from PIL import Image
     assert samples.dim() == 5, "Expected samples to have shape (B, C, T, H, W)"
     assert savetype in ["gif", "mp4", "npy", "mjpeg", "png"]
-    if gif_encoder not in GIF_ENCODERS:
-        raise ValueError(f"gif_encoder {gif_encoder!r}: one of {GIF_ENCODERS}")
-    if gif_encoder == "device" and savetype != "gif":
-        raise ValueError(f"gif_encoder='device' encodes gifs: savetype must be 'gif', got {savetype!r}")
+    writer = video_io.writer_of(savetype, gif_encoder)             # (the gif_encoder checks; None: npy, mp4)
     assert gpu_io or not signed, "signed samples are only taken on the gpu_io route"
     if savetype == "mp4":
         raise NotImplementedError("mp4 encoding needs imageio-ffmpeg / cv2, not installed here: use savetype='gif'")
     u8 = u8_grid = None
     if gpu_io:
         from ccedit_amd import ops
-        if savetype not in ("gif", "mjpeg", "png") or not samples.is_cuda:
+        if writer is None or not samples.is_cuda:
             raise ValueError("gpu_io saves uint8 frames (savetype='gif') of a device tensor")
         x = samples.detach().float().contiguous()
         u8 = ops.frames_to_u8(x, rounding=False, unit_range=not signed)                                # (B, T, H, W, 3)
-        u8 = u8 if savetype in ("mjpeg", "png") or gif_encoder == "device" else u8.cpu().numpy()      # (mjpeg, png, device gif: the frames stay on the device)
+        u8 = u8 if writer.on_device else u8.cpu().numpy()                  # (a device writer: the frames stay on the device)
         u8_grid = ops.frames_to_u8(x, rounding=True, unit_range=not signed).cpu().numpy() if save_grid else None
-    if savetype == "npy":          # (not in the reference) the frames themselves: <save_path>/npy/frames-XXXX.npy, (T, H, W, C) float32 in [0, 1]
-        os.makedirs(os.path.join(save_path, "npy"), exist_ok=True)
-        count = len(os.listdir(os.path.join(save_path, "npy")))
-        savepaths = []
-        for sample in samples:
-            savepath = os.path.join(save_path, "npy", f"frames-{count:04}.npy")
-            np.save(savepath, sample.detach().float().cpu().permute(1, 2, 3, 0).numpy())
-            count += 1
-            savepaths.append(savepath)
-        return savepaths if return_savepaths else None
-    os.makedirs(os.path.join(save_path, savetype), exist_ok=True)
-    count = len(os.listdir(os.path.join(save_path, savetype)))
-    if save_grid:
-        os.makedirs(os.path.join(save_path, "grid"), exist_ok=True)
-        count_grid = len(os.listdir(os.path.join(save_path, "grid")))
     savepaths = []
+    if savetype == "npy":          # (not in the reference) the frames themselves: <save_path>/npy/frames-XXXX.npy, (T, H, W, C) float32 in [0, 1]
+        for sample in samples:
+            savepaths.append(video_io.next_path(os.path.join(save_path, "npy"), "frames", ".npy"))
+            np.save(savepaths[-1], sample.detach().float().cpu().permute(1, 2, 3, 0).numpy())
+        return savepaths if return_savepaths else None
+    options = {k: v for k, v in dict(video_quality=video_quality, gif_encoder=gif_encoder).items() if k in writer.options}
     for b, sample in enumerate(samples):
         if u8 is None:
             frames_f = sample.detach().float().cpu().permute(1, 2, 3, 0).numpy()          # (T, H, W, C)
         if save_grid:
             # torchvision.utils.save_image(normalize=False, padding=0): x * 255 + 0.5, clamp, uint8
             grid = np.concatenate(list(np.clip(frames_f * 255.0 + 0.5, 0, 255).astype(np.uint8) if u8 is None else u8_grid[b]), axis=1)
-            Image.fromarray(grid).save(os.path.join(save_path, "grid", f"grid-{count_grid:04}.png"))
-            count_grid += 1
-        if savetype == "mjpeg":
-            savepath = save_avi_u8(save_path, (255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b], fps, video_quality)
-            count += 1
-            savepaths.append(savepath)
-            continue
-        if savetype == "png":
-            savepath = save_png_u8(save_path, (255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b], fps)
-            count += 1
-            savepaths.append(savepath)
-            continue
-        savepath = os.path.join(save_path, "gif", f"animation-{count:04}.gif")
-        if gif_encoder == "device":
-            _write_gif_device(savepath, (255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b], fps)
-            count += 1
-            savepaths.append(savepath)
-            continue
-        frames = [Image.fromarray(f) for f in ((255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b])]
-        frames[0].save(savepath, save_all=True, append_images=frames[1:], duration=int(round(1000.0 / fps)), loop=0)
-        count += 1
-        savepaths.append(savepath)
+            Image.fromarray(grid).save(video_io.next_path(os.path.join(save_path, "grid"), "grid", ".png"))
+        savepaths.append(video_io.save_u8(save_path, writer, (255.0 * frames_f).astype(np.uint8) if u8 is None else u8[b], fps, **options))
     return savepaths if return_savepaths else None
+

@@ -223,29 +223,29 @@ def test_cabi_pngdec():
 
 # ---- the routing, as far as it goes without a device: what is declined is declined by parsing alone
 def test_routing_declines_without_a_device(tmp_path, capsys, monkeypatch):
-    from scripts.sampling import util as U
+    from ccedit_amd import video_io as V
     mixed = tmp_path / "mixed"
     mixed.mkdir()
     img = K.image(16, 24, 1)
     Image.fromarray(img).save(str(mixed / "000.png"))
     Image.fromarray(img).save(str(mixed / "001.jpg"))
     paths = [str(mixed / f) for f in sorted(os.listdir(str(mixed)))]
-    assert U._png_files_u8_device(paths, "cuda", "mixed") is None and U._image_files_u8_device(paths, "cuda", "mixed") is None
+    assert V.files_u8_device((V.PNG,), paths, "cuda", "mixed") is None and V.files_u8_device(V.FILES.device, paths, "cuda", "mixed") is None
     assert capsys.readouterr().err == ""
     odd = tmp_path / "odd"
     odd.mkdir()
     Image.fromarray(img).save(str(odd / "000.png"))
     Image.fromarray(img).convert("RGBA").save(str(odd / "001.png"))
     paths = [str(odd / f) for f in sorted(os.listdir(str(odd)))]
-    assert U._png_files_u8_device(paths, "cuda", "the clip") is None
+    assert V.files_u8_device((V.PNG,), paths, "cuda", "the clip") is None
     err = capsys.readouterr().err
     assert err.count("\n") == 1 and err.startswith("[pngdec] the clip: 001.png: ") and "alpha" in err
     assert err.endswith("this clip is decoded by Pillow on the host\n")
     bad = tmp_path / "bad.png"
     data = open(str(odd / "000.png"), "rb").read()
     bad.write_bytes(data[:50] + bytes([data[50] ^ 4]) + data[51:])
-    assert U._png_files_u8_device([str(bad)], "cuda", "one") is None and "CRC" in capsys.readouterr().err
-    assert U._png_files_u8_device([], "cuda", "none") is None
+    assert V.files_u8_device((V.PNG,), [str(bad)], "cuda", "one") is None and "CRC" in capsys.readouterr().err
+    assert V.files_u8_device((V.PNG,), [], "cuda", "none") is None
     # a status from the device names file, frame, code and byte position (the decoder itself is stood in for: there is no device here)
     Image.fromarray(img[::-1]).save(str(odd / "001.png"))
     Image.fromarray(img[:8]).save(str(odd / "002.png"))
@@ -256,9 +256,9 @@ def test_routing_declines_without_a_device(tmp_path, capsys, monkeypatch):
         return None
     monkeypatch.setattr(D, "decode", stopped)
     with pytest.raises(ValueError, match=r"^the clip: 001.png: frame 1: Adler-32 mismatch \(code 11 at byte 77\)$"):
-        U._png_files_u8_device(paths, "cuda", "the clip")                       # same size: one call
+        V.files_u8_device((V.PNG,), paths, "cuda", "the clip")                       # same size: one call
     with pytest.raises(ValueError, match=r"^the clip: 001.png: frame 1: Adler-32 mismatch \(code 11 at byte 77\)$"):
-        U._png_files_u8_device(paths + [str(odd / "002.png")], "cuda", "the clip")      # another size among them: a call per file
+        V.files_u8_device((V.PNG,), paths + [str(odd / "002.png")], "cuda", "the clip")      # another size among them: a call per file
     monkeypatch.undo()
     anim = P.write_apng(str(tmp_path / "rgba.png"), M.encode_frames(np.stack([K.image(8, 9, i) for i in range(2)])), 100, 9, 8)
     raw = bytearray(open(anim, "rb").read())
@@ -266,6 +266,6 @@ def test_routing_declines_without_a_device(tmp_path, capsys, monkeypatch):
     raw[at + 8:at + 12] = struct.pack(">I", 8)                                   # a narrower second frame
     raw[at + 30:at + 34] = struct.pack(">I", zlib.crc32(bytes(raw[at:at + 30])) & 0xffffffff)
     open(anim, "wb").write(bytes(raw))
-    assert U._apng_u8_device(anim, "cuda") is None
+    assert V.clip_u8_device(V.APNG.device, anim, "cuda") is None
     err = capsys.readouterr().err
     assert err.startswith("[pngdec] ") and "partial-frame fcTL" in err and err.endswith("this clip is decoded by Pillow on the host\n")

@@ -217,12 +217,13 @@ def _interlaced(img: np.ndarray) -> bytes:
 
 def test_animated_png_equals_the_gif_route(tmp_path, monkeypatch, capfd):
     """An animated .png (8 frames of 128 x 192, the own encoder's file) through both loaders, at its own size and at (64, 96): the device
-    decoder and the _decode_gif_u8 route (the parser made to refuse) give the same tensors, frame for frame."""
+    decoder and Pillow's route, the .gif's, (the parser made to refuse) give the same tensors, frame for frame."""
     _need_gpu()
     from scripts.sampling import util as U
     frames = np.stack([K.image(128, 192, 30 + i) for i in range(8)])
     path = P.write_apng(str(tmp_path / "clip.png"), M.encode_frames(frames), 125, 192, 128)
-    assert U._is_frame_file(path) and U.count_video_frames(path) == 8
+    from ccedit_amd import video_io
+    assert video_io.kind_of(path) is video_io.APNG and U.count_video_frames(path) == 8
     calls = _count_launches(monkeypatch)
 
     def load():
