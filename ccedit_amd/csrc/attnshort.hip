@@ -10,15 +10,13 @@
 // segments through an LDS staging tile.  The general flash kernel (attention.hip, one 64-thread workgroup per
 // (pixel, head), 80-byte row pieces) reaches 2.2 / 1.9 / 0.9 TB/s on these launches.
 #include "common.h"
+#include "streamw.h"      // lds_barrier(): here __syncthreads() would wait for the prefetch of the next pixel
 
 namespace {
 
 constexpr int GW = 320;                   // channels per workgroup
 constexpr int GR = GW / 8;                // 16-byte granules per row
 constexpr int RS = GW * 2 + 16;           // LDS row stride: 164 dwords, rows land 36 banks apart
-
-// LDS-only workgroup barrier: __syncthreads() would also drain vmcnt, i.e. wait for the prefetch of the next pixel
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int D>
 __global__ __launch_bounds__(256) void attn_short_kernel(const CcAttnDesc a, int nblk) {

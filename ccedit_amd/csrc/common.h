@@ -135,6 +135,21 @@ static inline int cc_max_dynamic_lds(const void* fn, int bytes, unsigned long lo
     return CCEDIT_OK;
 }
 
+// ... for every arm (template instantiation) of a kernel family, once per device at the family's FIRST launch there — not at the
+// arm's own first launch, which can fall inside a graph capture.  One `done` word per family.
+template <class... Arms>
+static inline int cc_family_dynamic_lds(int bytes, unsigned long long* done, const char* what, Arms*... arms) {
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && dev < 64 && ((*done >> dev) & 1ull)) return CCEDIT_OK;
+    int rc = CCEDIT_OK;
+    for (const void* fn : {(const void*)arms...}) {
+        unsigned long long arm_done = 0;
+        if (rc == CCEDIT_OK) rc = cc_max_dynamic_lds(fn, bytes, &arm_done, what);
+    }
+    if (rc == CCEDIT_OK && dev < 64) *done |= 1ull << dev;
+    return rc;
+}
+
 static inline int cc_launch_status(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -12,6 +12,7 @@
 // Slices of wider layers (640 / 960 / 2560 rows) run as different workgroups of one XCD on the SAME pixel tiles at the
 // same time, so the activation rows come out of that XCD's L2 for all but the first.
 #include "common.h"
+#include "streamw.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -30,8 +31,6 @@ constexpr int kERow = kSlice * 4 + 16;          // fp32 staging row of one pixel
 constexpr int kStage = kP * kERow;              // 41,472 B
 constexpr int kNT = 512;
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // LN: the rows of A are LayerNorm-normalised ((x - mean) * rstd over the 320 channels, rounded to bf16) on their way through
 // LDS — `q = to_q(norm(x))` without the normalised tensor ever existing in memory.  gamma / beta are folded into W / bias by
 // the packer (W' = W diag(gamma), b' = b + W beta), d.ln_eps carries the epsilon.
@@ -48,16 +47,11 @@ __global__ __launch_bounds__(kNT, 1) void lin320_kernel(const CcGemmDesc d, int 
     const int grp = wave & 3, khalf = wave >> 2;
     const int l31 = lane & 31, hi = lane >> 5;
 
-    // workgroup b runs on XCD b % 8: its 32 workgroups take (32 / nslice) pixel lanes x nslice channel slices
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int lanes = 32 / nslice;
-    const int slice = j % nslice, plane = j / nslice;
-    if (plane >= lanes) return;
-    const int per_xcd = (pt_n + 7) >> 3;
-    const int pt_lo = xcd * per_xcd, pt_hi = min(pt_lo + per_xcd, pt_n);
-    int pt = pt_lo + plane;
-    if (pt >= pt_hi) return;
-    const int ch0 = slice * kSlice;
+    const WorkSplit ws = work_split(blockIdx.x, nslice, pt_n);      // pixel tiles pt, pt + lanes, ... < pt_hi
+    if (ws.first >= ws.end) return;
+    const int lanes = ws.lanes, pt_hi = ws.end;
+    int pt = ws.first;
+    const int ch0 = ws.slice * kSlice;
 
     // ---- the weight slice: A-operand fragments, resident for the whole kernel ----
     bf16x8 wf[3][kKS / 2];
@@ -158,7 +152,7 @@ __global__ __launch_bounds__(kNT, 1) void lin320_kernel(const CcGemmDesc d, int 
     const int my_issues = (2 * 8 + wave < kWaveIssues) ? 3 : 2;      // DMA instructions of this wave per tile
     stage(pt, 0);
     if (pt + lanes < pt_hi) stage(pt + lanes, 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vmcnt<0>();
     int buf = 0, sb = 0, prev_pt = -1;
     for (; pt < pt_hi; pt += lanes) {
         // tile `pt` has landed for every wave; the sums of tile pt-1 are complete in staging tile sb^1; staging tile sb has
@@ -175,7 +169,8 @@ __global__ __launch_bounds__(kNT, 1) void lin320_kernel(const CcGemmDesc d, int 
         if (more) stage(pt + 2 * lanes, buf == 0 ? 2 : buf - 1);      // (buf + 2) % 3
         if constexpr (LN) {
             // 16 threads per pixel row: granules sub, sub + 16, sub + 32 (< 40) of the row; two-pass statistics in fp32 as in
-            // layernorm_kernel (norm.hip), the normalised row written back in place
+            // layernorm_kernel (norm.hip), the normalised row written back in place.  (The same text stands in lin320s_kernel: moved
+            // into a shared function, hipcc vectorises and contracts the sums of THIS kernel differently and its output bits change.)
             char* const rowp = sX + buf * kXBuf + (tid >> 4) * kRS;
             const int sub = tid & 15;
             bf16x8 t[3];
@@ -224,28 +219,20 @@ __global__ __launch_bounds__(kNT, 1) void lin320_kernel(const CcGemmDesc d, int 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ti][r] = 0.f;
         const char* xb = sX + buf * kXBuf + l31 * kRS + khalf * kK + hi * 16;
-        // the activation fragment of k-step ks + 2 is requested before the MFMAs of k-step ks are issued (hipcc on its own
-        // reads, waits, multiplies, reads again)
-        bf16x8 xq[3];
-        xq[0] = *(const bf16x8*)(xb);
-        xq[1] = *(const bf16x8*)(xb + 32);
+        frag_pipeline<kKS / 2, 3>([&](int ks) { return *(const bf16x8*)(xb + ks * 32); },
+                                  [&](int ks, const bf16x8& x) {
 #pragma unroll
-        for (int ks = 0; ks < kKS / 2; ++ks) {
-            if (ks + 2 < kKS / 2) xq[(ks + 2) % 3] = *(const bf16x8*)(xb + (ks + 2) * 32);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ti = 0; ti < 3; ++ti)
-                if (ti == 0 || grp < 3)        // 320 = 3 * 96 + 32: the last wave group has one real row tile, do not multiply padding
-                    acc[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ti][ks], xq[ks % 3], acc[ti], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+                                      for (int ti = 0; ti < 3; ++ti)
+                                          if (ti == 0 || grp < 3)        // 320 = 3 * 96 + 32: the last wave group has one real row tile, do not multiply padding
+                                              acc[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ti][ks], x, acc[ti], 0, 0, 0);
+                                  });
         // Tile pt+1 (staged one iteration ago) must have landed before the next loop-top barrier.  Waited for HERE, before
         // this iteration's stores are issued: loads complete in order, so once at most `my_issues` operations (the DMA just
         // issued for tile pt+2) are outstanding, tile pt+1 is complete — and so are the previous output pass's stores, which
         // share the counter but have had a whole iteration to drain.
-        if (!more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (my_issues == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        if (!more) vmcnt<0>();
+        else if (my_issues == 3) vmcnt<3>();
+        else vmcnt<2>();
         // while the MFMAs execute: the previous tile's output pass
         if (prev_pt >= 0) output_pass(prev_pt, sb ^ 1);
 
@@ -274,7 +261,7 @@ __global__ __launch_bounds__(kNT, 1) void lin320_kernel(const CcGemmDesc d, int 
         }
         if constexpr (RES) load_residual(pt);     // for this tile's output pass, one iteration from now
         prev_pt = pt;
-        buf = buf == 2 ? 0 : buf + 1;
+        ring_next<3>(buf);
         sb ^= 1;
     }
     lds_barrier();
@@ -303,21 +290,25 @@ __global__ __launch_bounds__(kNT, 1) void lin320_kernel(const CcGemmDesc d, int 
 // relies on); other shapes keep lin320_kernel.
 constexpr int kBufsS = 7;
 
-template <int N>
-__device__ __forceinline__ void l3_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// The counted wait of this kernel is a run-time switch, not streamw.h's wait_later: all eight waves request AND store (a store in
+// the queue makes the wait longer than needed, never shorter), the 21 DMA instructions of a tile make 3 or 2 per wave (doubled
+// with a residual), so (tiles in flight behind the awaited one) x (loads per tile) is wave-uniform but no compile-time constant.
 __device__ __forceinline__ void l3_vmcnt_n(int n) {      // n is wave-uniform
     switch (n) {
-        case 0: l3_vmcnt<0>(); break;
-        case 2: l3_vmcnt<2>(); break;
-        case 3: l3_vmcnt<3>(); break;
-        case 4: l3_vmcnt<4>(); break;
-        case 6: l3_vmcnt<6>(); break;
-        case 8: l3_vmcnt<8>(); break;
-        case 9: l3_vmcnt<9>(); break;
-        case 12: l3_vmcnt<12>(); break;
-        default: l3_vmcnt<0>(); break;
+        case 0: vmcnt<0>(); break;
+        case 2: vmcnt<2>(); break;
+        case 3: vmcnt<3>(); break;
+        case 4: vmcnt<4>(); break;
+        case 6: vmcnt<6>(); break;
+        case 8: vmcnt<8>(); break;
+        case 9: vmcnt<9>(); break;
+        case 12: vmcnt<12>(); break;
+        default: vmcnt<0>(); break;
     }
 }
+struct XPair {      // the B fragments of a k-step for the two 16-pixel halves of a tile
+    bf16x8 p[2];
+};
 
 template <bool RES, bool LN>
 __global__ __launch_bounds__(kNT, 1) void lin320s_kernel(const CcGemmDesc d, int nslice, int pt_n) {
@@ -332,16 +323,10 @@ __global__ __launch_bounds__(kNT, 1) void lin320s_kernel(const CcGemmDesc d, int
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, g4 = lane >> 4;
 
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int lanes = 32 / nslice;
-    const int slice = j % nslice, plane = j / nslice;
-    if (plane >= lanes) return;
-    const int per_xcd = (pt_n + 7) >> 3;
-    const int pt_lo = xcd * per_xcd, pt_hi = min(pt_lo + per_xcd, pt_n);
-    const int pt0 = pt_lo + plane;
-    if (pt0 >= pt_hi) return;
-    const int ntile = (pt_hi - pt0 + lanes - 1) / lanes;        // tiles of this workgroup: pt0 + i * lanes
-    const int ch0 = slice * kSlice;
+    const WorkSplit ws = work_split(blockIdx.x, nslice, pt_n);
+    if (ws.count == 0) return;
+    const int lanes = ws.lanes, pt0 = ws.first, ntile = ws.count;      // tiles of this workgroup: pt0 + i * lanes
+    const int ch0 = ws.slice * kSlice;
 
     // ---- DMA plan (as lin320_kernel): slot n of a tile = row n / 41, granule n % 41 (granule 40 = row padding) ----
     const bf16* __restrict__ Ap = (const bf16*)d.A;
@@ -395,21 +380,10 @@ __global__ __launch_bounds__(kNT, 1) void lin320s_kernel(const CcGemmDesc d, int
         bf16x8 wf[NTW][kK / 32];
         f32x4 bq[NTW];
         {
-            const bf16* __restrict__ Wp = (const bf16*)d.W;
 #pragma unroll
             for (int ti = 0; ti < NTW; ++ti) {
-                if (d.Wfrag) {      // fragment-ordered copy (CcGemmDesc.Wfrag): one contiguous kilobyte per fragment and wave
-                    const bf16* blk = (const bf16*)d.Wfrag + ((size_t)((ch0 >> 4) + tile0 + ti) * (kK / 32) * 64 + lane) * 8;
-#pragma unroll
-                    for (int ks = 0; ks < kK / 32; ++ks) wf[ti][ks] = *(const bf16x8*)(blk + ks * 512);
-                } else {
-                    const bf16* row = Wp + (size_t)(ch0 + 16 * (tile0 + ti) + c16) * d.Kpad + g4 * 8;
-#pragma unroll
-                    for (int ks = 0; ks < kK / 32; ++ks) wf[ti][ks] = *(const bf16x8*)(row + ks * 32);
-                }
-                const int cb = ch0 + 16 * (tile0 + ti) + 4 * g4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) bq[ti][e] = d.bias ? d.bias[cb + e] : 0.f;
+                load_wfrags<kK>(wf[ti], d, ch0 + 16 * (tile0 + ti), lane, [](int ks) { return 32 * ks; });
+                bq[ti] = load_quad(d.bias, ch0 + 16 * (tile0 + ti) + 4 * g4);
             }
         }
         const int xlane = c16 * kRS + g4 * 16;                  // B fragment of pixel tile p, k-step ks: + p * 16 rows + ks * 64
@@ -420,20 +394,18 @@ __global__ __launch_bounds__(kNT, 1) void lin320s_kernel(const CcGemmDesc d, int
         int staged = 0;
         for (; staged < RX - 1 && staged < ntile; ++staged) {
             stage(staged, xs, os);
-            xs = xs == RX - 1 ? 0 : xs + 1;
-            os = os == RO - 1 ? 0 : os + 1;
+            ring_next<RX>(xs);
+            ring_next<RO>(os);
         }
-        // (round 6) the first tiles were requested BEHIND the weight loads, in the same breath — one latency instead of two at the start
-        // of every launch; this wait covers both: from here on the queue holds DMA and stores only
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vmcnt<0>();      // behind the weight loads, as streamw.h's ring_prologue (here the tile index is an argument of stage)
         int xb = 0, ob = 0, obp = 0;                             // slots of tile i / of tile i - 1's output
         for (int i = 0; i < ntile; ++i) {
             lds_barrier();      // tile i is in LDS for every wave; output tile i-1 is complete; X slot of tile i-1 and O slot of tile i-2 are free
             if (staged < ntile) {
                 stage(staged, xs, os);
                 ++staged;
-                xs = xs == RX - 1 ? 0 : xs + 1;
-                os = os == RO - 1 ? 0 : os + 1;
+                ring_next<RX>(xs);
+                ring_next<RO>(os);
             }
             char* const xt = sXr + xb * kXBuf;
             char* const ot = sOr + ob * kXBuf;
@@ -503,34 +475,30 @@ __global__ __launch_bounds__(kNT, 1) void lin320s_kernel(const CcGemmDesc d, int
                     }
                 }
             const char* const xq0 = xt + xlane;
-            bf16x8 xq[3][2];
+            frag_pipeline<kK / 32, 3>(
+                [&](int ks) {
+                    XPair x;
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                xq[0][p] = *(const bf16x8*)(xq0 + p * 16 * kRS);
-                xq[1][p] = *(const bf16x8*)(xq0 + p * 16 * kRS + 64);
-            }
+                    for (int p = 0; p < 2; ++p) x.p[p] = *(const bf16x8*)(xq0 + p * 16 * kRS + ks * 64);
+                    return x;
+                },
+                [&](int ks, const XPair& x) {
 #pragma unroll
-            for (int ks = 0; ks < kK / 32; ++ks) {
-                if (ks + 2 < kK / 32) {
+                    for (int ti = 0; ti < NTW; ++ti)
 #pragma unroll
-                    for (int p = 0; p < 2; ++p) xq[(ks + 2) % 3][p] = *(const bf16x8*)(xq0 + p * 16 * kRS + (ks + 2) * 64);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                        for (int p = 0; p < 2; ++p)
+                            acc[ti][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ti][ks], x.p[p], acc[ti][p], 0, 0, 0);
+                },
+                [&](int ks) {
+                    if (ks == 1 && i > 0) {
+                        // output pass of tile i - 1, second half: whole rows to memory while the matrix pipe is busy
+                        bf16* const op = (bf16*)d.out + (int64_t)(pt0 + (i - 1) * lanes) * kP * d.ldc;
 #pragma unroll
-                for (int ti = 0; ti < NTW; ++ti)
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)
-                        acc[ti][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ti][ks], xq[ks % 3][p], acc[ti][p], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (ks == 1 && i > 0) {
-                    // output pass of tile i - 1, second half: whole rows to memory while the matrix pipe is busy
-                    bf16* const op = (bf16*)d.out + (int64_t)(pt0 + (i - 1) * lanes) * kP * d.ldc;
-#pragma unroll
-                    for (int k = 0; k < kTI; ++k)
-                        if (k < nt_mine) *(bf16x8*)(op + tout[k]) = ov[k];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+                        for (int k = 0; k < kTI; ++k)
+                            if (k < nt_mine) *(bf16x8*)(op + tout[k]) = ov[k];
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
             // bf16 cells of this wave's channels into the output tile
 #pragma unroll
             for (int ti = 0; ti < NTW; ++ti)
@@ -545,8 +513,8 @@ __global__ __launch_bounds__(kNT, 1) void lin320s_kernel(const CcGemmDesc d, int
             // may still be outstanding
             if (i + 1 < ntile) l3_vmcnt_n((staged - (i + 2)) * per_tile);
             obp = ob;
-            xb = xb == RX - 1 ? 0 : xb + 1;
-            ob = ob == RO - 1 ? 0 : ob + 1;
+            ring_next<RX>(xb);
+            ring_next<RO>(ob);
         }
         lds_barrier();
         {
@@ -574,11 +542,10 @@ bool cc_lin320_applicable(const CcGemmDesc& d) {
 int cc_lin320_launch(const CcGemmDesc& d, hipStream_t s) {
     const int lds = 2 * kStage + 3 * kXBuf + kSlice * 4;
     const bool geglu = d.act == CCEDIT_ACT_GEGLU;
-    static unsigned long long attr_done[4] = {0, 0, 0, 0};
-    if (int rc = cc_max_dynamic_lds((const void*)lin320_kernel<false, false, false>, lds, &attr_done[0], "lin320")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)lin320_kernel<false, true, false>, lds, &attr_done[1], "lin320")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)lin320_kernel<true, false, false>, lds, &attr_done[2], "lin320")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)lin320_kernel<false, false, true>, lds, &attr_done[3], "lin320")) return rc;
+    static unsigned long long attr_done = 0;
+    if (int rc = cc_family_dynamic_lds(lds, &attr_done, "lin320", lin320_kernel<false, false, false>, lin320_kernel<false, true, false>,
+                                       lin320_kernel<true, false, false>, lin320_kernel<false, false, true>))
+        return rc;
     const int64_t pt_n = (d.M + kP - 1) / kP;
     if (pt_n > 2147483647LL) {
         cc_set_error("ccedit_gemm: grid too large");
@@ -587,14 +554,12 @@ int cc_lin320_launch(const CcGemmDesc& d, hipStream_t s) {
     // whole tiles and no GEGLU: the deep-ring variant (policy lin320s = 0: A/B against the K-split kernel)
     if (cc_policy().lin320s && !geglu && d.M % kP == 0) {
         const int lds_s = kBufsS * kXBuf;
-        static unsigned long long attr_s[3] = {0, 0, 0};
-        if (int rc = cc_max_dynamic_lds((const void*)lin320s_kernel<false, false>, lds_s, &attr_s[0], "lin320s")) return rc;
-        if (int rc = cc_max_dynamic_lds((const void*)lin320s_kernel<true, false>, lds_s, &attr_s[1], "lin320s")) return rc;
-        if (int rc = cc_max_dynamic_lds((const void*)lin320s_kernel<false, true>, lds_s, &attr_s[2], "lin320s")) return rc;
+        static unsigned long long attr_s = 0;
+        if (int rc = cc_family_dynamic_lds(lds_s, &attr_s, "lin320s", lin320s_kernel<false, false>, lin320s_kernel<true, false>, lin320s_kernel<false, true>))
+            return rc;
         cc_note_kernel("lin320s_kernel");
-        if (d.res1) hipLaunchKernelGGL((lin320s_kernel<true, false>), dim3(256), dim3(kNT), lds_s, s, d, d.N / kSlice, (int)pt_n);
-        else if (d.ln_eps != 0.f) hipLaunchKernelGGL((lin320s_kernel<false, true>), dim3(256), dim3(kNT), lds_s, s, d, d.N / kSlice, (int)pt_n);
-        else hipLaunchKernelGGL((lin320s_kernel<false, false>), dim3(256), dim3(kNT), lds_s, s, d, d.N / kSlice, (int)pt_n);
+        const auto arm = d.res1 ? lin320s_kernel<true, false> : d.ln_eps != 0.f ? lin320s_kernel<false, true> : lin320s_kernel<false, false>;
+        hipLaunchKernelGGL(arm, dim3(256), dim3(kNT), lds_s, s, d, d.N / kSlice, (int)pt_n);
         return cc_launch_status("lin320s_kernel");
     }
     cc_note_kernel("lin320_kernel");
@@ -606,9 +571,7 @@ int cc_lin320_launch(const CcGemmDesc& d, hipStream_t s) {
     CcGemmDesc dd = d;
     dd.cgroup = flag_env << 24;
     const CcGemmDesc& d2 = dd;
-    if (geglu) hipLaunchKernelGGL((lin320_kernel<true, false, false>), dim3(256), dim3(kNT), lds, s, d2, d.N / kSlice, (int)pt_n);
-    else if (d.res1) hipLaunchKernelGGL((lin320_kernel<false, true, false>), dim3(256), dim3(kNT), lds, s, d2, d.N / kSlice, (int)pt_n);
-    else if (d.ln_eps != 0.f) hipLaunchKernelGGL((lin320_kernel<false, false, true>), dim3(256), dim3(kNT), lds, s, d2, d.N / kSlice, (int)pt_n);
-    else hipLaunchKernelGGL((lin320_kernel<false, false, false>), dim3(256), dim3(kNT), lds, s, d2, d.N / kSlice, (int)pt_n);
+    const auto arm = geglu ? lin320_kernel<true, false, false> : d.res1 ? lin320_kernel<false, true, false> : d.ln_eps != 0.f ? lin320_kernel<false, false, true> : lin320_kernel<false, false, false>;
+    hipLaunchKernelGGL(arm, dim3(256), dim3(kNT), lds, s, d2, d.N / kSlice, (int)pt_n);
     return cc_launch_status("lin320_kernel");
 }

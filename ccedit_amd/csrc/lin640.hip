@@ -11,9 +11,8 @@
 // slower than gemm8p.)  The slices of a layer (3 for 640 channels — the third half empty —, 8 for the 1920 of q,k,v) are different
 // workgroups of one XCD walking the SAME pixel tiles, so the activation rows come out of that XCD's L2 for all but the first.
 //
-// Waves 0..3 issue the DMA, waves 4..7 the stores and atomics: a requesting wave's vector-memory queue then holds loads only and
-// the counted wait is exact (a store in the same queue has to complete as well before the count can fall to the number of younger
-// loads).  No register-returning load inside the loop (the compiler's wait for it would drain the DMA queue).
+// Waves 0..3 issue the DMA, waves 4..7 the stores and atomics, and no register-returning load is left inside the loop: the counted
+// wait is then exact (streamw.h: wait_later, which also holds the other building blocks this kernel shares with lin320s / temp320s).
 //
 // Epilogue in registers: the C layout gives lane (pixel, 4 channels) — the accumulators start from the bias (+ the residual
 // cell: the residual slice arrives by DMA like the activations), leave as bf16 into an LDS tile in row layout (for the residual
@@ -27,18 +26,14 @@
 //        the slice's totals to row_sums[M][2] with double atomics one iteration later — as gemm8p.hip does across channel tiles.
 // Requires M % 16 == 0 (whole tiles: the counted wait relies on the number of loads per iteration), K = Kpad = 640, N % 128 == 0.
 #include "common.h"
+#include "streamw.h"
 #include <stdlib.h>
 
 namespace {
 
 constexpr int kK = 640, kKS = kK / 32;          // 20 MFMA k-steps
 constexpr int kP = 16;                          // pixels per tile
-// Activation tile in LDS: 16 rows of 80 sixteen-byte granules, NO padding; granule j of row r sits at position j ^ (r & 15) of its
-// row (the DMA picks the source granule per destination slot).  ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27},
-// {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md): lane (c, g) of a B fragment reads granule 4 ks + g of row c, so a group holds all
-// sixteen c — half of them with g, half with g + 1 — and both halves are closed under c ^ 1 and c ^ 2: the positions
-// ((4 ks + g) ^ c) cover the sixteen 16-byte bank groups exactly once.  (Rows padded to 1296 B, the usual recipe, put two lanes of
-// every group on the same banks: SQ_LDS_BANK_CONFLICT = 20 % of the kernel's cycles.)
+// Activation tile in LDS: 16 rows of 80 sixteen-byte granules, NO padding, XOR-swizzled (streamw.h: swizzled_lanes has the bank argument)
 constexpr int kRS = kK * 2;                     // 1280 B = 5 x 256: a row's position in the banks depends on the swizzle alone
 constexpr int kGPR = kRS / 16;                  // 80
 constexpr int kXI = kP * kGPR / 64;             // 20 wave-wide DMA instructions per tile (+ one 16-lane instruction for the statistics, LNF)
@@ -53,10 +48,7 @@ constexpr int kNT = 512;
 constexpr int kLds = kRX * kXBuf + kROres * kOBuf + 2 * kP * 16;      // + two [16][2] double accumulators of the row sums: 157,184 B
 constexpr int kXDmax = 6;                       // activation fragments in flight per wave (LDS read -> MFMA distance, in k-steps; 5 with the LayerNorm's extra registers)
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int N>
-__device__ __forceinline__ void l6_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// (these loops are bound by instruction issue — temp320.hip has the measurement: ring slots are wrap-around counters, tile addresses
+// (these loops are bound by instruction issue — streamw.h has the measurement: ring slots are wrap-around counters, tile addresses
 //  running byte offsets, every lane of every DMA instruction has a valid source (no selects, no exec masks), and every requesting wave
 //  issues the same number of loads per tile, so the counted waits are compile-time constants)
 
@@ -73,17 +65,10 @@ __global__ __launch_bounds__(kNT, 1) void lin640s_kernel(const CcGemmDesc d, int
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, g4 = lane >> 4;
 
-    // workgroup b runs on XCD b % 8: its 32 workgroups take (32 / nslice) pixel lanes x nslice channel slices
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int lanes = 32 / nslice;
-    const int slice = j % nslice, plane = j / nslice;
-    if (plane >= lanes) return;
-    const int per_xcd = (pt_n + 7) >> 3;
-    const int pt_lo = xcd * per_xcd, pt_hi = min(pt_lo + per_xcd, pt_n);
-    const int pt0 = pt_lo + plane;
-    if (pt0 >= pt_hi) return;
-    const int ntile = (pt_hi - pt0 + lanes - 1) / lanes;        // tiles of this workgroup: pt0 + i * lanes
-    const int ch0 = slice * kSlice;
+    const WorkSplit ws = work_split(blockIdx.x, nslice, pt_n);
+    if (ws.count == 0) return;
+    const int lanes = ws.lanes, pt0 = ws.first, ntile = ws.count;      // tiles of this workgroup: pt0 + i * lanes
+    const int ch0 = ws.slice * kSlice;
     const bool rsum = d.row_sums != nullptr;                     // (uniform)
     const bool live = ch0 + 32 * wave < d.N;                     // N % 256 == 128: waves 4..7 of the last slice have no channels
 
@@ -136,32 +121,16 @@ __global__ __launch_bounds__(kNT, 1) void lin640s_kernel(const CcGemmDesc d, int
         st_x += x_step;
         st_r += r_step;
         st_s += s_step;
-        st_xs = st_xs == kRX - 1 ? 0 : st_xs + 1;
-        st_os = st_os == (RES ? kROres : kROplain) - 1 ? 0 : st_os + 1;
+        ring_next<kRX>(st_xs);
+        ring_next<RO>(st_os);
     };
-    auto wait_later = [&](int later) {                            // at most the loads of `later` (<= kRX - 2) newer tiles may be outstanding
-        if (later >= 3) l6_vmcnt<3 * kPerTile>();
-        else if (later == 2) l6_vmcnt<2 * kPerTile>();
-        else if (later == 1) l6_vmcnt<kPerTile>();
-        else l6_vmcnt<0>();
-    };
-    static_assert(kRX - 2 == 3, "wait_later covers three tiles in flight behind the awaited one");
 
     // ---- the weight rows of this wave: A-operand fragments, resident for the whole kernel; bias (and colsum) of the lane's 2 x 4 channels ----
     bf16x8 wf[2][kKS];
     f32x4 bq[2], cq[2];
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti) {
-        if (d.Wfrag) {      // fragment-ordered copy (CcGemmDesc.Wfrag): a fragment is one contiguous kilobyte per wave (rows are padded to 256: dead waves read zeros)
-            const bf16* __restrict__ blk = (const bf16*)d.Wfrag + ((size_t)((ch0 + 32 * wave + 16 * ti) >> 4) * (kK / 32) * 64 + lane) * 8;
-#pragma unroll
-            for (int ks = 0; ks < kKS; ++ks) wf[ti][ks] = *(const bf16x8*)(blk + ks * 512);
-        } else {
-            const int cr = min(ch0 + 32 * wave + 16 * ti + c16, d.N - 1);      // (dead waves: any valid row)
-            const bf16* __restrict__ row = (const bf16*)d.W + (size_t)cr * d.Kpad + g4 * 8;
-#pragma unroll
-            for (int ks = 0; ks < kKS; ++ks) wf[ti][ks] = *(const bf16x8*)(row + ks * 32);
-        }
+        load_wfrags<kK>(wf[ti], d, ch0 + 32 * wave + 16 * ti, lane, [](int ks) { return 32 * ks; });
         const int cb = min(ch0 + 32 * wave + 16 * ti + 4 * g4, d.N - 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -170,15 +139,11 @@ __global__ __launch_bounds__(kNT, 1) void lin640s_kernel(const CcGemmDesc d, int
         }
     }
     if (tid < 2 * kP * 2) sSum[tid] = 0.0;
-    // the first tiles are requested BEHIND the weight loads, in the same breath (round 6: one latency instead of two at the start of
-    // every launch); one wait below covers both — from then on a requesting wave's queue holds DMA only
     int staged = 0;
-    for (; staged < kRX - 1 && staged < ntile; ++staged) stage_next();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ring_prologue<kRX>(staged, ntile, stage_next);
 
-    int xlane[4];                                               // B fragment of k-step ks: xlane[ks & 3] + (ks >> 2) * 256
-#pragma unroll
-    for (int m = 0; m < 4; ++m) xlane[m] = c16 * kRS + (((4 * m + g4) ^ c16) << 4);
+    int xlane[4];
+    swizzled_lanes<kRS>(xlane, c16, g4);
     // C cell (pixel c16, channels 32 w + 16 ti + 4 g4 .. + 3) = half (g4 & 1) of granule 4 w + 2 ti + (g4 >> 1), at its swizzled position
     int olane[2];
 #pragma unroll
@@ -202,10 +167,7 @@ __global__ __launch_bounds__(kNT, 1) void lin640s_kernel(const CcGemmDesc d, int
     const double inv_k = 1.0 / kK;
     for (int i = 0; i < ntile; ++i) {
         lds_barrier();      // tile i is in LDS for every wave; output tile i-1 and its row sums are complete; the X slot of tile i-1 and the O slot of tile i-2 are free
-        if (staged < ntile) {
-            stage_next();
-            ++staged;
-        }
+        ring_step(staged, ntile, stage_next);
         const char* const xt = sXr + xb * kXBuf;
         char* const ot = sOr + ob * kOBuf;
         // output pass of tile i - 1, first half: its row pieces out of LDS; its row sums to memory
@@ -213,12 +175,7 @@ __global__ __launch_bounds__(kNT, 1) void lin640s_kernel(const CcGemmDesc d, int
         if (i > 0 && !dma_wave) {
             ov[0] = *(const bf16x8*)(sOr + obp * kOBuf + olds0);
             ov[1] = *(const bf16x8*)(sOr + obp * kOBuf + olds1);
-            if (rsum && wave == 5 && lane < 2 * kP) {
-                double* const acc2 = sSum + ((i - 1) & 1) * 2 * kP + lane;
-                const double v = *acc2;
-                *acc2 = 0.0;
-                unsafeAtomicAdd(d.row_sums + 2 * so_rows + lane, v);
-            }
+            if (rsum && wave == 5 && lane < 2 * kP) lds_flush_f64(sSum + ((i - 1) & 1) * 2 * kP + lane, d.row_sums + 2 * so_rows + lane);
             // stored right away, while the requesting waves issue their DMA (inside the MFMA loop the store would wait for `ov`
             // behind the fragment prefetch in the LDS queue: temp320.hip measured the storing waves 350 cycles per step behind)
             if (ost) {
@@ -262,18 +219,11 @@ __global__ __launch_bounds__(kNT, 1) void lin640s_kernel(const CcGemmDesc d, int
         }
         if (live) {
             constexpr int kXD = LNF ? kXDmax - 1 : kXDmax;
-            bf16x8 xq[kXD];
+            frag_pipeline<kKS, kXD>([&](int ks) { return swizzled_frag(xt, xlane, ks); },
+                                    [&](int ks, const bf16x8& x) {
 #pragma unroll
-            for (int ks = 0; ks < kXD - 1; ++ks) xq[ks] = *(const bf16x8*)(xt + xlane[ks & 3] + (ks >> 2) * 256);
-#pragma unroll
-            for (int ks = 0; ks < kKS; ++ks) {
-                if (ks + kXD - 1 < kKS) xq[(ks + kXD - 1) % kXD] = *(const bf16x8*)(xt + xlane[(ks + kXD - 1) & 3] + ((ks + kXD - 1) >> 2) * 256);
-                __builtin_amdgcn_sched_barrier(0);
-                // the compiler counts the reads still in flight behind this fragment (all issued above, in order)
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti) acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ti][ks], xq[ks % kXD], acc[ti], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+                                        for (int ti = 0; ti < 2; ++ti) acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ti][ks], x, acc[ti], 0, 0, 0);
+                                    });
         }
         // bf16 cells of this wave's 32 channels into the output tile; row sums of the rounded values
         if (live) {
@@ -295,22 +245,18 @@ __global__ __launch_bounds__(kNT, 1) void lin640s_kernel(const CcGemmDesc d, int
                 q += __shfl_xor(q, 16);
                 s += __shfl_xor(s, 32);
                 q += __shfl_xor(q, 32);
-                if (g4 == 0) {
-                    // (asm: for an LDS atomic the compiler first drains the vector-memory queue — the DMA writes LDS too)
-                    const uint32_t a2 = (uint32_t)(uintptr_t)(LDS_AS char*)(sSum + (i & 1) * 2 * kP + 2 * c16);
-                    asm volatile("ds_add_f64 %0, %1\n\tds_add_f64 %0, %2 offset:8" ::"v"(a2), "v"((double)s), "v"((double)q) : "memory");
-                }
+                if (g4 == 0) lds_add_f64_pair(sSum + (i & 1) * 2 * kP + 2 * c16, s, q);
             }
         }
         // tile i + 1 must have landed (this wave's part) before the next barrier: at most the loads of the tiles after it may be outstanding
-        if (i + 1 < ntile && dma_wave) wait_later(staged - (i + 2));
+        if (i + 1 < ntile && dma_wave) wait_later<kPerTile, kRX - 2>(staged - (i + 2));
         if (i > 0) {                                             // the output cursor follows one tile behind
             so_off += o_step;
             so_rows += tile_rows;
         }
         obp = ob;
-        xb = xb == kRX - 1 ? 0 : xb + 1;
-        ob = ob == RO - 1 ? 0 : ob + 1;
+        ring_next<kRX>(xb);
+        ring_next<RO>(ob);
     }
     lds_barrier();
     {
@@ -319,7 +265,7 @@ __global__ __launch_bounds__(kNT, 1) void lin640s_kernel(const CcGemmDesc d, int
             *(bf16x8*)op = *(const bf16x8*)(sOr + obp * kOBuf + olds0);
             *(bf16x8*)(op + oout8) = *(const bf16x8*)(sOr + obp * kOBuf + olds1);
         }
-        if (rsum && wave == 5 && lane < 2 * kP) unsafeAtomicAdd(d.row_sums + 2 * so_rows + lane, sSum[((ntile - 1) & 1) * 2 * kP + lane]);
+        if (rsum && wave == 5 && lane < 2 * kP) lds_flush_f64(sSum + ((ntile - 1) & 1) * 2 * kP + lane, d.row_sums + 2 * so_rows + lane);
     }
 }
 
@@ -335,10 +281,9 @@ bool cc_lin640_applicable(const CcGemmDesc& d) {
 }
 
 int cc_lin640_launch(const CcGemmDesc& d, hipStream_t s) {
-    static unsigned long long attr_done[3] = {0, 0, 0};
-    if (int rc = cc_max_dynamic_lds((const void*)lin640s_kernel<false, false>, kLds, &attr_done[0], "lin640s")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)lin640s_kernel<true, false>, kLds, &attr_done[1], "lin640s")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)lin640s_kernel<false, true>, kLds, &attr_done[2], "lin640s")) return rc;
+    static unsigned long long attr_done = 0;
+    if (int rc = cc_family_dynamic_lds(kLds, &attr_done, "lin640s", lin640s_kernel<false, false>, lin640s_kernel<true, false>, lin640s_kernel<false, true>))
+        return rc;
     const int64_t pt_n = d.M / kP;
     if (pt_n > 2147483647LL) {
         cc_set_error("ccedit_gemm: grid too large");
@@ -346,8 +291,7 @@ int cc_lin640_launch(const CcGemmDesc& d, hipStream_t s) {
     }
     cc_note_kernel("lin640s_kernel");
     const int nslice = (d.N + kSlice - 1) / kSlice;
-    if (d.res1) hipLaunchKernelGGL((lin640s_kernel<true, false>), dim3(256), dim3(kNT), kLds, s, d, nslice, (int)pt_n);
-    else if (d.ln_stats || d.ln_sums) hipLaunchKernelGGL((lin640s_kernel<false, true>), dim3(256), dim3(kNT), kLds, s, d, nslice, (int)pt_n);
-    else hipLaunchKernelGGL((lin640s_kernel<false, false>), dim3(256), dim3(kNT), kLds, s, d, nslice, (int)pt_n);
+    const auto arm = d.res1 ? lin640s_kernel<true, false> : d.ln_stats || d.ln_sums ? lin640s_kernel<false, true> : lin640s_kernel<false, false>;
+    hipLaunchKernelGGL(arm, dim3(256), dim3(kNT), kLds, s, d, nslice, (int)pt_n);
     return cc_launch_status("lin640s_kernel");
 }

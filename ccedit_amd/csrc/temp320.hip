@@ -3,7 +3,7 @@
 //
 // Every block shape of the tiled GEMMs lands at 230-290 us for this layer (208896 rows, 128 GFLOP, 0.4-0.5 GB of operands:
 // a tile sweep, round 4): with 320 output channels a pixel tile meets 3-5 channel tiles, and each of them pulls the rows of
-// three frames through the L2 -> LDS path again.  Here (the scheme of lin320s / lin640s, lin640.hip) a workgroup keeps the
+// three frames through the L2 -> LDS path again.  Here (the scheme of lin320s / lin640s; the shared pieces are in streamw.h) a workgroup keeps the
 // weights of ALL THREE TAPS for a 128-channel slice in registers — wave w: 16 channels x 3 taps x 320 k = 30 A fragments, 120 VGPRs —
 // and walks pixel COLUMNS (clip, 16 pixels) frame by frame: the 16 x 320 activation tile of frame t arrives once by DMA and every
 // fragment read from LDS feeds three MFMAs — tap +1 of output t-1, tap 0 of output t, tap -1 of output t+1 (three rolling
@@ -11,12 +11,13 @@
 // per-clip row bias were its initial value, the residual cells come from tiles that travelled with the activations, it leaves as
 // bf16 through the first residual's tile (in place) and goes to memory one step later as whole 256-byte row pieces.
 //
-// DMA by waves 0-3 only, stores / atomics by waves 4-7 (the counted vmcnt wait is then exact), ring of six 12 KB activation tiles
+// DMA by waves 0-3 only, stores / atomics by waves 4-7 (the counted vmcnt wait is then exact: streamw.h), ring of six 12 KB activation tiles
 // (rows of 768 B, granules XOR-swizzled by the row: conflict-free ds_read_b128 in the 16x16x32 B layout), one barrier per step.
 // GroupNorm(32) statistics of the stored values (gn_stats): per lane the sums of its 4 channels split at the group boundary, a
 // butterfly over the 16 pixels, exact double adds in LDS across waves, double atomics to the frame's slots one step later.
 // Requires Cin = 320 (Kpad = 960), N % 64 == 0, HW % 16 == 0, unsharded frames.
 #include "common.h"
+#include "streamw.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -35,17 +36,7 @@ constexpr int kNT = 512;
 constexpr int kLds = kRX * kXBuf + 2 * kRR * kOBuf + kRX * kGB + 2 * 16 * 16;      // 151,040 B (incl. two [16][2] double statistics arrays)
 constexpr int kXD = 5;                          // activation fragments in flight per wave
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int N>
-__device__ __forceinline__ void t3_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// These loops are bound by INSTRUCTION ISSUE, not by a pipe: a wave issues at most one instruction per four cycles, a step has 30 MFMAs
-// (480 cycles) per wave, and the first version of this kernel spent ~860 instructions per step and wave — 500 of them scalar (ring
-// wrap-arounds, 64-bit address products, exec-mask juggling around lane-dependent DMA selects, a 45-way switch for the counted
-// wait, SGPR spills) — i.e. 1.5 us per step whatever the memory system or the matrix pipe did (ablation: all of MFMA, DMA and
-// stores switched off left 0.56 us per step).  Hence: ring slots as wrap-around counters (three scalar instructions each), running byte
-// offsets instead of row x stride products, DMA sources valid for every lane (padding slots copy a neighbouring granule: no
-// selects, no exec masks), the same number of loads per tile in every requesting wave (compile-time wait counts).
+// (these loops are bound by instruction issue — streamw.h has the measurement and what follows from it)
 template <int NRES, bool GB>
 __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, int nslice, int ncol_clip) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -60,20 +51,13 @@ __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, in
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, g4 = lane >> 4;
 
-    // workgroup b runs on XCD b % 8: its 32 workgroups take (32 / nslice) column lanes x nslice channel slices
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int lanes = 32 / nslice;
-    const int slice = j % nslice, plane = j / nslice;
-    if (plane >= lanes) return;
     const int T = d.T, HW = d.HW;
     const int ncol = (int)(d.M / ((int64_t)T * HW)) * ncol_clip; // columns: (clip, 16-pixel block)
-    const int per_xcd = (ncol + 7) >> 3;
-    const int c_lo = xcd * per_xcd, c_hi = min(c_lo + per_xcd, ncol);
-    const int col0 = c_lo + plane;
-    if (col0 >= c_hi) return;
-    const int mycols = (c_hi - col0 + lanes - 1) / lanes;
+    const WorkSplit ws = work_split(blockIdx.x, nslice, ncol);
+    if (ws.count == 0) return;
+    const int lanes = ws.lanes, col0 = ws.first, mycols = ws.count;      // columns of this workgroup: col0 + ci * lanes
     const int nstep = mycols * T;                                // step s = (column s / T of this workgroup, frame s % T)
-    const int ch0 = slice * kSlice;
+    const int ch0 = ws.slice * kSlice;
     const bool live = ch0 + 16 * wave < d.N;                     // N = 320: waves 4..7 of the third slice have no channels
     const bool gn = d.gn_stats != nullptr;
     const bool dma_wave = wave < 4;
@@ -107,30 +91,15 @@ __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, in
     // ---- the weights of this wave: A fragments [tap][k-step] of channels ch0 + 16 w + (lane & 15); bias of the lane's 4 channels ----
     bf16x8 wf[3][kKS];
     f32x4 bq;
-    {
-        const int cr = min(ch0 + 16 * wave + c16, d.N - 1);
-        const bf16* __restrict__ row = (const bf16*)d.W + (size_t)cr * d.Kpad;
-        // fragment-ordered copy (CcGemmDesc.Wfrag): one contiguous kilobyte per fragment and wave (rows are padded to 256: a wave
-        // beyond N reads zeros); the 32-element k block of (tap, ks) is the one its g4 = 0 lanes start
-        const bf16* __restrict__ blk = (const bf16*)d.Wfrag + ((size_t)((ch0 >> 4) + wave) * (d.Kpad / 32) * 64 + lane) * 8;
+    // (the k order of a weight row is tap-major, or with d.korder 64-channel blocks of the three taps)
 #pragma unroll
-        for (int tap = 0; tap < 3; ++tap)
-#pragma unroll
-            for (int ks = 0; ks < kKS; ++ks) {
-                const int c0 = 32 * ks;
-                const int off0 = d.korder ? (c0 >> 6) * 192 + tap * 64 + (c0 & 63) : tap * kC + c0;
-                if (d.Wfrag) wf[tap][ks] = *(const bf16x8*)(blk + (off0 >> 5) * 512);
-                else wf[tap][ks] = *(const bf16x8*)(row + off0 + 8 * g4);
-            }
-        const int cb = min(ch0 + 16 * wave + 4 * g4, d.N - 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bq[e] = d.bias ? d.bias[cb + e] : 0.f;
-    }
+    for (int tap = 0; tap < 3; ++tap)
+        load_wfrags<3 * kC>(wf[tap], d, ch0 + 16 * wave, lane, [&](int ks) { return d.korder ? (32 * ks >> 6) * 192 + tap * 64 + (32 * ks & 63) : tap * kC + 32 * ks; });
+    bq = load_quad(d.bias, min(ch0 + 16 * wave + 4 * g4, d.N - 4));
     if (tid < 64) sSt[tid] = 0.0;
 
     int xlane[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) xlane[m] = c16 * kRS + (((4 * m + g4) ^ c16) << 4);
+    swizzled_lanes<kRS>(xlane, c16, g4);
     // C cell (pixel c16, channels 16 w + 4 g4 .. + 3) = half (g4 & 1) of granule 2 w + (g4 >> 1), at position granule ^ pixel
     const int olane = c16 * 256 + (((2 * wave + (g4 >> 1)) ^ c16) << 4) + (g4 & 1) * 8;
     const int ot0 = tid & 255;                                   // output pass (waves 4..7): granule ot0 % 16 of row ot0 / 16
@@ -167,8 +136,8 @@ __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, in
                 if (lane < 8) glds16(Gb + (int64_t)st_clip * gb_ld + soffg, sGB + st_xs * kGB + wave * 128);
             }
         }
-        st_xs = st_xs == kRX - 1 ? 0 : st_xs + 1;
-        st_rs = st_rs == kRR - 1 ? 0 : st_rs + 1;
+        ring_next<kRX>(st_xs);
+        ring_next<kRR>(st_rs);
         if (++st_t == T) {
             st_t = 0;
             if (++st_col < mycols) {
@@ -183,19 +152,8 @@ __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, in
             if constexpr (NRES >= 2) st_r2 += r2_step;
         }
     };
-    auto wait_later = [&](int later) {                            // at most the loads of `later` (<= kRX - 2) newer tiles may be outstanding
-        if (later >= 4) t3_vmcnt<4 * kPerTile>();
-        else if (later == 3) t3_vmcnt<3 * kPerTile>();
-        else if (later == 2) t3_vmcnt<2 * kPerTile>();
-        else if (later == 1) t3_vmcnt<kPerTile>();
-        else t3_vmcnt<0>();
-    };
-    static_assert(kRX - 2 == 4, "wait_later covers four tiles in flight behind the awaited one");
     int staged = 0;
-    for (; staged < kRX - 1 && staged < nstep; ++staged) stage_next();
-    // (round 6) the first tiles are requested BEHIND the weight loads, in the same breath — one latency instead of two at the start of
-    // every launch; this wait covers both: from here on a requesting wave's queue holds DMA only
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ring_prologue<kRX>(staged, nstep, stage_next);
     int cx = 0, fr = kRR - 2, sr = kRR - 3;                      // slots: activations of tile s; cells of output s - 2; output s - 3
     // output cursor: the output stored at step s is s - 3
     int so_t = 0, so_col = 0, so_clip;
@@ -243,19 +201,14 @@ __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, in
             s1 = rowsum(s1);
             q1 = rowsum(q1);
             if (c16 == 15) {
-                const uint32_t a0 = (uint32_t)(uintptr_t)(LDS_AS char*)(sSt + parity * 32 + 2 * (gq0 - g_first));
-                asm volatile("ds_add_f64 %0, %1\n\tds_add_f64 %0, %2 offset:8" ::"v"(a0), "v"((double)s0), "v"((double)q0) : "memory");
-                if (nlo < 4) asm volatile("ds_add_f64 %0, %1 offset:16\n\tds_add_f64 %0, %2 offset:24" ::"v"(a0), "v"((double)s1), "v"((double)q1) : "memory");
+                const double* const pair = sSt + parity * 32 + 2 * (gq0 - g_first);
+                lds_add_f64_pair(pair, s0, q0);
+                if (nlo < 4) lds_add_f64_pair<16>(pair, s1, q1);      // the next group's pair
             }
         }
     };
     auto flush_stats = [&](int parity, int frame) {
-        if (gn && wave == 5 && lane < 2 * ngrp) {
-            double* const a = sSt + parity * 32 + lane;
-            const double v = *a;
-            *a = 0.0;
-            unsafeAtomicAdd(d.gn_stats + (int64_t)frame * 64 + 2 * g_first + lane, v);
-        }
+        if (gn && wave == 5 && lane < 2 * ngrp) lds_flush_f64(sSt + parity * 32 + lane, d.gn_stats + (int64_t)frame * 64 + 2 * g_first + lane);
     };
 
     // Step s: [barrier] request tile s + 3 | stores of output s - 3 | MFMAs of tile s with the epilogue of output s - 2 in their shadow |
@@ -263,10 +216,7 @@ __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, in
     for (int s = 0; s < nstep + 2; ++s) {
         lds_barrier();
         const bool work = s < nstep;                             // the last two iterations only drain the epilogue / store pipeline
-        if (staged < nstep) {
-            stage_next();
-            ++staged;
-        }
+        ring_step(staged, nstep, stage_next);
         // stores of output s - 3 (its cells were written during step s - 1), first half: out of LDS; its statistics to memory
         bf16x8 ov;
         const bool have_out = s >= 3;
@@ -299,22 +249,18 @@ __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, in
         const bool has_prev = tcur > 0, has_next = tcur + 1 < T;
         auto taps = [&](auto hp_, auto hn_) {
             constexpr bool HP = decltype(hp_)::value, HN = decltype(hn_)::value;
-            bf16x8 xq[kXD];
-#pragma unroll
-            for (int ks = 0; ks < kXD - 1; ++ks) xq[ks] = *(const bf16x8*)(xt + xlane[ks & 3] + (ks >> 2) * 256);
-#pragma unroll
-            for (int ks = 0; ks < kKS; ++ks) {
-                if (ks + kXD - 1 < kKS) xq[(ks + kXD - 1) % kXD] = *(const bf16x8*)(xt + xlane[(ks + kXD - 1) & 3] + ((ks + kXD - 1) >> 2) * 256);
-                __builtin_amdgcn_sched_barrier(0);
-                accc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1][ks], xq[ks % kXD], accc, 0, 0, 0);
-                if constexpr (HP) accp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[2][ks], xq[ks % kXD], accp, 0, 0, 0);      // x[t] is the t + 1 neighbour of output t - 1
-                if constexpr (HN) accn = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][ks], xq[ks % kXD], accn, 0, 0, 0);      // ... the t - 1 neighbour of output t + 1
-                __builtin_amdgcn_sched_barrier(0);
-                if (ks == 5 && have_fin) {
-                    finish(s & 1, accd, rc1, rc2, o_fin);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+            frag_pipeline<kKS, kXD>([&](int ks) { return swizzled_frag(xt, xlane, ks); },
+                                    [&](int ks, const bf16x8& x) {
+                                        accc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1][ks], x, accc, 0, 0, 0);
+                                        if constexpr (HP) accp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[2][ks], x, accp, 0, 0, 0);      // x[t] is the t + 1 neighbour of output t - 1
+                                        if constexpr (HN) accn = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][ks], x, accn, 0, 0, 0);      // ... the t - 1 neighbour of output t + 1
+                                    },
+                                    [&](int ks) {
+                                        if (ks == 5 && have_fin) {
+                                            finish(s & 1, accd, rc1, rc2, o_fin);
+                                            __builtin_amdgcn_sched_barrier(0);
+                                        }
+                                    });
         };
         if (live && work) {
             using Y = std::true_type;
@@ -326,10 +272,10 @@ __global__ __launch_bounds__(kNT, 1) void temp320s_kernel(const CcGemmDesc d, in
             if (have_fin) finish(s & 1, accd, rc1, rc2, o_fin);
         }
         // tile s + 1 must have landed (this wave's part): at most the loads of the tiles requested after it may be outstanding
-        if (dma_wave && s + 1 < nstep) wait_later(staged - (s + 2));
-        cx = cx == kRX - 1 ? 0 : cx + 1;
-        fr = fr == kRR - 1 ? 0 : fr + 1;
-        sr = sr == kRR - 1 ? 0 : sr + 1;
+        if (dma_wave && s + 1 < nstep) wait_later<kPerTile, kRX - 2>(staged - (s + 2));
+        ring_next<kRX>(cx);
+        ring_next<kRR>(fr);
+        ring_next<kRR>(sr);
         // rotate: output s - 1 is complete now (its last tap was this step's; at a column start it was complete already)
         accd = accp;
         accp = accc;
@@ -369,26 +315,16 @@ bool cc_temp320_applicable(const CcGemmDesc& d) {
 }
 
 int cc_temp320_launch(const CcGemmDesc& d, hipStream_t s) {
-    static unsigned long long attr_done[6] = {0, 0, 0, 0, 0, 0};
-    if (int rc = cc_max_dynamic_lds((const void*)temp320s_kernel<0, false>, kLds, &attr_done[0], "temp320s")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)temp320s_kernel<1, false>, kLds, &attr_done[1], "temp320s")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)temp320s_kernel<2, false>, kLds, &attr_done[2], "temp320s")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)temp320s_kernel<0, true>, kLds, &attr_done[3], "temp320s")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)temp320s_kernel<1, true>, kLds, &attr_done[4], "temp320s")) return rc;
-    if (int rc = cc_max_dynamic_lds((const void*)temp320s_kernel<2, true>, kLds, &attr_done[5], "temp320s")) return rc;
+    static unsigned long long attr_done = 0;
+    if (int rc = cc_family_dynamic_lds(kLds, &attr_done, "temp320s", temp320s_kernel<0, false>, temp320s_kernel<1, false>, temp320s_kernel<2, false>,
+                                       temp320s_kernel<0, true>, temp320s_kernel<1, true>, temp320s_kernel<2, true>))
+        return rc;
     cc_note_kernel("temp320s_kernel");
     const int nslice = (d.N + kSlice - 1) / kSlice;
     const int ncol_clip = d.HW / kP;
     const int nres = d.res2 ? 2 : d.res1 ? 1 : 0;
-    const dim3 grid(256), block(kNT);
-    if (d.group_bias) {
-        if (nres == 2) hipLaunchKernelGGL((temp320s_kernel<2, true>), grid, block, kLds, s, d, nslice, ncol_clip);
-        else if (nres == 1) hipLaunchKernelGGL((temp320s_kernel<1, true>), grid, block, kLds, s, d, nslice, ncol_clip);
-        else hipLaunchKernelGGL((temp320s_kernel<0, true>), grid, block, kLds, s, d, nslice, ncol_clip);
-    } else {
-        if (nres == 2) hipLaunchKernelGGL((temp320s_kernel<2, false>), grid, block, kLds, s, d, nslice, ncol_clip);
-        else if (nres == 1) hipLaunchKernelGGL((temp320s_kernel<1, false>), grid, block, kLds, s, d, nslice, ncol_clip);
-        else hipLaunchKernelGGL((temp320s_kernel<0, false>), grid, block, kLds, s, d, nslice, ncol_clip);
-    }
+    const auto arm = d.group_bias ? (nres == 2 ? temp320s_kernel<2, true> : nres == 1 ? temp320s_kernel<1, true> : temp320s_kernel<0, true>)
+                                  : (nres == 2 ? temp320s_kernel<2, false> : nres == 1 ? temp320s_kernel<1, false> : temp320s_kernel<0, false>);
+    hipLaunchKernelGGL(arm, dim3(256), dim3(kNT), kLds, s, d, nslice, ncol_clip);
     return cc_launch_status("temp320s_kernel");
 }

@@ -386,11 +386,10 @@ def test_g8_split_k():
 
 
 # ------------------------------------------------------------------------------------------ register-resident weights
-@pytest.mark.parametrize("m", [32, 130, 1000])
-@pytest.mark.parametrize("n", [320, 960])
+@pytest.mark.parametrize("n,m", [(n, m) for n in (320, 960) for m in (32, 130, 1000)] + [(1280, 16384)])
 def test_lin320(m, n):
     """tile 9: lin320_kernel (two K halves combined across wave sets; ragged M) and, for whole 32-pixel tiles, lin320s_kernel; plain,
-    and with a residual on strided operands."""
+    and with a residual on strided operands.  16384 x 1280: a workgroup walks 8 tiles, more than lin320s_kernel's seven ring slots."""
     _dev()
     from ccedit_amd import ops
     from ccedit_amd.packing import pack_weight
@@ -408,10 +407,11 @@ def test_lin320(m, n):
     assert bool((wide[:, :n] == 7.0).all()), "columns outside the output slice were written"
 
 
-@pytest.mark.parametrize("m,n", [(16, 640), (2064, 1920)])
+@pytest.mark.parametrize("m,n", [(16, 640), (2064, 1920), (4096, 1920)])
 def test_lin640s(m, n):
-    """tile 10: lin640s_kernel — one tile / ragged XCD ranges, the last 256-channel slice half empty; residual from a strided matrix,
-    and the LayerNorm row sums of what it wrote (row_sums), three launches alike."""
+    """tile 10: lin640s_kernel — one tile / ragged XCD ranges, the last 256-channel slice half empty / 8 tiles per workgroup (rings of
+    five and six slots wrap); residual from a strided matrix, and the LayerNorm row sums of what it wrote (row_sums), three launches
+    alike."""
     _dev()
     from ccedit_amd import ops
     from ccedit_amd.packing import pack_weight
@@ -429,10 +429,11 @@ def test_lin640s(m, n):
         _equal(ops.ln_sums_of(y), sums, "lin640s row_sums")
 
 
-@pytest.mark.parametrize("b_,t,cout,h,w", [(2, 5, 320, 8, 16), (3, 3, 64, 4, 4)])
+@pytest.mark.parametrize("b_,t,cout,h,w", [(2, 5, 320, 8, 16), (3, 3, 64, 4, 4), (2, 4, 1280, 24, 24)])
 def test_temp320s(b_, t, cout, h, w):
     """tile 14: temp320s_kernel — three rolling accumulators per pixel column, the missing MFMA at the clip ends and between clips,
-    128-channel slices (320 = 128 + 128 + 64), row bias + two residuals, statistics with 10-channel groups across the lanes' quads."""
+    128-channel slices (320 = 128 + 128 + 64), row bias + two residuals, statistics with 10-channel groups across the lanes' quads.
+    2 x 4 x 24 x 24 -> 1280: a workgroup walks 3 columns = 12 steps, more than the rings of six and nine slots hold."""
     _dev()
     from ccedit_amd import ops
     from ccedit_amd.packing import pack_weight
