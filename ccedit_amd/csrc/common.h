@@ -237,3 +237,11 @@ int cc_png_adler(const uint8_t* filtered, uint32_t* partials, uint32_t* adler, i
 int cc_pngdec_inflate(const uint8_t* data, int64_t data_bytes, const int64_t* streams, uint8_t* filtered, int32_t* status, int32_t N, int32_t H,
                       int32_t W, hipStream_t s);
 int cc_pngdec_unfilter(const uint8_t* filtered, uint8_t* rgb, int32_t* status, int32_t N, int32_t H, int32_t W, hipStream_t s);
+
+// GIF decoding launchers (gifdec.hip); entry points and argument checks in core.cpp
+int cc_gifdec_codes(const uint8_t* data, int64_t data_bytes, const int64_t* desc, int32_t* parent, int32_t* len, int32_t* off, uint8_t* first,
+                    uint8_t* last, int64_t total_codes, int32_t* ncodes, int32_t* status, int32_t N, hipStream_t s);
+int cc_gifdec_pixels(const int64_t* desc, const int32_t* parent, const int32_t* len, const int32_t* off, const uint8_t* last, int64_t total_codes,
+                     const int32_t* ncodes, uint8_t* planes, int64_t plane_bytes, int32_t N, int64_t max_codes, hipStream_t s);
+int cc_gifdec_compose(const uint8_t* data, int64_t data_bytes, const int64_t* desc, const uint8_t* planes, int64_t plane_bytes, uint8_t* canvas,
+                      uint8_t* out, int32_t* status, int32_t N, int32_t n_out, int32_t H, int32_t W, hipStream_t s);

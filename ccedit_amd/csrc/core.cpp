@@ -555,3 +555,50 @@ extern "C" int ccedit_pngdec_unfilter(const void* filtered, void* rgb, int32_t* 
     CC_CHECK_ARG(((uintptr_t)status & 3) == 0, "ccedit_pngdec_unfilter: status must be 4-byte aligned");
     return cc_pngdec_unfilter((const uint8_t*)filtered, (uint8_t*)rgb, status, N, H, W, (hipStream_t)stream);
 }
+
+// ---- GIF decoding (kernels and launchers: gifdec.hip).  Geometry and buffers are checked here, before any HIP call; the descriptors
+// are device data and are checked against these sizes by the kernels.
+static const int64_t kGifdecMaxCodes = (int64_t)1 << 31;
+
+static int gifdec_common_ok(const char* fn, int32_t N, int64_t total_codes) {
+    CC_CHECK_ARG(N >= 1 && N <= kGifMaxFrames, "%s: N=%d images (1 ... 65535)", fn, N);
+    CC_CHECK_ARG(total_codes >= 1 && total_codes < kGifdecMaxCodes, "%s: total_codes=%lld (1 ... 2^31 - 1)", fn, (long long)total_codes);
+    return 0;
+}
+
+extern "C" int ccedit_gifdec_codes(const void* data, int64_t data_bytes, const int64_t* desc, int32_t* parent, int32_t* len, int32_t* off,
+                                   void* first, void* last, int64_t total_codes, int32_t* ncodes, int32_t* status, int32_t N, void* stream) {
+    CC_CHECK_ARG(data && desc && parent && len && off && first && last && ncodes && status, "ccedit_gifdec_codes: null pointer");
+    if (int rc = gifdec_common_ok("ccedit_gifdec_codes", N, total_codes)) return rc;
+    CC_CHECK_ARG(data_bytes >= 1 && data_bytes < kPixelMax * 4, "ccedit_gifdec_codes: data_bytes=%lld (1 ... 2^33)", (long long)data_bytes);
+    CC_CHECK_ARG(((uintptr_t)desc & 7) == 0 && (((uintptr_t)parent | (uintptr_t)len | (uintptr_t)off | (uintptr_t)ncodes | (uintptr_t)status) & 3) == 0,
+                 "ccedit_gifdec_codes: desc must be 8-byte aligned, parent, len, off, ncodes and status 4-byte");
+    return cc_gifdec_codes((const uint8_t*)data, data_bytes, desc, parent, len, off, (uint8_t*)first, (uint8_t*)last, total_codes, ncodes, status, N,
+                           (hipStream_t)stream);
+}
+
+extern "C" int ccedit_gifdec_pixels(const int64_t* desc, const int32_t* parent, const int32_t* len, const int32_t* off, const void* last,
+                                    int64_t total_codes, const int32_t* ncodes, void* planes, int64_t plane_bytes, int32_t N, int64_t max_codes,
+                                    void* stream) {
+    CC_CHECK_ARG(desc && parent && len && off && last && ncodes && planes, "ccedit_gifdec_pixels: null pointer");
+    if (int rc = gifdec_common_ok("ccedit_gifdec_pixels", N, total_codes)) return rc;
+    CC_CHECK_ARG(plane_bytes >= 1 && plane_bytes < kPixelMax * 4, "ccedit_gifdec_pixels: plane_bytes=%lld (1 ... 2^33)", (long long)plane_bytes);
+    CC_CHECK_ARG(max_codes >= 1 && max_codes <= kGifMaxPixels + 1 && max_codes <= total_codes,
+                 "ccedit_gifdec_pixels: max_codes=%lld (1 ... 2^24 + 1, at most total_codes: the largest dCodeCap)", (long long)max_codes);
+    CC_CHECK_ARG(((uintptr_t)desc & 7) == 0 && (((uintptr_t)parent | (uintptr_t)len | (uintptr_t)off | (uintptr_t)ncodes) & 3) == 0,
+                 "ccedit_gifdec_pixels: desc must be 8-byte aligned, parent, len, off and ncodes 4-byte");
+    return cc_gifdec_pixels(desc, parent, len, off, (const uint8_t*)last, total_codes, ncodes, (uint8_t*)planes, plane_bytes, N, max_codes,
+                            (hipStream_t)stream);
+}
+
+extern "C" int ccedit_gifdec_compose(const void* data, int64_t data_bytes, const int64_t* desc, const void* planes, int64_t plane_bytes, void* canvas,
+                                     void* out, int32_t* status, int32_t N, int32_t n_out, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(data && desc && planes && canvas && status, "ccedit_gifdec_compose: null pointer (data, desc, planes, canvas and status are required)");
+    CC_CHECK_ARG(n_out >= 0 && n_out <= N && (out || n_out == 0), "ccedit_gifdec_compose: n_out=%d outputs (0 ... N, with a buffer)", n_out);
+    if (int rc = gif_shape_ok("ccedit_gifdec_compose", N, H, W)) return rc;
+    CC_CHECK_ARG(data_bytes >= 1 && data_bytes < kPixelMax * 4, "ccedit_gifdec_compose: data_bytes=%lld (1 ... 2^33)", (long long)data_bytes);
+    CC_CHECK_ARG(plane_bytes >= 1 && plane_bytes < kPixelMax * 4, "ccedit_gifdec_compose: plane_bytes=%lld (1 ... 2^33)", (long long)plane_bytes);
+    CC_CHECK_ARG(((uintptr_t)desc & 7) == 0 && ((uintptr_t)status & 3) == 0, "ccedit_gifdec_compose: desc must be 8-byte aligned, status 4-byte");
+    return cc_gifdec_compose((const uint8_t*)data, data_bytes, desc, (const uint8_t*)planes, plane_bytes, (uint8_t*)canvas, (uint8_t*)out, status, N,
+                             n_out, H, W, (hipStream_t)stream);
+}

@@ -1464,3 +1464,74 @@ def pngdec_unfilter(filtered: torch.Tensor, h: int, w: int):
     hip.check(hip.lib().ccedit_pngdec_unfilter(filtered.data_ptr(), out.data_ptr(), status.data_ptr(), n, int(h), int(w), _stream()),
               "ccedit_pngdec_unfilter")
     return out, status
+
+
+# ------------------------------------------------------------------------------------------
+# GIF decoding (csrc/gifdec.hip; the container parser, the descriptors and the frame loop: ccedit_amd/gifdec.py)
+# ------------------------------------------------------------------------------------------
+def _gifdec_desc(desc: torch.Tensor, name: str) -> int:
+    from . import gifdec
+    if (desc.dtype != torch.int64 or not desc.is_cuda or not desc.is_contiguous() or desc.dim() != 2 or desc.shape[1] != gifdec.DESC_WORDS
+            or desc.shape[0] < 1):
+        raise ValueError(f"{name}: desc: expected a contiguous cuda int64 tensor (N, {gifdec.DESC_WORDS}), N >= 1, got {desc.dtype} {tuple(desc.shape)}")
+    return desc.shape[0]
+
+
+def gifdec_codes(data: torch.Tensor, desc: torch.Tensor, total_codes: int):
+    """The LZW streams in `data` (uint8 (B,)) of the images described by `desc` (int64 (N, 16): gifdec.py describe) -> (table int32
+    (3, total_codes): parent, len, off of every data code; ends uint8 (2, total_codes): first and last byte of its string; ncodes int32
+    (N,); status int32 (N, 2): code (0: decoded) and bit position).  No pixel is touched."""
+    _chk_u8(data, "gifdec_codes: data", 1)
+    n = _gifdec_desc(desc, "gifdec_codes")
+    if int(total_codes) < 1 or data.numel() < 1:
+        raise ValueError(f"gifdec_codes: total_codes={total_codes} (>= 1: the sum of the descriptors' capacities), {data.numel()} bytes of data")
+    table = torch.empty((3, int(total_codes)), dtype=torch.int32, device=data.device)
+    ends = torch.empty((2, int(total_codes)), dtype=torch.uint8, device=data.device)
+    ncodes = torch.empty((n,), dtype=torch.int32, device=data.device)
+    status = torch.empty((n, 2), dtype=torch.int32, device=data.device)
+    hip.check(hip.lib().ccedit_gifdec_codes(data.data_ptr(), data.numel(), desc.data_ptr(), table[0].data_ptr(), table[1].data_ptr(),
+                                            table[2].data_ptr(), ends[0].data_ptr(), ends[1].data_ptr(), int(total_codes), ncodes.data_ptr(),
+                                            status.data_ptr(), n, _stream()), "ccedit_gifdec_codes")
+    return table, ends, ncodes, status
+
+
+def gifdec_pixels(desc: torch.Tensor, table: torch.Tensor, ends: torch.Tensor, ncodes: torch.Tensor, plane_bytes: int, max_codes: int) -> torch.Tensor:
+    """The code table of gifdec_codes -> planes uint8 (plane_bytes,): every image's indices in stream order at its descriptor's plane
+    offset.  max_codes: the largest capacity among the descriptors."""
+    n = _gifdec_desc(desc, "gifdec_pixels")
+    _chk_u8(ends, "gifdec_pixels: ends", 2)
+    if table.dtype != torch.int32 or not table.is_cuda or not table.is_contiguous() or table.dim() != 2 or table.shape[0] != 3 \
+            or tuple(ends.shape) != (2, table.shape[1]) or table.shape[1] < 1:
+        raise ValueError(f"gifdec_pixels: expected table int32 (3, C) and ends uint8 (2, C), got {table.dtype} {tuple(table.shape)}, {tuple(ends.shape)}")
+    _chk_i32(ncodes, "gifdec_pixels: ncodes", (n,))
+    total = table.shape[1]
+    if int(plane_bytes) < 1 or not 1 <= int(max_codes) <= total:
+        raise ValueError(f"gifdec_pixels: plane_bytes={plane_bytes} (>= 1), max_codes={max_codes} (1 ... {total})")
+    planes = torch.empty((int(plane_bytes),), dtype=torch.uint8, device=desc.device)
+    hip.check(hip.lib().ccedit_gifdec_pixels(desc.data_ptr(), table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), ends[1].data_ptr(),
+                                             total, ncodes.data_ptr(), planes.data_ptr(), int(plane_bytes), n, int(max_codes), _stream()),
+              "ccedit_gifdec_pixels")
+    return planes
+
+
+def gifdec_compose(data: torch.Tensor, desc: torch.Tensor, planes: torch.Tensor, canvas: torch.Tensor, n_out: int):
+    """The images' index planes composited in order on `canvas` (uint8 (H, W, 3), updated in place) -> (uint8 (n_out, H, W, 3): the images
+    whose descriptor names an output; status int32 (N, 2): code (0, or 5: an index beyond the palette) and the offset in the plane)."""
+    from . import gif
+    _chk_u8(data, "gifdec_compose: data", 1)
+    _chk_u8(planes, "gifdec_compose: planes", 1)
+    _chk_u8(canvas, "gifdec_compose: canvas", 3)
+    n = _gifdec_desc(desc, "gifdec_compose")
+    h, w = canvas.shape[0], canvas.shape[1]
+    gif.check_size(h, w)
+    if canvas.shape[2] != 3 or not 0 <= int(n_out) <= n or data.numel() < 1 or planes.numel() < 1:
+        raise ValueError(f"gifdec_compose: canvas {tuple(canvas.shape)} (H, W, 3), n_out={n_out} (0 ... {n}), {data.numel()} bytes of data, "
+                         f"{planes.numel()} of planes")
+    out = torch.empty((int(n_out), h, w, 3), dtype=torch.uint8, device=canvas.device)
+    status = torch.empty((n, 2), dtype=torch.int32, device=canvas.device)
+    status[:, 0] = 0
+    status[:, 1] = 0x7fffffff
+    hip.check(hip.lib().ccedit_gifdec_compose(data.data_ptr(), data.numel(), desc.data_ptr(), planes.data_ptr(), planes.numel(), canvas.data_ptr(),
+                                              out.data_ptr() if n_out else None, status.data_ptr(), n, int(n_out), h, w, _stream()),
+              "ccedit_gifdec_compose")
+    return out, status

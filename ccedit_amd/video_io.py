@@ -5,7 +5,8 @@ here which way a path goes; a further format is one entry here, and its codec mo
 Sources.  A clip goes ONE way as a whole: every file (every frame of an .avi, the whole animated PNG) is parsed before anything is
 decoded, and what the parser declines sends the whole clip to Pillow on the host, with one line on stderr.  Image files, GIFs and the
 frames of a Motion-JPEG .avi or an animated .png are Pillow's on the host route; with a device, JPEG and PNG are decoded THERE
-(jpegdec.py, pngdec.py: the same bytes as Pillow's).  mp4 needs a codec library (decord / cv2 / imageio-ffmpeg) that is not installed.
+(jpegdec.py, pngdec.py: the same bytes as Pillow's), and a .gif is when the caller opts in (gif_decoder="device": gifdec.py, a kind's
+`opt_in` decoders).  mp4 needs a codec library (decord / cv2 / imageio-ffmpeg) that is not installed.
 
 Sinks.  `--save_type gif` (Pillow's writer, or the device's with `--gif_encoder device`), `mjpeg` and `png`: a numbered file in a
 folder of its own; the device writers take uint8 frames where they are, or upload a host array once."""
@@ -19,7 +20,7 @@ from typing import Any, Callable, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import gif, jpegdec, mjpeg, png, pngdec
+from . import gif, gifdec, jpegdec, mjpeg, png, pngdec
 from .codec_common import duration_ms
 
 
@@ -74,10 +75,19 @@ def _parse_apng(path: str):
     return data, pngdec.parse(data)
 
 
+def _parse_gif(path: str):
+    with open(path, "rb") as f:
+        data = f.read()
+    return data, gifdec.parse(data)
+
+
 JPEG = Decoder(jpegdec, (".jpg", ".jpeg"), jpegdec.JpegUnsupported, lambda info: info.ncomp == 3, _jpeg_status, mjpeg.parse_avi,
                lambda path, parsed, device, select: mjpeg.decode_avi_device(path, device, select, parsed))
 PNG = Decoder(pngdec, (".png",), ValueError, None, _png_status, _parse_apng,           # (PngUnsupported is a ValueError: any declines)
               lambda path, parsed, device, select: pngdec.decode_apng(parsed[0], device, select, info=parsed[1]))
+# (no image files: a directory of .gif stills is not a video of GIF frames.  GifUnsupported is a ValueError: any declines)
+GIFDEC = Decoder(gifdec, (), ValueError, None, _png_status, _parse_gif,
+                 lambda path, parsed, device, select: gifdec.decode_gif(parsed[0], device, select, info=parsed[1]))
 
 
 def _declined(dec: Decoder, text: str) -> None:
@@ -146,6 +156,7 @@ class Kind(NamedTuple):
     pil: Callable[..., Tuple[int, Callable]]      # (path, each) -> (n, pick): pick(i) = each(frame i as Pillow decodes it); files are opened when picked
     u8: Optional[Callable[[str], np.ndarray]]     # a video in one file: all frames by Pillow -> uint8 (N, h, w, 3) on the host
     device: Tuple[Decoder, ...]                   # who decodes it on the device, asked in this order
+    opt_in: Tuple[Decoder, ...] = ()              # who decodes it on the device when the caller asks for it (gif_decoder="device"), after `device`
 
 
 def is_apng(path: str) -> bool:
@@ -192,7 +203,7 @@ def _sequence_u8(path: str) -> np.ndarray:
 
 # (.gif and .avi match case-sensitively, .png and the image files of the decoders in lower case: as ever)
 FILES = Kind("directory", os.path.isdir, lambda p: len(os.listdir(p)), _pil_files, None, (JPEG, PNG))      # JPEG is asked before PNG
-GIF = Kind(".gif", lambda p: p.endswith(".gif"), _pil_count, _pil_sequence, _sequence_u8, ())
+GIF = Kind(".gif", lambda p: p.endswith(".gif"), _pil_count, _pil_sequence, _sequence_u8, (), (GIFDEC,))
 AVI = Kind(".avi", lambda p: p.endswith(".avi"), lambda p: len(mjpeg.read_avi(p)[0]), _pil_avi, mjpeg.decode_avi_u8, (JPEG,))
 APNG = Kind("animated .png", is_apng, _pil_count, _pil_sequence, _sequence_u8, (PNG,))
 KINDS = (FILES, GIF, AVI, APNG)
@@ -216,6 +227,12 @@ def kind_of(path: str, mp4_hint: bool = True, missing_ok: bool = False) -> Optio
 # sinks
 # ------------------------------------------------------------------------------------------
 GIF_ENCODERS = ("pillow", "device")
+
+
+def decoders_of(kind: Kind, gif_decoder: str = "pillow") -> Tuple[Decoder, ...]:
+    """Who decodes a source of `kind` on the device: its `device` decoders, and with gif_decoder="device" its opt-in ones behind them
+    (anything else: the route as it always was)."""
+    return kind.device + kind.opt_in if gif_decoder == "device" else kind.device
 
 
 def to_device(frames) -> torch.Tensor:

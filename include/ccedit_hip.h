@@ -713,6 +713,40 @@ int ccedit_pngdec_inflate(const void* data, int64_t data_bytes, const int64_t* s
                           int32_t W, void* stream);
 int ccedit_pngdec_unfilter(const void* filtered, void* rgb, int32_t* status, int32_t N, int32_t H, int32_t W, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GIF decoding (added without an ABI bump: three new functions, CCEDIT_ABI_VERSION stays 12).  The images of one .gif -> uint8 frames
+ * [n_out][H][W][3] on the device, composited on a canvas [H][W][3] that the caller carries from call to call; only the compressed bytes,
+ * the palettes and one descriptor per image go up.  ccedit_amd/gifdec.py: the container parser and the frame loop.  Kernels:
+ * csrc/gifdec.hip, csrc/gifdec_core.h.  H and W 1 ... 65535 with H * W <= 2^24; N <= 65535.
+ *
+ * data: uint8 [data_bytes]: every image's LZW stream (its sub-blocks concatenated) and every palette (RGB triples).
+ * desc: int64 [N][16] on the device, per image: 0 x, 1 y, 2 w, 3 h (its rectangle on the canvas), 4 interlace flag, 5 transparent
+ *   index or -1, 6 byte offset of its palette in data, 7 palette entries (1 ... 256), 8 LZW minimum code size (2 ... 8), 9 and 10 byte
+ *   offset and length of its stream in data, 11 and 12 offset and capacity of its part of the code table (capacity >= min(w * h,
+ *   8 * length / (min code size + 1)) + 1), 13 byte offset of its w * h indices in planes, 14 the output it is written to or -1,
+ *   15 zero.  A descriptor that points outside a buffer or the canvas gives code 6 and is not used.
+ * status: int32 [N][2] per call: a code (0: fine; the codes are gifdec_core.h's Status) and a position.
+ *
+ * ccedit_gifdec_codes: the bit streams -> the code table, without touching a pixel.  For data code k of an image (Clear and EOI are not
+ *   counted): parent[k] (a code of the same image, -1: a literal), len[k] (its string's length), first[k] / last[k] (its string's first
+ *   and last byte), off[k] (its pixel offset in stream order); ncodes[n]: the codes of image n.  Decoding stops at EOI or once w * h
+ *   pixels are reached (the code that crosses the end keeps its full length).  Codes: 1 a code above the next free entry, 2 a first code
+ *   after Clear that is not a literal, 3 the stream ends before w * h pixels, 4 minimum code size outside 2 ... 8; position: the bit
+ *   position of the code.  One wave per image.
+ * ccedit_gifdec_pixels: the code table -> planes uint8 [plane_bytes]: every image's indices in stream order.  One lane per code, one hop
+ *   up the chain of parents per pixel.  max_codes: the largest capacity among the descriptors.
+ * ccedit_gifdec_compose: for every canvas pixel, the images in order: inside the rectangle the index (an interlaced image's rows in
+ *   four-pass order) and, unless it is the transparent index, its palette entry; an image with output >= 0 is written to
+ *   out[output]; the canvas is read at the start and written at the end.  Code 5: an index at or beyond the palette's entries (the
+ *   pixel is left as it was), position: the lowest such offset in the image's plane; the caller sets status to (0, INT32_MAX) before.
+ */
+int ccedit_gifdec_codes(const void* data, int64_t data_bytes, const int64_t* desc, int32_t* parent, int32_t* len, int32_t* off, void* first,
+                        void* last, int64_t total_codes, int32_t* ncodes, int32_t* status, int32_t N, void* stream);
+int ccedit_gifdec_pixels(const int64_t* desc, const int32_t* parent, const int32_t* len, const int32_t* off, const void* last, int64_t total_codes,
+                         const int32_t* ncodes, void* planes, int64_t plane_bytes, int32_t N, int64_t max_codes, void* stream);
+int ccedit_gifdec_compose(const void* data, int64_t data_bytes, const int64_t* desc, const void* planes, int64_t plane_bytes, void* canvas, void* out,
+                          int32_t* status, int32_t N, int32_t n_out, int32_t H, int32_t W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

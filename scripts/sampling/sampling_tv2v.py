@@ -38,6 +38,9 @@ csrc/propagate.hip), written to <save_path>/<basemodel>/result_full/gif/ (or mjp
 csrc/png.hip); any H and W; an animated .png is also a video SOURCE wherever a .gif is.
 `--gif_encoder device` (with --save_type gif) quantises and LZW-codes every .gif a job writes on the GPU (ccedit_amd/gif.py, csrc/gif.hip);
 the default, `pillow`, writes them on the host as before.
+`--gif_decoder device` (with --gpu_io) decodes every .gif SOURCE on the GPU (ccedit_amd/gifdec.py, csrc/gifdec.hip: a table of LZW codes, one
+lane per code, frames composited on the device; the same bytes as Pillow's); a file outside its subset, and the default `pillow`, go
+through Pillow on the host as before.  Masks stay Pillow's.
 """
 from __future__ import annotations
 
@@ -141,6 +144,11 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                         "pillow (default): Pillow on the host, byte for byte as before.  device: colour quantisation (Wu's quantiser, a local "
                         "palette of 256 colours per frame) and LZW coding on the GPU (ccedit_amd/gif.py, csrc/gif.hip); with --gpu_io the "
                         "uint8 frames never leave the device, only palettes and LZW bytes come back.  An error with any other --save_type")
+    p.add_argument("--gif_decoder", type=str, default="pillow", choices=["pillow", "device"],
+                   help="(not in the reference script) who decodes a .gif source (--video_path and its kin; --propagate's source frames).  "
+                        "pillow (default): Pillow on the host, as before.  device: LZW decoding and frame compositing on the GPU "
+                        "(ccedit_amd/gifdec.py, csrc/gifdec.hip), the same bytes as Pillow's; only the compressed bytes go up; a file outside "
+                        "the decoder's subset goes through Pillow with one line on stderr.  Needs --gpu_io; masks stay Pillow's")
 
 
 def make_parser() -> argparse.ArgumentParser:
@@ -168,6 +176,8 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
                     f"--save_type png (got {args.save_type})")
     if getattr(args, "gif_encoder", "pillow") == "device" and args.save_type != "gif":
         p.error(f"--gif_encoder device encodes the files of --save_type gif (got --save_type {args.save_type})")
+    if getattr(args, "gif_decoder", "pillow") == "device" and not getattr(args, "gpu_io", False):
+        p.error("--gif_decoder device decodes .gif sources where --gpu_io keeps the frames: add --gpu_io")
     if not 1 <= getattr(args, "video_quality", 90) <= 100:
         p.error(f"--video_quality must be in 1 ... 100 (got {args.video_quality})")
     if args.save_type == "mjpeg" and (args.H % 16 or args.W % 16):
@@ -232,7 +242,7 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
     edited = ops.frames_to_u8(samples.float().contiguous(), rounding=False, unit_range=False)           # (bs, T, H, W, 3)
     paths = []
     for b, v in enumerate(cvideos):
-        source = load_video_frames_u8(resolve_video(v), (args.H, args.W), dev)
+        source = load_video_frames_u8(resolve_video(v), (args.H, args.W), dev, **_gif_decoder(args))
         n_all = source.shape[0]
         masks = None
         if args.inpainting_mode and args.mask_composite:
@@ -303,7 +313,7 @@ def conditioning_tensors(args, g: torch.Generator, need_frames: bool, need_ref: 
             cond["cond_img"] = torch.rand(1, 3, args.H, args.W, generator=g) * 2 - 1
     if args.video_path:           # sampling_tv2v.py:314-331: keyframes (T,3,H,W) -> (1,3,T,H,W)
         from scripts.sampling.util import load_video_keyframes
-        kf = load_video_keyframes(args.video_path, args.original_fps, args.target_fps, T, (args.H, args.W), **_io_device(args))
+        kf = load_video_keyframes(args.video_path, args.original_fps, args.target_fps, T, (args.H, args.W), **_io_device(args, video=True))
         cond["keyframes"] = kf.permute(1, 0, 2, 3)[None].contiguous()
     if need_ref and getattr(args, "reference_path", ""):
         from scripts.sampling.util import load_img
@@ -314,9 +324,17 @@ def conditioning_tensors(args, g: torch.Generator, need_frames: bool, need_ref: 
     return cond
 
 
-def _io_device(args) -> dict:
-    """device= of load_img / load_video_keyframes: the current GPU under --gpu_io, else nothing (the host route, unchanged)."""
-    return {"device": torch.device("cuda", torch.cuda.current_device())} if getattr(args, "gpu_io", False) else {}
+def _gif_decoder(args) -> dict:
+    """gif_decoder= of the video loaders: given only with --gif_decoder device (else the loaders' default, the route as before)."""
+    return {"gif_decoder": "device"} if getattr(args, "gif_decoder", "pillow") == "device" else {}
+
+
+def _io_device(args, video: bool = False) -> dict:
+    """device= of load_img / load_video_keyframes / load_video_mask: the current GPU under --gpu_io, else nothing (the host route,
+    unchanged).  video: a loader of video frames, which takes --gif_decoder through the same dict (masks and images do not)."""
+    if not getattr(args, "gpu_io", False):
+        return {}
+    return dict({"device": torch.device("cuda", torch.cuda.current_device())}, **(_gif_decoder(args) if video else {}))
 
 
 def text_inputs(cond, dev, args=None):
@@ -671,7 +689,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
             bs = min(len(cprompts), batch_size)
             print(f"\nProgress: {idx} / {len(prompts_chunk)}. ")
             try:
-                kfs = [load_video_keyframes(resolve_video(v), args.original_fps, args.target_fps, T, (H, W), **_io_device(args)).permute(1, 0, 2, 3)[None]
+                kfs = [load_video_keyframes(resolve_video(v), args.original_fps, args.target_fps, T, (H, W), **_io_device(args, video=True)).permute(1, 0, 2, 3)[None]
                        for v in cvideos]
             except Exception as e:                                       # (:312-330: a clip that does not load is reported and skipped)
                 print(f"Error when loading video from  {cvideos}: {type(e).__name__}: {e}")

@@ -6,6 +6,7 @@ controlnet_img and the anchor cross-frame attention) and `--prior_type {video, r
 (sampling_tv2v_ref.py:415-437).  Config: configs/inference_ccedit/keyframe_ref_cp_no2ndca_add_cfca_depthzoe.yaml.
 `--cond_path` additionally holds `cond_img`.  Job mode (lists, `--videos_directory`, `--json_path` + `--videos_root` + `--reference_root` with
 one `output-<Target Prompt>.png` per job, `--batch_size`, `--auto_ref_editing`, which raises as in the reference): see sampling_tv2v.py.
+`--gif_decoder device` (with --gpu_io) decodes .gif sources on the GPU, as there (ccedit_amd/gifdec.py); the default is Pillow on the host.
 """
 from __future__ import annotations
 

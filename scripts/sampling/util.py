@@ -303,10 +303,11 @@ def _files_u8(paths, device, what: str):
     return on_device if on_device is not None else _upload([_decode_rgb_u8(p) for p in paths], device)
 
 
-def _clip_u8(kind, video_path: str, device, select=None):
+def _clip_u8(kind, video_path: str, device, select=None, gif_decoder: str = "pillow"):
     """A video in one file (all frames, or those at select(number of frames)) -> [uint8 (N, h, w, 3) on `device`]: decoded there where a
-    decoder takes the whole clip, else Pillow's frames, selected before the upload."""
-    on_device = video_io.clip_u8_device(kind.device, video_path, device, select)
+    decoder takes the whole clip, else Pillow's frames, selected before the upload.  gif_decoder="device": the kind's opt-in decoders
+    (a .gif: ccedit_amd/gifdec.py) are asked too."""
+    on_device = video_io.clip_u8_device(video_io.decoders_of(kind, gif_decoder), video_path, device, select)
     if on_device is not None:
         return [on_device]
     frames = kind.u8(video_path)
@@ -356,13 +357,15 @@ def keyframe_indices(num_allframes: int, original_fps: int, target_fps: int, num
     return np.asarray(idx[:num_keyframes])
 
 
-def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
+def load_video_frames_u8(video_path: str, size: tuple, device, gif_decoder: str = "pillow") -> torch.Tensor:
     """(not in the reference) ALL frames of what load_video_keyframes reads -> uint8 (F, H, W, 3) on `device` at size = (H, W): the
     source side of --propagate.  JPEG and PNG sources (a directory of such files, the frames of an .avi or of an animated .png) are
     decoded on the device (ccedit_amd/jpegdec.py, pngdec.py: only the compressed bytes go up; Pillow's bytes exactly); everything else,
     and a clip the device decoder declines, is decoded by Pillow on the host and uploaded.  The frames reach the output size by the
     routes of the keyframes — image files by Pillow's 8-bit bicubic (ops.resize_u8_pil), the frames of a video in one file by the fp32
-    bicubic of F.interpolate and then the nearest byte (ops.resize_bicubic, ops.frames_to_u8 with rounding)."""
+    bicubic of F.interpolate and then the nearest byte (ops.resize_bicubic, ops.frames_to_u8 with rounding).
+    gif_decoder="device": a .gif is decoded on the device too (ccedit_amd/gifdec.py: Pillow's bytes exactly; a file outside its subset
+    goes through Pillow with one line on stderr); "pillow" (the default): a .gif is Pillow's, as before."""
     from ccedit_amd import ops
     assert device is not None and size and len(size) == 2, "load_video_frames_u8 works on a device, size should be (H, W)"
     kind = video_io.kind_of(video_path)
@@ -370,18 +373,20 @@ def load_video_frames_u8(video_path: str, size: tuple, device) -> torch.Tensor:
         groups = _files_u8([os.path.join(video_path, f) for f in sorted(os.listdir(video_path))], device, video_path)
         out = [ops.resize_u8_pil(g.contiguous(), size) for g in groups]
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
-    x = ops.resize_bicubic(_u8_to_float(_clip_u8(kind, video_path, device), None).contiguous(), size)      # (F, 3, h, w) in [-1, 1] -> (F, 3, H, W)
+    x = ops.resize_bicubic(_u8_to_float(_clip_u8(kind, video_path, device, gif_decoder=gif_decoder), None).contiguous(), size)      # (F, 3, h, w) in [-1, 1] -> (F, 3, H, W)
     return ops.frames_to_u8(x.permute(1, 0, 2, 3)[None].contiguous(), rounding=True)[0]
 
 
 def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None,
-                         device=None) -> torch.Tensor:
+                         device=None, gif_decoder: str = "pillow") -> torch.Tensor:
     """util.py:689-762: directory of frame images, a .gif, a Motion-JPEG .avi or an animated .png -> keyframes (T, 3, H, W) in [-1, 1].
     device=None: everything on the host, as the reference.  With a device, JPEG and PNG sources (such files, the frames of an .avi or
     of an animated .png) are decoded there (ccedit_amd/jpegdec.py, pngdec.py: only the compressed bytes go up, the frames are Pillow's
     byte for byte); everything else, and a clip the device decoder declines, is decoded by Pillow on the host and uploaded once as
     uint8.  Either way the keyframes are resized / scaled by the kernels of ccedit_amd/csrc/pixel.hip: image files exactly as on the
-    host (Pillow's 8-bit bicubic), the frames of a video in one file by the fp32 bicubic of F.interpolate (equal to fp32 rounding)."""
+    host (Pillow's 8-bit bicubic), the frames of a video in one file by the fp32 bicubic of F.interpolate (equal to fp32 rounding).
+    gif_decoder="device" (with a device; not in the reference): a .gif is decoded on the device as well (ccedit_amd/gifdec.py: the same
+    bytes as Pillow's); "pillow" (the default) is the route as before."""
     if device is not None and size:
         assert len(size) == 2, "size should be (H, W)"
     select = lambda n: keyframe_indices(n, original_fps, target_fps, num_keyframes)      # noqa: E731
@@ -394,7 +399,7 @@ def load_video_keyframes(video_path: str, original_fps: int, target_fps: int, nu
         return torch.cat([load_img(p, size) for p in paths], dim=0)
     if device is not None:
         from ccedit_amd import ops
-        x = _u8_to_float(_clip_u8(kind, video_path, device, select), None).contiguous()       # uint8 -> x / 255 * 2 - 1, (T, 3, h, w)
+        x = _u8_to_float(_clip_u8(kind, video_path, device, select, gif_decoder), None).contiguous()       # uint8 -> x / 255 * 2 - 1, (T, 3, h, w)
         return ops.resize_bicubic(x, size) if size else x
     frames = torch.from_numpy(kind.u8(video_path)).permute(0, 3, 1, 2).float() / 255.0
     frames = frames[select(frames.shape[0])]
