@@ -177,6 +177,7 @@ int cc_mask_latent(const uint8_t* mask_px, uint8_t* mask_lat, int64_t N, int32_t
 int cc_mask_inpaint_blend(const float* x, const float* x0, const float* noise, const uint8_t* mask, float* y, int32_t B, int32_t C, int64_t P,
                           float sigma, float s, hipStream_t st);
 int cc_mask_composite(const float* result, const float* original, const uint8_t* mask_px, float* out, int32_t B, int64_t P, hipStream_t st);
+int cc_mask_dilate(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int64_t N, int32_t H, int32_t W, int32_t R, int32_t invert, hipStream_t s);
 
 // Window launchers (window.hip); entry points and argument checks in core.cpp
 int cc_window_gather(const float* x, float* xw, const int32_t* starts, int32_t W, int32_t BC, int32_t N, int32_t T, int64_t P, hipStream_t s);
@@ -191,6 +192,11 @@ int cc_prop_warp(const uint8_t* src, const int32_t* vec, const int32_t* pairs, i
                  int32_t W, int32_t C, hipStream_t s);
 int cc_prop_blend(const uint8_t* wE, const uint8_t* wY, const uint8_t* lum, const int32_t* pairs, const int32_t* gtab, const uint8_t* rgb,
                   const uint8_t* mask, uint8_t* out, int32_t NF, int32_t F, int32_t H, int32_t W, hipStream_t s);
+
+// Mask-tracking launchers (masktrack.hip); entry points and argument checks in core.cpp
+int cc_masktrack_select(const uint8_t* lum, const int32_t* pairs, const int32_t* vec, uint32_t* out, int32_t P, int32_t F, int32_t H, int32_t W,
+                        hipStream_t s);
+int cc_masktrack_step(const uint32_t* v, const uint32_t* r, const uint8_t* mg, uint8_t* mf, int32_t H, int32_t W, int32_t limit, hipStream_t s);
 
 // Motion-JPEG launchers (mjpeg.hip); entry points and argument checks in core.cpp
 int64_t cc_mjpeg_segment_bytes(int32_t W);

@@ -194,6 +194,17 @@ extern "C" int ccedit_mask_composite(const float* result, const float* original,
     return cc_mask_composite(result, original, (const uint8_t*)mask_px, out, B, P, (hipStream_t)stream);
 }
 
+extern "C" int ccedit_mask_dilate(const void* src, void* tmp, void* dst, int64_t N, int32_t H, int32_t W, int32_t radius, int32_t invert, void* stream) {
+    CC_CHECK_ARG(src && dst && (tmp || radius == 0), "ccedit_mask_dilate: null pointer (tmp alone may be null, with radius 0)");
+    CC_CHECK_ARG(N > 0 && H > 0 && W > 0 && W % 4 == 0, "ccedit_mask_dilate: N=%lld masks of %dx%d (positive, W a multiple of 4)", (long long)N, H, W);
+    CC_CHECK_ARG(N < kPixelMax && N * H * W < kPixelMax * 4, "ccedit_mask_dilate: more than 2^33 pixels in one call");
+    CC_CHECK_ARG(radius >= 0 && radius <= 32, "ccedit_mask_dilate: radius=%d (0 ... 32)", radius);
+    CC_CHECK_ARG(invert == 0 || invert == 1, "ccedit_mask_dilate: invert=%d (0 or 1)", invert);
+    CC_CHECK_ARG((((uintptr_t)src | (uintptr_t)tmp | (uintptr_t)dst) & 3) == 0, "ccedit_mask_dilate: src, tmp and dst must be 4-byte aligned");
+    CC_CHECK_ARG(src != dst && tmp != dst && src != tmp, "ccedit_mask_dilate: src, tmp and dst must be different buffers");
+    return cc_mask_dilate((const uint8_t*)src, (uint8_t*)tmp, (uint8_t*)dst, N, H, W, radius, invert, (hipStream_t)stream);
+}
+
 // ---- windows of a long clip (kernels and launchers: window.hip).  Everything the host can see is checked here, before any HIP call;
 // the device tables (starts, coef, the pointer table) are held inside their tensors by the kernels themselves.
 static int window_shape_ok(const char* fn, int32_t W, int32_t B, int32_t C, int32_t N, int32_t T, int64_t P) {
@@ -269,6 +280,27 @@ extern "C" int ccedit_prop_blend(const void* warped_rgb, const void* warped_luma
                  "ccedit_prop_blend: warped_rgb, out, rgb and mask must be 4-byte aligned");
     return cc_prop_blend((const uint8_t*)warped_rgb, (const uint8_t*)warped_luma, (const uint8_t*)pyr, pairs, gtab, (const uint8_t*)rgb,
                          (const uint8_t*)mask, (uint8_t*)out, NF, F, H, W, (hipStream_t)stream);
+}
+
+// ---- mask tracking (kernels and launchers: masktrack.hip).  The pair list and the block vectors are device data, held in range by
+// the kernel; the per-pixel vectors of a step are any int16 pairs (the looked-up position is clamped into the frame).
+extern "C" int ccedit_masktrack_select(const void* pyr, const int32_t* pairs, const int32_t* vec, void* vsel, int32_t P, int32_t F, int32_t H,
+                                       int32_t W, void* stream) {
+    CC_CHECK_ARG(pyr && pairs && vec && vsel, "ccedit_masktrack_select: null pointer");
+    if (int rc = prop_shape_ok("ccedit_masktrack_select", P, F, H, W)) return rc;
+    CC_CHECK_ARG(((uintptr_t)vsel & 3) == 0, "ccedit_masktrack_select: vsel must be 4-byte aligned");
+    return cc_masktrack_select((const uint8_t*)pyr, pairs, vec, (uint32_t*)vsel, P, F, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_masktrack_step(const void* v, const void* r, const void* mask_g, void* mask_f, int32_t H, int32_t W, int32_t limit,
+                                     void* stream) {
+    CC_CHECK_ARG(v && r && mask_g && mask_f, "ccedit_masktrack_step: null pointer");
+    if (int rc = prop_shape_ok("ccedit_masktrack_step", 1, 1, H, W)) return rc;
+    CC_CHECK_ARG(limit >= 0, "ccedit_masktrack_step: limit=%d (not negative)", limit);
+    CC_CHECK_ARG(((uintptr_t)v & 15) == 0 && (((uintptr_t)r | (uintptr_t)mask_f) & 3) == 0,
+                 "ccedit_masktrack_step: v must be 16-byte, r and mask_f 4-byte aligned");
+    CC_CHECK_ARG(mask_g != mask_f, "ccedit_masktrack_step: mask_f is gathered from mask_g: two buffers");
+    return cc_masktrack_step((const uint32_t*)v, (const uint32_t*)r, (const uint8_t*)mask_g, (uint8_t*)mask_f, H, W, limit, (hipStream_t)stream);
 }
 
 // ---- Motion-JPEG (kernels and launchers: mjpeg.hip).  Everything the host can see is checked here, before any HIP call; the device

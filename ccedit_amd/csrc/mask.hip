@@ -3,8 +3,9 @@
 //   mask_latent           pixel mask -> latent mask: an 8 x 8 cell is 1 when MORE than 32 of its pixels are set
 //   inpaint_blend         the per-step re-injection y = m ? x : (x0 + noise * sigma) / s, mask broadcast over the channels
 //   mask_composite        out = m ? result : original on the decoded frames
+//   mask_dilate           pixel mask -> its (2R + 1)^2 square maximum in two separable passes, optionally inverted (255 - m) on the way out
 // Convention everywhere: set (pixel masks: byte >= 128, latent masks: byte != 0) = edit, clear = keep the original.
-// All four move bytes: grid-stride loops over a grid of at most kMaxBlocks workgroups, 16-byte accesses where sizes and alignment
+// All of them move bytes: grid-stride loops over a grid of at most kMaxBlocks workgroups, 16-byte accesses where sizes and alignment
 // allow and a one-element variant otherwise; the mask is never expanded to the tensors' shape.  The file is compiled with
 // -ffp-contract=off: inpaint_blend is one fp32 multiply, one add and one correctly rounded divide, in the reference's order.
 // The argument checks live with the exported entry points in core.cpp; the launchers below trust their arguments.
@@ -166,11 +167,60 @@ void launch_select(const float* x, const float* a, const float* noise, const uin
                            sigma, s);
 }
 
+// ---- dilation: one pass of the separable (2R + 1)^2 square maximum over uint8 masks [N][H][W], the window clipped at the border;
+// one thread per four consecutive pixels of a row (W % 4 == 0).  VERT = false: along x, true: along y; `inv`: 255 - m on the way out.
+template <bool VERT>
+__global__ __launch_bounds__(kThreads) void mask_dilate_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t N, int H, int W,
+                                                               int R, uint32_t inv) {
+    const int G = W / 4;
+    const int64_t total = N * H * G;
+    for (int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kThreads) {
+        const int64_t ny = idx / G;
+        const int x0 = (int)(idx - ny * G) * 4;
+        const int64_t n = ny / H;
+        const int y = (int)(ny - n * H);
+        const uint8_t* img = src + n * H * W;
+        uint32_t m[4] = {0, 0, 0, 0};
+        if constexpr (VERT) {
+            const int lo = y - R < 0 ? 0 : y - R, hi = y + R > H - 1 ? H - 1 : y + R;
+            for (int yy = lo; yy <= hi; ++yy) {
+                const uint32_t d = *(const uint32_t*)(img + (int64_t)yy * W + x0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t b = (d >> (8 * j)) & 255u;
+                    m[j] = b > m[j] ? b : m[j];
+                }
+            }
+        } else {
+            const uint8_t* row = img + (int64_t)y * W;
+            const int lo = x0 - R < 0 ? 0 : x0 - R, hi = x0 + 3 + R > W - 1 ? W - 1 : x0 + 3 + R;
+            for (int xx = lo; xx <= hi; ++xx) {
+                const uint32_t b = row[xx];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int dx = xx - (x0 + j);
+                    if (dx >= -R && dx <= R) m[j] = b > m[j] ? b : m[j];
+                }
+            }
+        }
+        *(uint32_t*)(dst + ny * W + x0) = (m[0] | (m[1] << 8) | (m[2] << 16) | (m[3] << 24)) ^ inv;
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
 // launchers (arguments validated by the entry points in core.cpp)
 // ------------------------------------------------------------------------------------------
+int cc_mask_dilate(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int64_t N, int32_t H, int32_t W, int32_t R, int32_t invert, hipStream_t s) {
+    const unsigned grid = grid_for(N * H * (W / 4));
+    const uint32_t inv = invert ? 0xffffffffu : 0u;                        // 255 - m of every byte
+    if (R > 0)
+        hipLaunchKernelGGL(mask_dilate_kernel<false>, dim3(grid), dim3(kThreads), 0, s, src, tmp, N, H, W, R, 0u);
+    hipLaunchKernelGGL(mask_dilate_kernel<true>, dim3(grid), dim3(kThreads), 0, s, R > 0 ? tmp : src, dst, N, H, W, R, inv);
+    return cc_launch_status("mask_dilate");
+}
+
 int cc_mask_resize_nearest(const uint8_t* src, uint8_t* dst, const int32_t* ytab, const int32_t* xtab, int32_t N, int32_t Hs, int32_t Ws,
                            int32_t H, int32_t W, hipStream_t s) {
     if (W % 4 == 0 && aligned(dst, 4))

@@ -161,6 +161,10 @@ _SIGS = {
                                    C.c_int32, C.c_void_p]),
     "ccedit_prop_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    # mask tracking (csrc/masktrack.hip; dilate: csrc/mask.hip): added within ABI 12, nothing existing changed
+    "ccedit_masktrack_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_masktrack_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_mask_dilate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     # Motion-JPEG output (csrc/mjpeg.hip): added within ABI 12, nothing existing changed
     "ccedit_mjpeg_segment_bytes": (C.c_int64, [C.c_int32]),
     "ccedit_mjpeg_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

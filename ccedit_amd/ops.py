@@ -1063,6 +1063,60 @@ def prop_blend(warped_rgb: torch.Tensor, warped_luma: torch.Tensor, pyr: torch.T
 
 
 # ------------------------------------------------------------------------------------------
+# Mask tracking (csrc/masktrack.hip, ccedit_mask_dilate in csrc/mask.hip; constants, pair lists and the clip loop: ccedit_amd/masktrack.py)
+# ------------------------------------------------------------------------------------------
+def _chk_i16(t: torch.Tensor, name: str, shape):
+    if t.dtype != torch.int16 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected a contiguous cuda int16 tensor {tuple(shape)}, got {t.dtype} {t.device} {tuple(t.shape)}")
+
+
+def masktrack_select(pyr: torch.Tensor, pairs: torch.Tensor, vec: torch.Tensor, frames: int, h: int, w: int) -> torch.Tensor:
+    """All pairs (P, 4) of the call: per pixel the best of the 3 x 3 neighbouring blocks' level-0 vectors `vec` (P, h / 8, w / 8, 2) by the
+    5 x 5 box sum of absolute luma differences -> int16 (P, h, w, 2) = (dy, dx)."""
+    _chk_u8(pyr, "masktrack_select", 1)
+    assert pyr.numel() == prop_pyramid_bytes(frames, h, w), f"masktrack_select: a pyramid of {frames} frames {h}x{w} has {prop_pyramid_bytes(frames, h, w)} bytes"
+    p = pairs.shape[0]
+    _chk_i32(pairs, "masktrack_select: pairs", (p, 4))
+    _chk_i32(vec, "masktrack_select: vec", (p, h // 8, w // 8, 2))
+    out = torch.empty((p, h, w, 2), dtype=torch.int16, device=pyr.device)
+    hip.check(hip.lib().ccedit_masktrack_select(pyr.data_ptr(), pairs.data_ptr(), vec.data_ptr(), out.data_ptr(), p, frames, h, w, _stream()),
+              "ccedit_masktrack_select")
+    return out
+
+
+def masktrack_step(v: torch.Tensor, r: torch.Tensor, mask_g: torch.Tensor, limit: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One frame of the chain: per-pixel vectors v (f -> g) and r (g -> f), int16 (H, W, 2), and g's mask uint8 (H, W) -> f's mask:
+    mask_g at q = clamp(p + v(p)), or 0 where |v(p) + r(q)|_1 > limit.  `out`: where to write it (a frame of the clip's masks)."""
+    _chk_u8(mask_g, "masktrack_step: mask_g", 2)
+    h, w = mask_g.shape
+    _chk_i16(v, "masktrack_step: v", (h, w, 2))
+    _chk_i16(r, "masktrack_step: r", (h, w, 2))
+    y = torch.empty((h, w), dtype=torch.uint8, device=mask_g.device) if out is None else out
+    _chk_u8(y, "masktrack_step: out", 2)
+    assert tuple(y.shape) == (h, w), f"masktrack_step: out {tuple(y.shape)} for a mask of {h}x{w}"
+    hip.check(hip.lib().ccedit_masktrack_step(v.data_ptr(), r.data_ptr(), mask_g.data_ptr(), y.data_ptr(), h, w, int(limit), _stream()),
+              "ccedit_masktrack_step")
+    return y
+
+
+def mask_dilate(mask: torch.Tensor, radius: int, invert: bool = False) -> torch.Tensor:
+    """uint8 masks (..., H, W) -> their (2 radius + 1)^2 square maximum (window clipped at the border), then 255 - m with `invert`.
+    radius 0 without invert is the identity: the mask itself comes back and nothing is launched."""
+    if not 0 <= int(radius) <= 32:
+        raise ValueError(f"mask_dilate: radius={radius} must be in 0 ... 32")
+    if int(radius) == 0 and not invert:
+        return mask
+    _chk_u8(mask, "mask_dilate", mask.dim())
+    assert mask.dim() >= 2 and mask.shape[-1] % 4 == 0, f"mask_dilate: masks (..., H, W) with W a multiple of 4, got {tuple(mask.shape)}"
+    h, w = mask.shape[-2:]
+    out = torch.empty_like(mask)
+    tmp = torch.empty_like(mask) if radius else None
+    hip.check(hip.lib().ccedit_mask_dilate(mask.data_ptr(), None if tmp is None else tmp.data_ptr(), out.data_ptr(), mask.numel() // (h * w), h, w,
+                                           int(radius), int(bool(invert)), _stream()), "ccedit_mask_dilate")
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # Motion-JPEG output (csrc/mjpeg.hip; constants, header, container and the frame loop: ccedit_amd/mjpeg.py)
 # ------------------------------------------------------------------------------------------
 def mjpeg_segment_bytes(w: int) -> int:

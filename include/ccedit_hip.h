@@ -541,6 +541,29 @@ int ccedit_prop_blend(const void* warped_rgb, const void* warped_luma, const voi
                       const void* mask, void* out, int32_t NF, int32_t F, int32_t H, int32_t W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mask tracking (added without an ABI bump: three new functions, CCEDIT_ABI_VERSION stays 12).  `--mask_track`: an edit mask painted
+ * on one source frame is carried to every frame of the clip along the source's motion (ccedit_amd/masktrack.py: constants, pair lists,
+ * track_clip).  Kernels: csrc/masktrack.hip, and ccedit_mask_dilate in csrc/mask.hip.  Everything is integer arithmetic on bytes and
+ * equals tests/_masktrack_numpy.py bit for bit.  Frames, pyramids and pairs are those of "Propagation" above (of a pair row only
+ * (f, k) are read).  A PER-PIXEL VECTOR is two int16 (dy, dx), [H][W][2].
+ *
+ * ccedit_masktrack_select: all P pairs in one launch.  pyr as written by ccedit_prop_pyramid (level 0 is read), vec: the level-0 block
+ *   vectors int32 [P][H / 8][W / 8][2] of ccedit_prop_match, each component clamped into +-64 before use.  Per pixel p of block
+ *   (y >> 3, x >> 3): the candidates are the vectors of the 3 x 3 neighbouring blocks (indices clamped) in the order (dby, dbx) = (0,0)
+ *   (-1,0) (0,-1) (0,1) (1,0) (-1,-1) (-1,1) (1,-1) (1,1); S_c(p) = the 5 x 5 edge-replicated box sum of d_c = |Y_f(p') - Y_k(clamp(p' + c))|;
+ *   the candidate of minimum S_c * 16 + order is written to vsel [P][H][W][2] (int16, 4-byte aligned).
+ * ccedit_masktrack_step: one frame of the chain.  v, r: per-pixel vectors [H][W][2] of the pairs (f, g) and (g, f); q = clamp(p + v(p));
+ *   mask_f(p) = mask_g(q), or 0 where |v_y(p) + r_y(q)| + |v_x(p) + r_x(q)| > limit.  v 16-byte, r and mask_f 4-byte aligned.
+ * ccedit_mask_dilate: uint8 masks [N][H][W] (W % 4 == 0, 4-byte aligned) -> dst: the (2 radius + 1)^2 square maximum, the window clipped
+ *   at the border (radius 0 ... 32; two separable passes through tmp [N][H][W], which may be null with radius 0), then, with invert = 1,
+ *   255 - m.  src, tmp and dst are three different buffers.
+ */
+int ccedit_masktrack_select(const void* pyr, const int32_t* pairs, const int32_t* vec, void* vsel, int32_t P, int32_t F, int32_t H, int32_t W,
+                            void* stream);
+int ccedit_masktrack_step(const void* v, const void* r, const void* mask_g, void* mask_f, int32_t H, int32_t W, int32_t limit, void* stream);
+int ccedit_mask_dilate(const void* src, void* tmp, void* dst, int64_t N, int32_t H, int32_t W, int32_t radius, int32_t invert, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG (added without an ABI bump: five new functions, CCEDIT_ABI_VERSION stays 12).  `--save_type mjpeg`: uint8 frames
  * [N][H][W][3] on the device (what ccedit_frames_to_u8 writes) -> one baseline JPEG per frame (ITU-T T.81: sequential DCT, 8 bit,
  * YCbCr 4:2:0, MCU 16 x 16, restart interval = one MCU row = one SEGMENT), ccedit_amd/mjpeg.py: constants, header, container.

@@ -23,6 +23,9 @@ MiDaS / Zoe recipe), prompts through `--tokenizer_path`; `--synthetic` substitut
 `--mask_path`, `--mask_root/<video name>.{png,gif}` | `<video name>/`, or `<video stem>.mask.png | .mask.gif | .mask/`; white = edit, black = keep —
 through the samplers' sample_inpainting and the kernels of ccedit_amd/csrc/mask.hip; `--mask_composite` puts the original pixels back
 outside the mask after decoding; the mask as applied is saved under <save_path>/<basemodel>/mask/.
+`--mask_track` (with ONE mask image, painted on source frame `--mask_frame`) gives every source frame its own mask, tracked along the
+source's motion on the device (ccedit_amd/masktrack.py, csrc/masktrack.hip); `--mask_dilate R` and `--mask_invert` apply afterwards,
+to untracked masks too.
 `--window_frames T` (with `--window_overlap O`, default T // 2) lifts the limit of one window of keyframes: with `--num_keyframes N` > T the
 clip is covered by overlapping windows of T frames, each evaluated by the unchanged network at every sampler evaluation and fused into
 one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everything else — inpainting, SDEdit, the prior mix,
@@ -120,6 +123,15 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="directory of masks of a multi-clip invocation: <video name>.png, <video name>.gif or <video name>/")
     p.add_argument("--mask_composite", action="store_true",
                    help="with --inpainting_mode: put the original pixels back outside the mask after decoding (the VAE round trip is lossy)")
+    p.add_argument("--mask_track", action="store_true",
+                   help="(not in the reference script) the mask is ONE image painted on source frame --mask_frame; every frame of the video "
+                        "gets its own mask, tracked forwards and backwards along the source's motion on the device (ccedit_amd/masktrack.py, "
+                        "csrc/masktrack.hip).  Needs --inpainting_mode and --H, --W multiples of 64")
+    p.add_argument("--mask_frame", type=int, default=0, help="with --mask_track: the source frame the mask was painted on")
+    p.add_argument("--mask_dilate", type=int, default=0,
+                   help="grow every mask (tracked or not) by this many pixels, 0 ... 32: a (2R + 1) x (2R + 1) square maximum, after tracking")
+    p.add_argument("--mask_invert", action="store_true",
+                   help="swap edit and keep (255 - mask), after tracking and --mask_dilate: with --mask_track, edit everything but the subject")
     p.add_argument("--window_frames", type=int, default=0,
                    help="(not in the reference script) keyframes per network evaluation; with --num_keyframes above it the clip is covered "
                         "by overlapping windows of this many frames whose denoised latents are fused at every sampler evaluation "
@@ -182,6 +194,7 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error(f"--video_quality must be in 1 ... 100 (got {args.video_quality})")
     if args.save_type == "mjpeg" and (args.H % 16 or args.W % 16):
         p.error(f"--save_type mjpeg codes 16 x 16 MCUs: --H and --W must be multiples of 16 (got {args.H}x{args.W})")
+    check_mask_options(args)                 # (--mask_track and its kin: ValueError, here and again where the masks are made)
 
 
 def windowing(args) -> bool:
@@ -237,7 +250,7 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
     from ccedit_amd import ops
     from ccedit_amd.propagate import propagate_clip
     from scripts.sampling import util
-    from scripts.sampling.util import keyframe_indices, load_video_frames_u8, load_video_mask
+    from scripts.sampling.util import keyframe_indices, load_video_frames_u8
     writer, options = video_writer(args)
     edited = ops.frames_to_u8(samples.float().contiguous(), rounding=False, unit_range=False)           # (bs, T, H, W, 3)
     paths = []
@@ -246,8 +259,7 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
         n_all = source.shape[0]
         masks = None
         if args.inpainting_mode and args.mask_composite:
-            masks = load_video_mask(find_mask(args, v), args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all,
-                                    device=dev, all_frames=True).contiguous()
+            masks = all_frame_masks(args, v, n_all, dev)
         idx = keyframe_indices(n_all, args.original_fps, args.target_fps, args.num_keyframes)
         full = propagate_clip(source, idx, edited[b], masks=masks)
         frames = full.contiguous() if writer.on_device else full.cpu().numpy()      # (a device writer encodes the frames where they are)
@@ -397,19 +409,84 @@ def find_mask(args, video_path: str):
     return None
 
 
+def check_mask_options(args) -> None:
+    """--mask_track, --mask_frame, --mask_dilate, --mask_invert: what can be refused before a video is opened (ValueError, with what to do)."""
+    from ccedit_amd import masktrack
+    masktrack.check_dilate(getattr(args, "mask_dilate", 0))
+    if not getattr(args, "mask_track", False):
+        return
+    if not args.inpainting_mode:
+        raise ValueError("--mask_track tracks the edit mask of --inpainting_mode: give both")
+    masktrack.check_size(args.H, args.W, "--mask_track")
+    if getattr(args, "mask_frame", 0) < 0:
+        raise ValueError(f"--mask_frame {args.mask_frame} is outside the video: frames count from 0")
+
+
+def finish_masks(args, masks):
+    """--mask_dilate, then --mask_invert, on the masks of a clip (tracked or not); at the defaults the masks as they are, nothing launched."""
+    from ccedit_amd import masktrack
+    radius, invert = getattr(args, "mask_dilate", 0), getattr(args, "mask_invert", False)
+    if not radius and not invert:
+        return masks
+    return masktrack.finish(masks.cuda() if not masks.is_cuda else masks, radius, invert)
+
+
+_TRACKED = {}           # the last clip's tracked masks: --propagate asks for the clip clip_masks has just tracked
+
+
+def tracked_masks(args, video_path: str, mask_path: str, dev):
+    """--mask_track: the ONE mask image `mask_path`, painted on frame --mask_frame, followed through every source frame of the clip
+    -> uint8 (F, H, W) on `dev`.  The frames come the way --propagate's do (load_video_frames_u8: the device decoders where they apply)."""
+    from ccedit_amd import masktrack, video_io
+    from scripts.sampling.util import load_video_frames_u8, load_video_mask
+    check_mask_options(args)
+    if video_io.kind_of(mask_path, missing_ok=True) is not None:
+        raise ValueError(f"--mask_track follows ONE mask image through the clip, but {mask_path} is a mask sequence: give the mask of frame "
+                         "--mask_frame as one image, or drop --mask_track to use the sequence as it is")
+    if not video_path:
+        raise ValueError("--mask_track follows the mask along the source video: give --video_path")
+    video = resolve_video(video_path)
+    key = (video, mask_path, args.mask_frame, args.H, args.W, str(dev), getattr(args, "gif_decoder", "pillow"))
+    if key not in _TRACKED:
+        source = load_video_frames_u8(video, (args.H, args.W), dev, **_gif_decoder(args))
+        masktrack.chain(source.shape[0], args.mask_frame)                                  # (--mask_frame outside the video: refused here)
+        anchor = load_video_mask(mask_path, args.original_fps, args.target_fps, 1, (args.H, args.W), device=dev)[0]
+        _TRACKED.clear()
+        _TRACKED[key] = masktrack.track_clip(source, anchor.contiguous(), args.mask_frame)
+    return _TRACKED[key]
+
+
 def clip_masks(args, video_paths, dev):
     """The pixel masks of a chunk: uint8 (bs, T, H, W) on `dev`, 0 = keep / 255 = edit, resized like the frames' geometry (nearest).
-    A clip without a mask is an error (NotImplementedError, as the flag alone always was)."""
-    from scripts.sampling.util import count_video_frames, load_video_mask
+    A clip without a mask is an error (NotImplementedError, as the flag alone always was).  --mask_track: the keyframes' masks are the
+    tracked masks at keyframe_indices; --mask_dilate / --mask_invert apply last."""
+    from scripts.sampling.util import count_video_frames, keyframe_indices, load_video_mask
     out = []
     for v in video_paths:
         mpath = find_mask(args, v)
         if mpath is None:
             raise NotImplementedError(f"no mask for {v or 'the clip'}: {NO_MASK}")
+        if getattr(args, "mask_track", False):
+            full = tracked_masks(args, v, mpath, dev)
+            idx = keyframe_indices(full.shape[0], args.original_fps, args.target_fps, args.num_keyframes)
+            out.append(finish_masks(args, full[torch.from_numpy(idx.astype("int64")).to(dev)]))
+            continue
         video = resolve_video(v) if v else ""
         n_all = count_video_frames(video) if video and (os.path.isdir(video) or video.endswith((".gif", ".avi"))) else None
-        out.append(load_video_mask(mpath, args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all, **_io_device(args)))
+        out.append(finish_masks(args, load_video_mask(mpath, args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all,
+                                                      **_io_device(args))))
     return torch.stack([m.to(dev) for m in out], dim=0).contiguous()
+
+
+def all_frame_masks(args, video_path: str, n_all: int, dev):
+    """clip_masks' sibling for --propagate --mask_composite: the masks of ALL n_all source frames of one clip, uint8 (n_all, H, W) on `dev`
+    — the user's sequence, the one image repeated, or with --mask_track the tracked masks; --mask_dilate / --mask_invert apply last."""
+    from scripts.sampling.util import load_video_mask
+    mpath = find_mask(args, video_path)
+    if getattr(args, "mask_track", False):
+        return finish_masks(args, tracked_masks(args, video_path, mpath, dev)).contiguous()
+    return finish_masks(args, load_video_mask(mpath, args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all,
+                                              device=dev, all_frames=True)).contiguous()
 
 
 def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None):
