@@ -230,6 +230,34 @@ extern "C" int ccedit_window_fuse(const void* yw, float* out, const int32_t* sta
     return cc_window_fuse((const float* const*)yw, out, starts, coef, W, B * C, N, T, P, (hipStream_t)stream);
 }
 
+// ---- tiles of a large frame (kernels and launchers: tile.hip).  Everything the host can see is checked here, before any HIP call;
+// the device tables (starts, coef, the pointer table) are held inside their tensors by the kernels themselves.
+static int tile_shape_ok(const char* fn, int32_t T, int64_t planes, int32_t h, int32_t w, int32_t th, int32_t tw) {
+    CC_CHECK_ARG(T >= 1 && T <= 64 && planes > 0 && th >= 1 && tw >= 1 && h >= th && w >= tw,
+                 "%s: T=%d (1 ... 64) tiles of %dx%d over frames of %dx%d (h >= th >= 1, w >= tw >= 1), planes=%lld (positive)", fn, T, th, tw, h, w,
+                 (long long)planes);
+    CC_CHECK_ARG(planes < kPixelMax && planes * h * w < kPixelMax * 4 && (int64_t)T * planes * th * tw < kPixelMax * 4,
+                 "%s: more than 2^33 elements in one call (T=%d planes=%lld %dx%d, tiles of %dx%d)", fn, T, (long long)planes, h, w, th, tw);
+    return CCEDIT_OK;
+}
+
+extern "C" int ccedit_tile_gather(const float* x, float* xt, const int32_t* starts, int32_t T, int64_t planes, int32_t h, int32_t w, int32_t th,
+                                  int32_t tw, void* stream) {
+    CC_CHECK_ARG(x && xt && starts, "ccedit_tile_gather: null pointer");
+    CC_CHECK_ARG(((uintptr_t)x & 3) == 0 && ((uintptr_t)xt & 3) == 0 && ((uintptr_t)starts & 3) == 0, "ccedit_tile_gather: pointers must be 4-byte aligned");
+    if (int rc = tile_shape_ok("ccedit_tile_gather", T, planes, h, w, th, tw)) return rc;
+    return cc_tile_gather(x, xt, starts, T, planes, h, w, th, tw, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_tile_fuse(const void* yt, float* out, const int32_t* starts, const float* coef, int32_t T, int64_t planes, int32_t h, int32_t w,
+                                int32_t th, int32_t tw, void* stream) {
+    CC_CHECK_ARG(yt && out && starts && coef, "ccedit_tile_fuse: null pointer");
+    CC_CHECK_ARG(((uintptr_t)yt & 7) == 0, "ccedit_tile_fuse: the table of tile pointers must be 8-byte aligned");
+    CC_CHECK_ARG(((uintptr_t)out & 3) == 0 && ((uintptr_t)coef & 3) == 0 && ((uintptr_t)starts & 3) == 0, "ccedit_tile_fuse: pointers must be 4-byte aligned");
+    if (int rc = tile_shape_ok("ccedit_tile_fuse", T, planes, h, w, th, tw)) return rc;
+    return cc_tile_fuse((const float* const*)yt, out, starts, coef, T, planes, h, w, th, tw, (hipStream_t)stream);
+}
+
 // ---- propagation of edited keyframes to every source frame (kernels and launchers: propagate.hip).  Everything the host can see is
 // checked here, before any HIP call; the device tables (pairs, rank, g, the block vectors) are held in range by the kernels themselves.
 static int prop_shape_ok(const char* fn, int32_t P, int32_t F, int32_t H, int32_t W) {

@@ -153,6 +153,11 @@ _SIGS = {
                                        C.c_void_p]),
     "ccedit_window_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int64, C.c_void_p]),
+    # tiles of a large frame (csrc/tile.hip): added within ABI 12, nothing existing changed
+    "ccedit_tile_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_void_p]),
+    "ccedit_tile_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_void_p]),
     # propagation of edited keyframes (csrc/propagate.hip): added within ABI 12, nothing existing changed
     "ccedit_prop_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ccedit_prop_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -968,6 +968,54 @@ def window_fuse(ys, starts: torch.Tensor, coef: torch.Tensor, frames: int, out: 
 
 
 # ------------------------------------------------------------------------------------------
+# Tiles of a large frame (csrc/tile.hip): gather T tiles of th x tw, cross-fade their outputs back (ccedit_amd/tiles.py)
+# ------------------------------------------------------------------------------------------
+def _chk_tile_starts(starts: torch.Tensor, name: str):
+    if starts.dtype != torch.int32 or not starts.is_cuda or not starts.is_contiguous() or starts.dim() != 2 or starts.shape[1] != 2:
+        raise ValueError(f"{name}: `starts` must be a contiguous cuda int32 (tiles, 2) table of (row, column), got {starts.dtype} "
+                         f"{starts.device} {tuple(starts.shape)}")
+
+
+def tile_gather(x: torch.Tensor, starts: torch.Tensor, tile_h: int, tile_w: int) -> torch.Tensor:
+    """(B, C, N, h, w) fp32 -> (T, B, C, N, th, tw): tile i is x[..., sy:sy + th, sx:sx + tw] with (sy, sx) = starts[i], all tiles in one
+    launch, a bit copy.  `starts`: int32 (T, 2) on the device (tiles.plan2d); the result's [i] are contiguous (B, C, N, th, tw) tensors."""
+    _chk_latent(x, "tile_gather")
+    _chk_tile_starts(starts, "tile_gather")
+    b, c, n, h, w = x.shape
+    nt, th, tw = starts.shape[0], int(tile_h), int(tile_w)
+    xt = torch.empty((nt, b, c, n, max(th, 0), max(tw, 0)), dtype=torch.float32, device=x.device)
+    _launch_mem("tile_gather", 8.0 * xt.numel(), lambda: hip.check(hip.lib().ccedit_tile_gather(
+        x.data_ptr(), xt.data_ptr(), starts.data_ptr(), nt, b * c * n, h, w, th, tw, _stream()), "ccedit_tile_gather"), (nt, b, c, n, th, tw))
+    return xt
+
+
+def tile_fuse(ys, starts: torch.Tensor, coef: torch.Tensor, height: int, width: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The T tiles' outputs `ys` (each (B, C, N, th, tw) fp32, read in place through a device table of their addresses) -> (B, C, N, h, w):
+    out[..., y, x] = sum over the tiles covering (y, x), ascending, of coef[i, y - sy_i, x - sx_i] * ys[i][..., y - sy_i, x - sx_i] — product
+    first, then multiply and add per further term, bit-equal to that loop in numpy float32.  `coef`: fp32 (T, th, tw) on the device."""
+    nt, h, w = len(ys), int(height), int(width)
+    if nt < 1:
+        raise ValueError("tile_fuse: no tiles")
+    _chk_tile_starts(starts, "tile_fuse")
+    for y in ys:
+        _chk_latent(y, "tile_fuse")
+        if y.shape != ys[0].shape or y.device != ys[0].device:
+            raise ValueError(f"tile_fuse: tiles of different shapes or devices: {tuple(y.shape)} and {tuple(ys[0].shape)}")
+    b, c, n, th, tw = ys[0].shape
+    if starts.shape[0] != nt or coef.dtype != torch.float32 or not coef.is_cuda or not coef.is_contiguous() or tuple(coef.shape) != (nt, th, tw):
+        raise ValueError(f"tile_fuse: {nt} tiles of {th}x{tw} need starts ({nt}, 2) and a contiguous cuda fp32 coef ({nt}, {th}, {tw}); got "
+                         f"{tuple(starts.shape)} and {coef.dtype} {tuple(coef.shape)}")
+    y = torch.empty((b, c, n, max(h, 0), max(w, 0)), dtype=torch.float32, device=ys[0].device) if out is None else out
+    assert y.dtype == torch.float32 and y.is_contiguous() and tuple(y.shape) == (b, c, n, h, w)
+    # the T addresses change with every evaluation: 8 T bytes through pinned memory, not blocking (see window_fuse)
+    table = torch.tensor([v.data_ptr() for v in ys], dtype=torch.int64).pin_memory().to(y.device, non_blocking=True)
+    _launch_mem("tile_fuse", 4.0 * (nt * ys[0].numel() + coef.numel() + y.numel()), lambda: hip.check(hip.lib().ccedit_tile_fuse(
+        table.data_ptr(), y.data_ptr(), starts.data_ptr(), coef.data_ptr(), nt, b * c * n, h, w, th, tw, _stream()), "ccedit_tile_fuse"),
+        (nt, b, c, n, h, w))
+    return y
+
+
+# ------------------------------------------------------------------------------------------
 # Propagation of edited keyframes to every source frame (csrc/propagate.hip; plan, tables and the clip loop: ccedit_amd/propagate.py)
 # ------------------------------------------------------------------------------------------
 def _chk_u8(t: torch.Tensor, name: str, dims: int):

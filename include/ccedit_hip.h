@@ -506,6 +506,31 @@ int ccedit_window_fuse(const void* yw, float* out, const int32_t* starts, const 
                        int32_t T, int64_t P, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tiles (added without an ABI bump: two new functions, CCEDIT_ABI_VERSION stays 12).  A frame larger than the size the network is
+ * built for is covered by T overlapping tiles of th x tw latent pixels; at every network evaluation each tile goes through the
+ * network at its usual shape and the tiles' denoised latents are cross-faded into one latent of h x w (ccedit_amd/tiles.py: plan2d,
+ * TiledDenoiser; `--tile_h`, `--tile_w`, `--tile_overlap`).  Kernels: csrc/tile.hip.  Latents are fp32 [planes][rows][columns],
+ * planes = B C N.  `starts` (int32 [T][2]: row, column of each tile's first element; y major, x minor, ascending) and `coef` (fp32
+ * [T][th][tw], per latent pixel summing to 1 over the tiles that cover it) are device tables uploaded once per clip; the kernels
+ * clamp a start into 0 ... h - th / 0 ... w - tw and write 0 for an element no tile covers, so no table can take an access outside
+ * its tensor.  All pointers are device pointers, 4-byte aligned; T is 1 ... 64, h >= th >= 1, w >= tw >= 1.
+ *
+ * ccedit_tile_gather: xt[t][p][i][j] = x[p][sy_t + i][sx_t + j]; x is [planes][h][w], xt [T][planes][th][tw] (tile t is the contiguous
+ *   tensor xt + t planes th tw); all T tiles in one launch, a bit copy.
+ * ccedit_tile_fuse: out[p][y][x] = sum, over the tiles covering (y, x) in ascending t, of coef[t][y - sy_t][x - sx_t] *
+ *   y_t[p][y - sy_t][x - sx_t]; out is [planes][h][w], y_t [planes][th][tw] at yt[t].  `yt` is a DEVICE table of T pointers (8-byte
+ *   aligned): the tiles' outputs are read where the network left them.  The first term is the product alone, every further term one
+ *   multiply then one add, never an fma: bit-equal to the same loop in numpy float32, and an element covered by one tile
+ *   (coefficient 1.0f) is a bit copy.  One launch, every output element written once, no atomics.
+ * Both use 16-byte accesses for 4 consecutive elements of a row wherever the row length is a multiple of 4 and the addresses are
+ * 16-byte aligned, decided per row in the kernel; any size and alignment is correct.
+ */
+int ccedit_tile_gather(const float* x, float* xt, const int32_t* starts, int32_t T, int64_t planes, int32_t h, int32_t w, int32_t th,
+                       int32_t tw, void* stream);
+int ccedit_tile_fuse(const void* yt, float* out, const int32_t* starts, const float* coef, int32_t T, int64_t planes, int32_t h, int32_t w,
+                     int32_t th, int32_t tw, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Propagation (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  Full-frame-rate output: the edited
  * keyframes are carried to every source frame between them along motion estimated on the source frames (ccedit_amd/propagate.py:
  * plan, tables, propagate_clip; `--propagate`).  Kernels: csrc/propagate.hip.  Everything is integer arithmetic on bytes and equals

@@ -30,6 +30,13 @@ to untracked masks too.
 clip is covered by overlapping windows of T frames, each evaluated by the unchanged network at every sampler evaluation and fused into
 one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everything else — inpainting, SDEdit, the prior mix,
 --noise_seed, --gpu_io — runs on the long latent as on a short one, first-stage encode / decode in groups of at most T frames.
+`--tile_h TH --tile_w TW` (pixels, multiples of 64; with `--tile_overlap O`, default a quarter of the tile per axis) lifts the limit of one
+frame size: with `--H` above TH or `--W` above TW the frame — any multiple of 8 pixels, 720 x 1280 and 1080 x 1920 included — is covered
+by overlapping tiles of TH x TW, each evaluated by the unchanged network at every sampler evaluation and fused into one denoised
+latent of the frame (ccedit_amd/tiles.py, csrc/tile.hip); everything else — inpainting, SDEdit, the prior mix, --window_frames (inside
+every tile), --noise_seed, --gpu_io, masks, the writers — runs on the large latent as on a small one, first-stage encode / decode on whole
+frames in groups sized so that no tensor outgrows a plain clip's at tile size.  Exact arithmetic and known shapes are what is claimed;
+image quality against a direct evaluation at the large size has not been measured.
 Launched under torch.distributed (RANK / WORLD_SIZE), the chunks are dealt round-robin to the ranks (BASELINE.json config 5:
 independent clips, one per GPU, no collective — ccedit_amd.parallel.shard_clips).
 `--propagate` (job mode, --save_type gif, mjpeg or png) adds the frames BETWEEN the keyframes: every source frame from the first to the last keyframe
@@ -138,6 +145,15 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                         "(17 for the shipped checkpoints).  0 = off: one window of --num_keyframes frames, as before")
     p.add_argument("--window_overlap", type=int, default=None,
                    help="(not in the reference script) frames shared by consecutive windows, 0 ... window_frames - 1 (default: window_frames // 2)")
+    p.add_argument("--tile_h", type=int, default=0,
+                   help="(not in the reference script) height in pixels (a multiple of 64) of the tile the network evaluates; with --tile_w, "
+                        "a frame with --H above it or --W above --tile_w is covered by overlapping tiles of this size whose denoised latents "
+                        "are fused at every sampler evaluation (512 for the shipped checkpoints).  0 = off: the frame as one piece, as before")
+    p.add_argument("--tile_w", type=int, default=0,
+                   help="(not in the reference script) width in pixels (a multiple of 64) of the tile, see --tile_h (768 for the shipped checkpoints)")
+    p.add_argument("--tile_overlap", type=int, default=None,
+                   help="(not in the reference script) pixels (a multiple of 8, less than the tile) shared by neighbouring tiles, on both axes "
+                        "(default: a quarter of the tile per axis, rounded down to a multiple of 8)")
     p.add_argument("--propagate", action="store_true",
                    help="(not in the reference script) full-frame-rate output: after a clip's keyframes are saved, every source frame from the "
                         "first to the last keyframe gets an edited frame — the two neighbouring edited keyframes carried along the source's "
@@ -179,6 +195,12 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--window_overlap is the overlap of the windows of --window_frames: give both")
     if args.window_frames and args.window_overlap is not None and not 0 <= args.window_overlap < args.window_frames:
         p.error("--window_overlap must be in 0 ... window_frames - 1")
+    if getattr(args, "tile_h", 0) < 0 or getattr(args, "tile_w", 0) < 0:
+        p.error("--tile_h and --tile_w must be positive (0 = off)")
+    if bool(getattr(args, "tile_h", 0)) != bool(getattr(args, "tile_w", 0)):
+        p.error("--tile_h and --tile_w are the two sides of one tile: give both")
+    if getattr(args, "tile_overlap", None) is not None and not getattr(args, "tile_h", 0):
+        p.error("--tile_overlap is the overlap of the tiles of --tile_h / --tile_w: give them too")
     if getattr(args, "propagate", False):
         if not job_mode(args):
             p.error("--propagate carries the edit to the frames between the keyframes of a video: give --prompt with --video_path "
@@ -213,6 +235,64 @@ def check_windowing(args, with_ref: bool = False) -> None:
         from ccedit_amd.windows import check_supported
         with open(args.config_path, "r") as f:
             check_supported(config=f.read())
+
+
+def tiling(args) -> bool:
+    """Tiles are active when both tile flags are set and the frame is larger than the tile on an axis; otherwise the plain path runs untouched."""
+    th, tw = getattr(args, "tile_h", 0) or 0, getattr(args, "tile_w", 0) or 0
+    return th > 0 and tw > 0 and (args.H > th or args.W > tw)
+
+
+def tile_overlap_px(args):
+    """(rows, columns) of pixels shared by neighbouring tiles: --tile_overlap on both axes, else a quarter of the tile per axis rounded
+    down to a multiple of 8."""
+    o = getattr(args, "tile_overlap", None)
+    return (args.tile_h // 4 // 8 * 8, args.tile_w // 4 // 8 * 8) if o is None else (int(o), int(o))
+
+
+def tile_plan_args(args):
+    """plan2d's arguments (latent units) for the flags: (lh, lw, th, tw, oh, ow)."""
+    oh, ow = tile_overlap_px(args)
+    return args.H // 8, args.W // 8, args.tile_h // 8, args.tile_w // 8, oh // 8, ow // 8
+
+
+def first_stage_frames(args) -> int:
+    """Frames per first-stage call under tiles: tiles.first_stage_group with T_plain = --window_frames if set, else --num_keyframes."""
+    from ccedit_amd.tiles import first_stage_group
+    lh, lw, th, tw, _, _ = tile_plan_args(args)
+    return first_stage_group(getattr(args, "window_frames", 0) or args.num_keyframes, th, tw, lh, lw)
+
+
+def check_tiling(args, with_ref: bool = False) -> None:
+    """Before any GPU work: what tiles cannot do is refused with what to do instead (ValueError; NotImplementedError for what tiles do
+    not cover).  With tiles off everything passes."""
+    if not tiling(args):
+        return
+    th, tw = args.tile_h, args.tile_w
+    if th % 64 or tw % 64:
+        raise ValueError(f"--tile_h {th} --tile_w {tw}: a tile is evaluated by the network directly, which takes multiples of 64 pixels — "
+                         f"choose tile sides that are multiples of 64 (512 x 768 for the shipped checkpoints)")
+    oh, ow = tile_overlap_px(args)
+    if oh % 8 or ow % 8 or oh < 0 or ow < 0:
+        raise ValueError(f"--tile_overlap {oh}: tiles are cut from the latent, 8 pixels per element — give a non-negative multiple of 8")
+    if oh >= th or ow >= tw:
+        raise ValueError(f"--tile_overlap {max(oh, ow)} is not smaller than the tile ({th}x{tw}): neighbouring tiles must differ — give less")
+    if args.H % 8 or args.W % 8:
+        raise ValueError(f"--H {args.H} --W {args.W}: tiles are cut from the latent, 8 pixels per element — frame sides must be multiples of 8")
+    if args.H < th or args.W < tw:
+        raise ValueError(f"--H {args.H} --W {args.W} does not fill one tile of {th}x{tw} on both axes: choose a tile no larger than the frame")
+    if with_ref:
+        raise NotImplementedError("--tile_h / --tile_w are not available with a reference image (sampling_tv2v_ref.py): the reference "
+                                  "latent (`cond_feat`) belongs to the whole frame, not to a tile")
+    if getattr(args, "propagate", False) and (args.H % 64 or args.W % 64):
+        raise ValueError(f"--propagate with --H {args.H} --W {args.W}: the motion matcher's pyramid (four levels of 8 x 8 blocks) takes frame "
+                         f"sides that are multiples of 64 — tiles lift that limit for the network only; choose such a size or drop --propagate")
+    from ccedit_amd import tiles
+    tiles.plan2d(*tile_plan_args(args))                                            # (more than 64 tiles: its own message)
+    tiles.check_frame_cap(args.H // 8, args.W // 8)
+    if args.config_path and os.path.exists(args.config_path):
+        with open(args.config_path, "r") as f:
+            tiles.check_supported(config=f.read())
 
 
 def check_propagate(args, video_paths) -> None:
@@ -502,8 +582,20 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
         if ref is not None:
             raise NotImplementedError("--window_frames is not available with a reference image: it belongs to the centre frame of one window")
         check_supported(cond=c)
-        denoiser = WindowedDenoiser(denoiser, args.window_frames, args.window_overlap, wrapper=model.model)
-        model = GroupedFirstStage(model, args.window_frames)      # (the closure above keeps the engine itself)
+        if not tiling(args):
+            denoiser = WindowedDenoiser(denoiser, args.window_frames, args.window_overlap, wrapper=model.model)
+            model = GroupedFirstStage(model, args.window_frames)      # (the closure above keeps the engine itself)
+
+    if tiling(args):             # a frame above the tile size: tiles outside, windows (if any) inside every tile
+        from ccedit_amd import tiles
+        from ccedit_amd.windows import GroupedFirstStage
+        if ref is not None:
+            raise NotImplementedError("--tile_h / --tile_w are not available with a reference image: it belongs to the whole frame, not to a tile")
+        tiles.check_supported(cond=c)
+        _, _, lth, ltw, loh, low = tile_plan_args(args)
+        denoiser = tiles.TiledDenoiser(denoiser, (lth, ltw), (loh, low), wrapper=model.model,
+                                       window=args.window_frames if windowing(args) else 0, window_overlap=args.window_overlap)
+        model = GroupedFirstStage(model, first_stage_frames(args))
 
     inpaint = getattr(args, "inpainting_mode", False)
     if inpaint and mask is None:
@@ -541,9 +633,9 @@ def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_t
     """sampling_tv2v.py:361-470 for one chunk: sample, decode and — with --mask_composite and the pixel masks `mask_px` — put the
     original pixels back outside the mask (ccedit_mask_composite)."""
     z = sample_latent(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=prior_type, mask=mask)
-    if windowing(args):
+    if tiling(args) or windowing(args):
         from ccedit_amd.windows import GroupedFirstStage
-        model = GroupedFirstStage(model, args.window_frames)
+        model = GroupedFirstStage(model, first_stage_frames(args) if tiling(args) else args.window_frames)
     samples = model.decode_first_stage(z)
     if getattr(args, "mask_composite", False) and mask_px is not None:
         from ccedit_amd import ops
@@ -708,6 +800,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
     log_info.json."""
     import json
     check_windowing(args, with_ref)
+    check_tiling(args, with_ref)
     from ccedit_amd.parallel import shard_clips
     from scripts.sampling.util import chunk, load_img, load_video_keyframes, model_load_ckpt, perform_save_locally_video
     prompts, video_paths, video_save_paths, ref_paths = expand_jobs(args, with_ref)
@@ -850,6 +943,7 @@ def main():
     if job_mode(args):
         return run_jobs(args)
     check_windowing(args)
+    check_tiling(args)
     from scripts.sampling.util import ResumeLog, save_frames
     model, dev = build_model(args)
     T, h, w = args.num_keyframes, args.H // 8, args.W // 8
