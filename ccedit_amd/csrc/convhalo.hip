@@ -504,11 +504,11 @@ int cc_conv_halo_launch(const CcGemmDesc& d, hipStream_t s) {
         constexpr int lds4 = epi_lds_total(BMC, BNP, TJ, 4 * BMC * 64 + 2 * kHaloBytes4);
         static unsigned long long attr_done4 = 0;
         if (int rc = cc_max_dynamic_lds((const void*)conv_halo4_kernel<WM, WN, TI, TJ>, lds4, &attr_done4, "conv_halo4")) return rc;
-        cc_note_kernel("conv_halo_kernel");
+        cc_note_kernel("conv_halo_kernel, four-slot weight ring");
         hipLaunchKernelGGL((conv_halo4_kernel<WM, WN, TI, TJ>), dim3((unsigned)nblk), dim3(WM * WN * 64), lds4, s, dd, tw_log2 | (1 << 8));
         return cc_launch_status("conv_halo4_kernel");
     }
-    cc_note_kernel("conv_halo_kernel");
+    cc_note_kernel("conv_halo_kernel, two-slot weight ring");
     hipLaunchKernelGGL((conv_halo_kernel<WM, WN, TI, TJ>), dim3((unsigned)nblk), dim3(WM * WN * 64), lds, s, dd,
                        tw_log2 | (1 << 8));
     return cc_launch_status("conv_halo_kernel");

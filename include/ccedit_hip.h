@@ -38,7 +38,8 @@ extern "C" {
 int ccedit_abi_version(void);
 const char* ccedit_last_error(void);
 /* name of the kernel template the last ccedit_gemm / ccedit_ff320 / ccedit_attention call of this thread dispatched to
- * ("g8_kernel 256x256", "conv_halo_kernel", "tap_gemm_kernel 128x128 s2", ...): bench.py's per-kernel roofline table */
+ * ("g8_kernel 256x256", "conv_halo_kernel, four-slot weight ring" / "conv_halo_kernel, two-slot weight ring" by policy conv_halo,
+ * "tap_gemm_kernel 128x128 s2", ...): bench.py's per-kernel roofline table */
 const char* ccedit_last_kernel(void);
 /* fills name with hipDeviceProp_t.gcnArchName of the current device; returns CU count or <0 */
 int ccedit_device_info(char* name, int name_len);

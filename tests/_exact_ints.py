@@ -1,8 +1,9 @@
 """Integer-valued operands for the exact-arithmetic kernel tests (tests/test_exact_gpu.py, tests/test_exact_host.py).
 
 Every tensor here is float64 on the CPU and holds integers.  The recipe: activations dense in [-xmax, xmax] (2 for the bf16
-kernels), weights in {-1, 0, +1} with about 48 non-zeros per output row and at least one in EVERY K column, bias and row bias in
-[-8, 8], residuals in [-16, 16].  Under the two conditions `check_inputs` asserts, a correct kernel reproduces the float64
+kernels), weights in {-1, 0, +1} with about 48 non-zeros per output row and at least one in EVERY K column (`rows_per_tile=R`: in
+every K column of every block of R consecutive output rows — a channel tile of a kernel), bias and row bias in [-8, 8], residuals
+in [-16, 16].  Under the two conditions `check_inputs` asserts, a correct kernel reproduces the float64
 reference bit for bit whatever its tile shape, K order, split or atomic order:
 
   * sum over K of |x| |w| plus the epilogue terms stays below 2^24, so every product and every partial sum in any order is an
@@ -30,10 +31,21 @@ def ints(shape, lo, hi, g):
     return torch.randint(lo, hi + 1, tuple(shape), generator=g).double()
 
 
-def sparse_weight(shape, g, wmax=1):
+def unobserved(w, rows_per_tile):
+    """(tiles, K) mask of the (block of `rows_per_tile` consecutive output rows, K column) pairs in which the block holds no weight:
+    a kernel whose defect lives in that channel tile may drop or misread that K element and the result does not change."""
+    w2 = w.reshape(w.shape[0], -1)
+    nt = (w2.shape[0] + rows_per_tile - 1) // rows_per_tile
+    return torch.stack([(w2[t * rows_per_tile:(t + 1) * rows_per_tile] != 0).sum(dim=0) == 0 for t in range(nt)])
+
+
+def sparse_weight(shape, g, wmax=1, rows_per_tile=0):
     """Reference-layout weight (O, I) / (O, I, K) / (O, I, KH, KW) with entries in {-wmax..-1, 0, 1..wmax}: density 48 / K (the
     density follows K, so the row sums stay near sqrt(48) whatever the layer), then one non-zero into every K column that got none —
-    a K column without a weight would leave that element of A unobserved."""
+    a K column without a weight would leave that element of A unobserved.
+    rows_per_tile = R > 0: afterwards every block of R consecutive output rows (a kernel's channel tile, or a part of one) gets one
+    +-1 at a random row of the block in every K column where the block holds no weight, so every K element is observed in EVERY
+    tile.  These draws come after all the others: with the default 0 nothing extra is drawn and the weights are what they were."""
     n = shape[0]
     kk = 1
     for s in shape[1:]:
@@ -46,27 +58,39 @@ def sparse_weight(shape, g, wmax=1):
     if empty.numel():
         rows = torch.randint(0, n, (empty.numel(),), generator=g)
         w[rows, empty] = sign[rows, empty] * mag[rows, empty]
+    if rows_per_tile:
+        for r0 in range(0, n, rows_per_tile):
+            blk = w[r0:r0 + rows_per_tile]                      # a view: the block is filled in place
+            empty = ((blk != 0).sum(dim=0) == 0).nonzero().flatten()
+            if empty.numel():
+                rows = torch.randint(0, blk.shape[0], (empty.numel(),), generator=g)
+                blk[rows, empty] = (torch.randint(0, 2, (empty.numel(),), generator=g) * 2 - 1).double()
     return w.reshape(shape)
 
 
-def check_inputs(x, w, ref, extra, out_max):
-    """The two conditions on the INPUTS (not tolerances): every K column of w carries a non-zero, and |ref| <= out_max.  Plus the
-    premise of exactness itself: (largest row sum of |w|) * max|x| + the epilogue terms < 2^24 bounds every partial sum."""
+def check_inputs(x, w, ref, extra, out_max, rows_per_tile=0):
+    """The two conditions on the INPUTS (not tolerances): every K column of w carries a non-zero — with rows_per_tile = R inside
+    every block of R consecutive output rows — and |ref| <= out_max.  Plus the premise of exactness itself: (largest row sum of
+    |w|) * max|x| + the epilogue terms < 2^24 bounds every partial sum."""
     w2 = w.reshape(w.shape[0], -1)
     assert bool((w2 != 0).any(dim=0).all()), "a K column of the weight has no non-zero entry"
+    if rows_per_tile:
+        gaps = int(unobserved(w, rows_per_tile).sum())
+        assert gaps == 0, f"{gaps} (block of {rows_per_tile} output rows, K column) pairs hold no weight"
     assert bool((ref == ref.round()).all()), "the reference is not integer-valued"
     assert ref.abs().max().item() <= out_max, f"max|ref| = {ref.abs().max().item()} > {out_max}"
     assert w2.abs().sum(dim=1).max().item() * x.abs().max().item() + extra < F32_EXACT, "partial sums may leave fp32's integers"
 
 
 def operands(xshape, wshape, fwd, seed=0, xmax=2, wmax=1, bias=True, rows_per_bias=0, frames_per_bias=0, nres=2, out_max=BF16_EXACT,
-             bmax=8, rmax=16):
+             bmax=8, rmax=16, rows_per_tile=0):
     """x, w, bias, row bias, residuals and the float64 reference `fwd(x, w, bias) + row bias + residuals`.
     fwd: F.linear / F.conv2d / F.conv1d on float64; its result is (M, N) or (frames, C, H, W).
-    rows_per_bias: one row-bias vector per that many GEMM rows (2-D results); frames_per_bias: per that many frames (4-D results)."""
+    rows_per_bias: one row-bias vector per that many GEMM rows (2-D results); frames_per_bias: per that many frames (4-D results).
+    rows_per_tile: see sparse_weight (the bias, row bias and residual draws follow the weight's, so they differ from the default's)."""
     g = gen(seed)
     x = ints(xshape, -xmax, xmax, g)
-    w = sparse_weight(wshape, g, wmax)
+    w = sparse_weight(wshape, g, wmax, rows_per_tile)
     b = ints((wshape[0],), -bmax, bmax, g) if bias else None
     ref = fwd(x, w, b)
     gb = None
@@ -79,7 +103,7 @@ def operands(xshape, wshape, fwd, seed=0, xmax=2, wmax=1, bias=True, rows_per_bi
     res = [ints(ref.shape, -rmax, rmax, g) for _ in range(nres)]
     for r in res:
         ref = ref + r
-    check_inputs(x, w, ref, 2 * bmax + nres * rmax, out_max)
+    check_inputs(x, w, ref, 2 * bmax + nres * rmax, out_max, rows_per_tile)
     return SimpleNamespace(x=x, w=w, b=b, gb=gb, res=res, r1=res[0] if nres > 0 else None, r2=res[1] if nres > 1 else None, ref=ref)
 
 

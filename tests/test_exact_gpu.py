@@ -12,6 +12,9 @@ are small integers (tests/_exact_ints.py), chosen so that every number a kernel 
 
 The generator asserts two conditions on its INPUTS before anything runs on the GPU: max|ref| <= 256 (2^24 for fp32 outputs), and
 every K column of the weight — every (tap, cin) of a packed convolution — carries a non-zero, so every element of A is observed.
+The convolution cases past one 64-channel input chunk ask for more (`rows_per_tile=16`): a non-zero in every K column inside EVERY
+block of 16 output rows, the smallest MFMA row tile of the library — a kernel's defect lives in one channel tile, and at 320 -> 640
+more than half of the (32-channel tile, K column) pairs of the plain recipe hold no weight (tests/test_exact_host.py).
 The assertions on the kernels are torch.equal against float64 F.linear / F.conv2d / F.conv1d, and the label of the kernel that ran.
 
 What this rests on: every kernel here accumulates bf16 x bf16 products in fp32 inside the matrix pipe (v_mfma_f32_32x32x16_bf16,
@@ -136,7 +139,7 @@ def test_tap_gemm_linear_strided_and_second_source(tile):
 
 
 # ------------------------------------------------------------------------------------------ tap_gemm, Conv2d
-def _conv_case(kind, cin, cout, seed):
+def _conv_case(kind, cin, cout, seed, rows_per_tile=0):
     """(operands, call) of one Conv2d geometry on two 9 x 7 frames (126 output pixels at stride 1: a tile straddles the frames)."""
     n, h, w = 2, 9, 7
     kw = {}
@@ -158,7 +161,7 @@ def _conv_case(kind, cin, cout, seed):
         zero = torch.zeros_like(halo)
         rows = (halo, zero) if kind == "halo_top" else (zero, halo)
         fwd = lambda x, wt, b: F.conv2d(torch.cat([rows[0], x, rows[1]], dim=2), wt, b, padding=(0, 1))
-    o = E.operands((n, cin, h, w), (cout, cin, 3, 3), fwd, seed=seed, frames_per_bias=1)
+    o = E.operands((n, cin, h, w), (cout, cin, 3, 3), fwd, seed=seed, frames_per_bias=1, rows_per_tile=rows_per_tile)
     if halo is not None:
         hr = _nhwc(halo).reshape(n, w, cin).contiguous()
         kw = dict(halo=(hr, None) if kind == "halo_top" else (None, hr))
@@ -167,15 +170,19 @@ def _conv_case(kind, cin, cout, seed):
 
 @pytest.mark.parametrize("kind,cin,cout,tile", [(k, 64, 96, t) for k in ("s1", "s2", "up", "asym") for t in (1, 2, 3, 4, 5)]
                          + [(k, 64, 96, t) for k in ("vpad", "halo_top", "halo_bot") for t in (1, 2, 3)]
-                         + [(k, 8, 320, t) for k in ("s1", "s2") for t in (1, 2, 3, 4, 5, 6)])
+                         + [(k, 8, 320, t) for k in ("s1", "s2") for t in (1, 2, 3, 4, 5, 6)]
+                         + [(k, 128, 96, t) for k in ("s1", "s2", "up", "asym") for t in (1, 2, 3, 4, 5)]
+                         + [(k, 128, 96, t) for k in ("vpad", "halo_top", "halo_bot") for t in (1, 2, 3)]
+                         + [("s1", 192, 320, t) for t in (1, 2, 3, 4, 5, 6)])
 def test_tap_gemm_conv2d(kind, cin, cout, tile):
     """tap_gemm_kernel's 3x3 gather: stride 1 / 2, the fused nearest-2x source, asymmetric padding through out_hw, halo rows inside
     the frames (vpad) or as separate tensors with one side None, Cin = 8 (the padded latent; K = [tap][Cin] order) and Cin = 64
-    (K = [Cin/64][tap][64] order) — image borders on all four sides of 9 x 7 frames, per-frame row bias and two residuals."""
+    (K = [Cin/64][tap][64] order) — image borders on all four sides of 9 x 7 frames, per-frame row bias and two residuals.
+    Cin = 128 / 192: the K order read past chunk 0 (k-tile c * 9 + tap), every K column observed in every 16-channel block."""
     _dev()
     from ccedit_amd import ops
     from ccedit_amd.packing import pack_weight
-    o, kw = _conv_case(kind, cin, cout, seed=tile + cin)
+    o, kw = _conv_case(kind, cin, cout, seed=tile + cin, rows_per_tile=16 if cin > 64 else 0)
     hw = o.ref.shape[2] * o.ref.shape[3]
     y = ops.conv2d(_nhwc(o.x), pack_weight(o.w, o.b).to("cuda"), group_bias=_f32(o.gb), group_rows=hw, res1=_flat(o.r1),
                    res2=_flat(o.r2), tile=tile, **kw)
@@ -184,22 +191,24 @@ def test_tap_gemm_conv2d(kind, cin, cout, tile):
 
 
 # ------------------------------------------------------------------------------------------ Conv1d over T: tap_gemm and g8
-@pytest.mark.parametrize("t", [2, 3, 17])
-@pytest.mark.parametrize("tile", [1, 2, 3, 4, 5, 12, 13])
-def test_temporal_conv(t, tile):
+@pytest.mark.parametrize("t,tile,c", [pytest.param(t, tile, 64, id=f"{tile}-{t}") for t in (2, 3, 17) for tile in (1, 2, 3, 4, 5, 12, 13)]
+                         + [pytest.param(3, tile, 128, id=f"{tile}-3-c128") for tile in (1, 2, 3, 4, 5, 12, 13)])
+def test_temporal_conv(t, tile, c):
     """Conv1d k3 over T, two clips: the taps at the clip ends AND between the clips are zeros.  tap_gemm on ragged 3 x 5 frames, the
-    persistent kernel's temporal gather on 4 x 8 frames (its row bias wants 32-row groups); per-clip row bias, two residuals."""
+    persistent kernel's temporal gather on 4 x 8 frames (its row bias wants 32-row groups); per-clip row bias, two residuals.
+    C = 128: two 64-channel chunks, every K column observed in every 16-channel block."""
     _dev()
     from ccedit_amd import ops
     from ccedit_amd.packing import pack_weight
-    b_, c, cout = 2, 64, 96
+    b_, cout = 2, 96
     h, w = (4, 8) if tile >= 12 else (3, 5)
-    o = E.operands((b_ * t, c, h, w), (cout, c, 3), E.temporal_ref(b_, t), seed=10 * t + tile, frames_per_bias=t)
+    o = E.operands((b_ * t, c, h, w), (cout, c, 3), E.temporal_ref(b_, t), seed=10 * t + tile, frames_per_bias=t,
+                   rows_per_tile=16 if c > 64 else 0)
     y = ops.conv_temporal(_nhwc(o.x), t, pack_weight(o.w, o.b).to("cuda"), group_bias=_f32(o.gb), group_rows=t * h * w,
                           res1=_flat(o.r1), res2=_flat(o.r2), tile=tile)
     want = G8[tile] + ", temporal taps" if tile >= 12 else TAP[tile]
     assert want in _last(), _last()
-    _equal(_nchw(y), o.ref, f"temporal conv T={t} tile {tile}")
+    _equal(_nchw(y), o.ref, f"temporal conv T={t} C={c} tile {tile}")
 
 
 def test_temporal_conv_frame_sharded():
@@ -251,6 +260,148 @@ def test_conv_halo(cin, cout, h, w):
         assert ops.gn_stats_of(y, h * w) is None
 
 
+# ---- convhalo past one 64-channel input chunk, both weight-ring arms (library policy `conv_halo`: 1 four-slot, 2 two-slot)
+# (frames, Cin, Cout, H, W) and what the case reaches in csrc/convhalo.hip:
+HALO_CASES = [
+    (3, 128, 128, 8, 16),     # two chunks: both halo buffers, the waits with a halo rectangle in flight; one channel tile
+    (3, 192, 320, 8, 12),     # three chunks (buffer 0 reused); 8 x 16 rectangles with 12 of 16 columns used; narrow last tile
+    (2, 320, 640, 16, 24),    # five chunks; 16 x 8 rectangles; five channel tiles in groups 3 + 2 (cgroup); statistics, 384 rows
+    (2, 128, 960, 16, 16),    # tiles_y = 2; eight channel tiles in groups 3 + 3 + 2, the last one narrow; statistics
+    (2, 128, 1280, 16, 8),    # 16 x 8 with one rectangle column; ten channel tiles in groups 3 + 3 + 3 + 1; statistics, 128 rows
+    (9, 128, 256, 8, 16),     # nine pixel tiles on eight XCDs: pt_per_xcd = 2, workgroups that return early
+    (2, 128, 256, 24, 40),    # H a multiple of 8, not of 16: three rectangle rows, the third column ragged (8 of 16)
+    (2, 128, 256, 32, 20),    # 16 x 8 rectangles, two rectangle rows, the third column ragged (4 of 8)
+    (1, 64, 64, 8, 16),       # a narrow tile with no full tile beside it
+]
+HALO_LABEL = {1: "conv_halo_kernel, four-slot weight ring", 2: "conv_halo_kernel, two-slot weight ring"}
+_halo_cache = {}
+
+
+def _halo_operands(case):
+    """Operands and float64 reference of one case: computed once, shared by the tests below, never modified."""
+    if case not in _halo_cache:
+        n, cin, cout, h, w = case
+        _halo_cache[case] = E.operands((n, cin, h, w), (cout, cin, 3, 3), lambda x, wt, b: F.conv2d(x, wt, b, padding=1), seed=cout + w,
+                                       frames_per_bias=1, nres=1, rows_per_tile=16)
+    return _halo_cache[case]
+
+
+def _set_halo_arm(value):
+    from ccedit_amd import hip
+    assert hip.lib().ccedit_policy_set(b"conv_halo", value) == 0
+
+
+@pytest.fixture(params=[1, 2], ids=["four-slot", "two-slot"])
+def halo_arm(request):
+    """Both weight rings of the LDS-halo conv (library policy `conv_halo`)."""
+    _dev()
+    _set_halo_arm(request.param)
+    yield request.param
+    _set_halo_arm(1)
+
+
+def _bits(t):
+    return t.view(torch.int16)
+
+
+class _HaloBuffers:
+    """Device operands of one case in the forms the network never guarantees to be tight: the source is the column slice [64, 64 + Cin)
+    of a buffer with row stride Cin + 128 and 2 W guard rows before the first and after the last frame, everything outside the
+    frames' slice bf16 NaN (a kernel may load such memory, but none of it may reach a result, not even as 0 * NaN); the residual is
+    a column slice of a wider buffer."""
+
+    def __init__(self, case, o):
+        from ccedit_amd.packing import pack_weight
+        n, cin, cout, h, w = case
+        self.case, self.o, self.rows, self.guard = case, o, n * h * w, 2 * w
+        self.pw = pack_weight(o.w, o.b).to("cuda")
+        self.src = torch.full((self.rows + 2 * self.guard, cin + 128), float("nan"), dtype=BF, device="cuda")
+        self.src[self.guard:self.guard + self.rows, 64:64 + cin] = _flat(o.x)
+        self.x = self.src[self.guard:self.guard + self.rows, 64:64 + cin].view(n, h, w, cin)
+        flat = self.x.reshape(-1, cin)
+        assert flat.data_ptr() == self.x.data_ptr() and flat.stride(0) == cin + 128       # the launch sees the slice, not a copy
+        self.res_wide = torch.full((self.rows, cout + 128), 7.0, dtype=BF, device="cuda")
+        self.res_wide[:, 64:64 + cout] = _flat(o.r1)
+        self.res = self.res_wide[:, 64:64 + cout]
+        self.src0, self.res0 = self.src.clone(), self.res_wide.clone()
+        self.kw = dict(group_bias=_f32(o.gb), group_rows=h * w, res1=self.res, gn=True)
+
+    def launch(self, tile=8, **kw):
+        from ccedit_amd import ops
+        return ops.conv2d(self.x, self.pw, tile=tile, **self.kw, **kw)
+
+    def unchanged(self):
+        assert torch.equal(_bits(self.src), _bits(self.src0)), "the source buffer was written"
+        assert torch.equal(_bits(self.res_wide), _bits(self.res0)), "the residual buffer was written"
+
+
+def _halo_first_launch(bufs, arm, tile=8):
+    """Contiguous output, row bias + residual, gn=True: equal to the reference, the arm's label; statistics where the producer fuses
+    them (Cout >= 256, frames of whole 128-pixel blocks): equal to the float64 group sums, three launches alike."""
+    from ccedit_amd import ops
+    n, cin, cout, h, w = bufs.case
+    what = f"halo conv {n} x {cin}->{cout} {h}x{w}, {HALO_LABEL[arm]}"
+    y = bufs.launch(tile)
+    assert _last() == HALO_LABEL[arm], _last()
+    _equal(_nchw(y), bufs.o.ref, what)
+    st = None
+    if cout >= 256 and (h * w) % 128 == 0:
+        st = _stats_equal(y, h * w, what)
+        for _ in range(2):
+            y2 = bufs.launch(tile)
+            assert torch.equal(y2, y) and torch.equal(ops.gn_stats_of(y2, h * w), st), f"{what}: run-to-run difference"
+    else:
+        assert ops.gn_stats_of(y, h * w) is None
+    return y, st
+
+
+@pytest.mark.parametrize("case", HALO_CASES, ids=lambda c: "{}x{}-{}-{}x{}".format(*c))
+def test_conv_halo_chunks(halo_arm, case):
+    """conv_halo4_kernel / conv_halo_kernel where their machinery is (HALO_CASES), on operands that observe every K column in every
+    16-channel block: strided NaN-guarded source, strided residual; a contiguous launch with statistics, then a launch into a column
+    slice of a wider, longer buffer holding the bit pattern 0x5A5A, which must survive everywhere outside the slice."""
+    _dev()
+    n, cin, cout, h, w = case
+    bufs = _HaloBuffers(case, _halo_operands(case))
+    _halo_first_launch(bufs, halo_arm)
+    guard = 2 * w
+    big = torch.full((bufs.rows + 2 * guard, cout + 128), 0x5A5A, dtype=torch.int16, device="cuda").view(BF)
+    bufs.launch(out=big[guard:guard + bufs.rows, 64:64 + cout])
+    assert _last() == HALO_LABEL[halo_arm], _last()
+    _equal(_nchw(big[guard:guard + bufs.rows, 64:64 + cout].reshape(n, h, w, cout)), bufs.o.ref, "halo conv into a column slice")
+    outside = _bits(big).clone()
+    outside[guard:guard + bufs.rows, 64:64 + cout] = 0x5A5A
+    assert bool((outside == 0x5A5A).all()), "elements outside the output slice were written"
+    bufs.unchanged()
+
+
+def test_conv_halo_automatic_dispatch(halo_arm):
+    """320 -> 640 at 16 x 24 without a forced tile: the same kernel, the same bits."""
+    _dev()
+    case = HALO_CASES[2]
+    bufs = _HaloBuffers(case, _halo_operands(case))
+    _halo_first_launch(bufs, halo_arm, tile=0)
+    bufs.unchanged()
+
+
+@pytest.mark.parametrize("case", HALO_CASES, ids=lambda c: "{}x{}-{}-{}x{}".format(*c))
+def test_conv_halo_arms_agree(case):
+    """The documented claim of csrc/convhalo.hip: the two-slot kernel gives bit-identical results (same k-step order) — outputs and
+    statistics of the two arms against each other."""
+    _dev()
+    bufs = _HaloBuffers(case, _halo_operands(case))
+    try:
+        got = {}
+        for arm in (1, 2):
+            _set_halo_arm(arm)
+            got[arm] = _halo_first_launch(bufs, arm)
+    finally:
+        _set_halo_arm(1)
+    assert torch.equal(got[1][0], got[2][0]), "the two weight rings wrote different outputs"
+    assert (got[1][1] is None) == (got[2][1] is None)
+    assert got[1][1] is None or torch.equal(got[1][1], got[2][1]), "the two weight rings left different statistics"
+
+
 # ------------------------------------------------------------------------------------------ g8 (tiles 11-13)
 @pytest.mark.parametrize("tile", [11, 12, 13])
 @pytest.mark.parametrize("nres", [0, 1, 2])
@@ -296,14 +447,16 @@ def test_g8_linear_row_bias_and_statistics(tile):
 
 
 @pytest.mark.parametrize("tile", [12, 13])
-@pytest.mark.parametrize("n,cin,cout,h,w", [(5, 64, 384, 12, 16), (3, 64, 256, 8, 16)])
+@pytest.mark.parametrize("n,cin,cout,h,w", [(5, 64, 384, 12, 16), (3, 64, 256, 8, 16), (3, 192, 384, 12, 16), (3, 128, 256, 8, 16)])
 def test_g8_conv3x3(n, cin, cout, h, w, tile):
     """g8_kernel's nine-tap gather: zeros outside the frame, also between the frames of the batch; row bias + residual; at 8 x 16 (whole
-    128-pixel blocks, a 256-pixel tile holds two frames) the fused statistics."""
+    128-pixel blocks, a 256-pixel tile holds two frames) the fused statistics.  Cin = 192 (27 K tiles: an odd count) and 128: the K
+    order past chunk 0 with every K column observed in every 16-channel block, and one launch on the plain epilogue."""
     _dev()
     from ccedit_amd import ops
     from ccedit_amd.packing import pack_weight
-    o = E.operands((n, cin, h, w), (cout, cin, 3, 3), lambda x, wt, b: F.conv2d(x, wt, b, padding=1), seed=n + tile, frames_per_bias=1, nres=1)
+    o = E.operands((n, cin, h, w), (cout, cin, 3, 3), lambda x, wt, b: F.conv2d(x, wt, b, padding=1), seed=n + tile, frames_per_bias=1, nres=1,
+                   rows_per_tile=16 if cin > 64 else 0)
     pw, xd = pack_weight(o.w, o.b).to("cuda"), _nhwc(o.x)
     with_stats = (h * w) % 128 == 0 and cout >= 256
     kw = dict(group_bias=_f32(o.gb), group_rows=h * w, res1=_flat(o.r1), gn=with_stats, tile=tile)
@@ -316,6 +469,10 @@ def test_g8_conv3x3(n, cin, cout, h, w, tile):
             s = _stats_equal(y, h * w, "g8 conv3x3")
             assert st is None or torch.equal(s, st), "g8 conv statistics: run-to-run difference"
             st = s
+    if cin > 64:
+        y = ops.conv2d(xd, pw, tile=tile)
+        assert G8[tile] + ", 3x3 taps" in _last(), _last()
+        _equal(_nchw(y), o.ref - o.r1 - o.gb[:, :, None, None], f"g8 conv3x3 {n}x{h}x{w} tile {tile}, plain epilogue")
 
 
 @pytest.mark.parametrize("tile", [12, 13])
@@ -338,16 +495,19 @@ def test_g8_temporal_with_statistics(tile):
         st = s
 
 
-@pytest.mark.parametrize("tile", [1, 12, 13])
-def test_upsample_parity_convs(tile):
+@pytest.mark.parametrize("tile,cin", [pytest.param(t, 64, id=str(t)) for t in (1, 12, 13)]
+                         + [pytest.param(t, 128, id=f"{t}-c128") for t in (1, 12, 13)])
+def test_upsample_parity_convs(tile, cin):
     """conv3x3(nearest 2x(x)) as four 2 x 2 parity convs (conv2d_upsampled) on one odd 5 x 7 frame: the merged taps are sums of up to
-    four weights in {-1, 0, 1} — integers, so the parity form equals the nine-tap float64 reference exactly."""
+    four weights in {-1, 0, 1} — integers, so the parity form equals the nine-tap float64 reference exactly.  Cin = 128: two chunks,
+    every K column of the nine-tap weight observed in every 16-channel block."""
     _dev()
     from ccedit_amd import ops
     from ccedit_amd.packing import pack_upsample_parities
-    n, h, w, cin, cout = 1, 5, 7, 64, 64
+    n, h, w, cout = 1, 5, 7, 64
     o = E.operands((n, cin, h, w), (cout, cin, 3, 3),
-                   lambda x, wt, b: F.conv2d(F.interpolate(x, scale_factor=2.0, mode="nearest"), wt, b, padding=1), seed=tile, nres=0)
+                   lambda x, wt, b: F.conv2d(F.interpolate(x, scale_factor=2.0, mode="nearest"), wt, b, padding=1), seed=tile, nres=0,
+                   rows_per_tile=16 if cin > 64 else 0)
     y = ops.conv2d_upsampled(_nhwc(o.x), pack_upsample_parities(o.w, o.b, device="cuda"), tile=tile)
     assert (G8[tile] + ", upsample parity taps" if tile >= 12 else TAP[tile]) in _last(), _last()
     _equal(_nchw(y), o.ref, f"parity convs tile {tile}")
