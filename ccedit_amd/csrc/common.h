@@ -190,6 +190,10 @@ int cc_tile_gather(const float* x, float* xt, const int32_t* starts, int32_t T, 
 int cc_tile_fuse(const float* const* yt, float* out, const int32_t* starts, const float* coef, int32_t T, int64_t planes, int32_t h, int32_t w,
                  int32_t th, int32_t tw, hipStream_t s);
 
+// Region launchers (region.hip); entry points and argument checks in core.cpp
+int cc_region_weights(const uint8_t* masks, float* coef, int32_t K, int32_t T, int32_t H, int32_t W, int32_t F, hipStream_t s);
+int cc_region_fuse(const float* const* yr, float* out, const float* coef, int32_t K, int64_t BC, int32_t T, int64_t P, hipStream_t s);
+
 // Propagation launchers (propagate.hip); entry points and argument checks in core.cpp
 int cc_prop_pyramid(const uint8_t* rgb, uint8_t* pyr, int32_t F, int32_t H, int32_t W, hipStream_t s);
 int cc_prop_match(const uint8_t* lum, const int32_t* pairs, const int32_t* rank, const int32_t* parent, int32_t* out, int32_t P, int32_t F,

@@ -258,6 +258,32 @@ extern "C" int ccedit_tile_fuse(const void* yt, float* out, const int32_t* start
     return cc_tile_fuse((const float* const*)yt, out, starts, coef, T, planes, h, w, th, tw, (hipStream_t)stream);
 }
 
+// ---- region prompts (kernels and launchers: region.hip).  Everything the host can see is checked here, before any HIP call; the
+// device tables (coef, the pointer table) cannot take an access outside a tensor: coef is only ever read at the output's own index.
+extern "C" int ccedit_region_weights(const void* masks, float* coef, int32_t K, int32_t T, int32_t H, int32_t W, int32_t F, void* stream) {
+    CC_CHECK_ARG(masks && coef, "ccedit_region_weights: null pointer");
+    CC_CHECK_ARG(K >= 1 && K <= 7, "ccedit_region_weights: K=%d regions (1 ... 7)", K);
+    CC_CHECK_ARG(F >= 0 && F <= 8, "ccedit_region_weights: F=%d latent cells of feather (0 ... 8)", F);
+    CC_CHECK_ARG(T >= 1 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0 && H <= 65536 && W <= 65536,
+                 "ccedit_region_weights: T=%d frames of %dx%d (T >= 1, H and W multiples of 8, 8 ... 65536)", T, H, W);
+    CC_CHECK_ARG((int64_t)K * T * H * W < kPixelMax * 4 && (int64_t)T * ((H + 127) / 128) * ((W + 127) / 128) < kPixelMax,
+                 "ccedit_region_weights: more than 2^33 mask bytes or 2^31 tiles in one call (K=%d T=%d %dx%d)", K, T, H, W);
+    CC_CHECK_ARG(((uintptr_t)masks & 7) == 0 && ((uintptr_t)coef & 3) == 0, "ccedit_region_weights: masks must be 8-byte and coef 4-byte aligned");
+    return cc_region_weights((const uint8_t*)masks, coef, K, T, H, W, F, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_region_fuse(const void* yr, float* out, const float* coef, int32_t K, int32_t B, int32_t C, int32_t T, int64_t P,
+                                  void* stream) {
+    CC_CHECK_ARG(yr && out && coef, "ccedit_region_fuse: null pointer");
+    CC_CHECK_ARG(K >= 1 && K <= 7, "ccedit_region_fuse: K=%d regions (1 ... 7; the table holds K + 1 pointers)", K);
+    CC_CHECK_ARG(B > 0 && C > 0 && T >= 1 && P > 0, "ccedit_region_fuse: B=%d C=%d T=%d P=%lld (positive)", B, C, T, (long long)P);
+    CC_CHECK_ARG((int64_t)B * C < kPixelMax && P < kPixelMax * 4 && (int64_t)B * C * T * P < kPixelMax * 4,
+                 "ccedit_region_fuse: more than 2^33 elements in one call (B=%d C=%d T=%d P=%lld)", B, C, T, (long long)P);
+    CC_CHECK_ARG(((uintptr_t)yr & 7) == 0, "ccedit_region_fuse: the table of region pointers must be 8-byte aligned");
+    CC_CHECK_ARG(((uintptr_t)out & 3) == 0 && ((uintptr_t)coef & 3) == 0, "ccedit_region_fuse: out and coef must be 4-byte aligned");
+    return cc_region_fuse((const float* const*)yr, out, coef, K, (int64_t)B * C, T, P, (hipStream_t)stream);
+}
+
 // ---- propagation of edited keyframes to every source frame (kernels and launchers: propagate.hip).  Everything the host can see is
 // checked here, before any HIP call; the device tables (pairs, rank, g, the block vectors) are held in range by the kernels themselves.
 static int prop_shape_ok(const char* fn, int32_t P, int32_t F, int32_t H, int32_t W) {

@@ -1242,12 +1242,12 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
 
     def __init__(self, diffusion_model, compile_model: bool = False):
         super().__init__(diffusion_model, compile_model)
-        # the per-clip caches (caches.PinnedCache: a key match always means the same bytes); two limits follow reserve_windows
+        # the per-clip caches (caches.PinnedCache: a key match always means the same bytes); three limits follow reserve_windows / reserve_contexts
         self._hint_val = PinnedCache(lambda: self._hint_slots)          # hint-stem outputs: one per CFG half (+ shards)
         self._hint_dup = PinnedCache(lambda: 2 * self._hint_slots)      # are the two halves of a hint tensor equal?
         self._hint_slices = PinnedCache(4)                              # this rank's contiguous part of a hint tensor
         self._twin_val = PinnedCache(8)                                 # are the two CFG halves of (x, t, hint, cond_feat) equal?
-        self._tkv_val = PinnedCache(6)                                  # text K / V per (network, conditioning tensor)
+        self._tkv_val = PinnedCache(lambda: self._tkv_slots)            # text K / V per (network, conditioning tensor)
         self._graphs = PinnedCache(lambda: self._graph_slots, evict="oldest")       # a GraphEntry per conditioning key
 
     def __setattr__(self, name, value):
@@ -1353,17 +1353,37 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
     # needs — nothing would ever be replayed.  reserve_windows(W) sizes the per-clip caches for W windows and gives the W graphs ONE
     # memory pool: they replay strictly one after another on one stream and every replay's output is cloned before the next (see
     # _forward_graphed), so the activations of one evaluation are held once, not W times.  Without the call nothing changes.
+    # Region prompts (ccedit_amd/regions.py) evaluate every window of every tile once per text context: reserve_contexts(R) multiplies
+    # the graph keys (R x windows, still ONE pool) and sizes the text K / V cache for R contexts in both networks; the hint tensor is
+    # the same object for all contexts, so the stem caches do not grow.  The two calls compose in either order (the region wrapper
+    # is the outermost one and reserves first); reserve_windows(0) puts back every limit of a plain clip, the contexts' too.
     _graph_slots = 2
     _hint_slots = 4
+    _tkv_slots = 6              # (UNet, ControlNet) x up to 3 conditioning tensors
     _graph_pool = None
+    _windows = 1
+    _contexts = 1
     graph_counts = None         # {"eager", "capture", "replay"}: evaluations of _forward_graphed by kind since reserve_windows / first use
 
     def reserve_windows(self, windows: int) -> None:
-        """Size the per-clip caches for `windows` conditioning keys evaluated in turn (0 or 1: back to a plain clip's limits)."""
-        w = max(int(windows), 1)
-        self._graph_slots = max(2, w)
+        """Size the per-clip caches for `windows` conditioning keys evaluated in turn (0: back to a plain clip's limits, text contexts
+        included; 1 or more: per text context of reserve_contexts)."""
+        if int(windows) <= 0:
+            self._contexts = 1
+        self._windows = max(int(windows), 1)
+        self._reserve()
+
+    def reserve_contexts(self, contexts: int) -> None:
+        """Size the per-clip caches for `contexts` text conditionings evaluated in turn for every window (0 or 1: one, as without the call)."""
+        self._contexts = max(int(contexts), 1)
+        self._reserve()
+
+    def _reserve(self) -> None:
+        w, keys = self._windows, self._windows * self._contexts
+        self._graph_slots = max(2, keys)
         self._hint_slots = max(4, 2 * w)           # per window: one stem output per kind of evaluation (shared CFG prefix or not)
-        self._graph_pool = torch.cuda.graph_pool_handle() if w > 1 and torch.cuda.is_available() else None
+        self._tkv_slots = max(6, 2 * self._contexts)
+        self._graph_pool = torch.cuda.graph_pool_handle() if keys > 1 and torch.cuda.is_available() else None
         self.graph_counts = dict(eager=0, capture=0, replay=0)
 
     def _count(self, kind: str) -> None:

@@ -1016,6 +1016,47 @@ def tile_fuse(ys, starts: torch.Tensor, coef: torch.Tensor, height: int, width: 
 
 
 # ------------------------------------------------------------------------------------------
+# Region prompts (csrc/region.hip): blend coefficients from K pixel masks, blend of the K + 1 evaluations (ccedit_amd/regions.py)
+# ------------------------------------------------------------------------------------------
+def region_weights(masks: torch.Tensor, feather: int) -> torch.Tensor:
+    """uint8 (K, T, H, W) pixel masks (>= 128 = this region's prompt; H, W multiples of 8) -> fp32 (K + 1, T, H / 8, W / 8): coef[0] the base
+    prompt's share of every latent cell, coef[r] region r's, from the masks' coverage summed over (2F + 1)^2 cells (regions.py); one
+    launch, bit-equal to tests/_regions_numpy.py.  K, F and the sizes are checked by the entry point."""
+    if masks.dtype != torch.uint8 or not masks.is_cuda or not masks.is_contiguous() or masks.dim() != 4:
+        raise ValueError(f"region_weights: expected a contiguous cuda uint8 (K, T, H, W) tensor, got {masks.dtype} {masks.device} "
+                         f"{tuple(masks.shape)} contiguous={masks.is_contiguous()}")
+    k, t, hh, ww = masks.shape
+    coef = torch.empty((k + 1, t, hh // 8, ww // 8), dtype=torch.float32, device=masks.device)
+    _launch_mem("region_weights", float(masks.numel()) + 4.0 * coef.numel(), lambda: hip.check(hip.lib().ccedit_region_weights(
+        masks.data_ptr(), coef.data_ptr(), k, t, hh, ww, int(feather), _stream()), "ccedit_region_weights"), (k, t, hh, ww, int(feather)))
+    return coef
+
+
+def region_fuse(ys, coef: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The K + 1 evaluations `ys` (each (B, C, T, h, w) fp32, read in place through a device table of their addresses) -> (B, C, T, h, w):
+    out[b, c] = sum over r, ascending, of coef[r] * ys[r][b, c], terms whose coefficient is exactly 0 skipped — product first, then
+    multiply and add per further term, bit-equal to that loop in numpy float32.  `coef`: fp32 (K + 1, T, h, w) on the device."""
+    nr = len(ys)
+    if nr < 1:
+        raise ValueError("region_fuse: no regions")
+    for y in ys:
+        _chk_latent(y, "region_fuse")
+        if y.shape != ys[0].shape or y.device != ys[0].device:
+            raise ValueError(f"region_fuse: regions of different shapes or devices: {tuple(y.shape)} and {tuple(ys[0].shape)}")
+    b, c, t, h, w = ys[0].shape
+    if coef.dtype != torch.float32 or not coef.is_cuda or not coef.is_contiguous() or tuple(coef.shape) != (nr, t, h, w):
+        raise ValueError(f"region_fuse: {nr} regions of {t} frames of {h}x{w} need a contiguous cuda fp32 coef ({nr}, {t}, {h}, {w}); got "
+                         f"{coef.dtype} {coef.device} {tuple(coef.shape)}")
+    y = torch.empty((b, c, t, h, w), dtype=torch.float32, device=ys[0].device) if out is None else out
+    assert y.dtype == torch.float32 and y.is_contiguous() and tuple(y.shape) == (b, c, t, h, w)
+    # the K + 1 addresses change with every evaluation: 8 (K + 1) bytes through pinned memory, not blocking (see window_fuse)
+    table = torch.tensor([v.data_ptr() for v in ys], dtype=torch.int64).pin_memory().to(y.device, non_blocking=True)
+    _launch_mem("region_fuse", 4.0 * (nr * ys[0].numel() + coef.numel() + y.numel()), lambda: hip.check(hip.lib().ccedit_region_fuse(
+        table.data_ptr(), y.data_ptr(), coef.data_ptr(), nr - 1, b, c, t, h * w, _stream()), "ccedit_region_fuse"), (nr, b, c, t, h, w))
+    return y
+
+
+# ------------------------------------------------------------------------------------------
 # Propagation of edited keyframes to every source frame (csrc/propagate.hip; plan, tables and the clip loop: ccedit_amd/propagate.py)
 # ------------------------------------------------------------------------------------------
 def _chk_u8(t: torch.Tensor, name: str, dims: int):

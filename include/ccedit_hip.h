@@ -532,6 +532,30 @@ int ccedit_tile_fuse(const void* yt, float* out, const int32_t* starts, const fl
                      int32_t th, int32_t tw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Regions (added without an ABI bump: two new functions, CCEDIT_ABI_VERSION stays 12).  A prompt per masked region of the frame: at
+ * every network evaluation the network runs once per prompt at its usual shape and the K + 1 denoised latents (region 0 is the base
+ * prompt, which covers what the K regions leave) are blended into one by fixed per-cell coefficients (ccedit_amd/regions.py:
+ * RegionDenoiser; `--region_prompt`, `--region_mask`, `--region_feather`).  Kernels: csrc/region.hip.  1 <= K <= 7, 0 <= F <= 8.  All
+ * pointers are device pointers.
+ *
+ * ccedit_region_weights: masks uint8 [K][T][H][W] (H, W multiples of 8; 8-byte aligned; a pixel is set when its byte is >= 128) ->
+ *   coef fp32 [K + 1][T][h][w], h = H / 8, w = W / 8, one launch.  a_r = set pixels of a latent cell (0 ... 64); s_r = the sum of a_r
+ *   over the (2F + 1) x (2F + 1) cells around it, coordinates clamped into the frame (the edge is replicated, F may exceed h or w);
+ *   tot = sum_r s_r, S = 64 (2F + 1)^2, D = max(S, tot), s_0 = D - tot; coef[r] = (float)((double)s_r / (double)D): formed from integers
+ *   and rounded once per conversion, bit-equal to tests/_regions_numpy.py.  Every cell has a non-zero coefficient; where s_r = D the
+ *   coefficient of r is exactly 1.0f and every other exactly 0.0f.
+ * ccedit_region_fuse: out[b][c][t][p] = sum over r = 0 ... K, ascending, of coef[r][t][p] * y_r[b][c][t][p]; out and y_r are fp32
+ *   [B][C][T][P], P = h w, y_r at yr[r].  `yr` is a DEVICE table of K + 1 pointers (8-byte aligned): the evaluations are read where the
+ *   network left them.  A term whose coefficient is exactly 0 is SKIPPED — its y is not looked at, so a non-finite value of a region
+ *   cannot reach a cell the region does not own; an element whose coefficients are all 0 is written 0.  The first term is the product
+ *   alone, every further term one multiply then one add, never an fma: bit-equal to the same loop in numpy float32, and a cell owned
+ *   by one region (coefficient 1.0f) is a bit copy.  One launch, every output element written once, no atomics; 16-byte accesses
+ *   where P % 4 == 0 and the pointers allow, one element per access otherwise.
+ */
+int ccedit_region_weights(const void* masks, float* coef, int32_t K, int32_t T, int32_t H, int32_t W, int32_t F, void* stream);
+int ccedit_region_fuse(const void* yr, float* out, const float* coef, int32_t K, int32_t B, int32_t C, int32_t T, int64_t P, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Propagation (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  Full-frame-rate output: the edited
  * keyframes are carried to every source frame between them along motion estimated on the source frames (ccedit_amd/propagate.py:
  * plan, tables, propagate_clip; `--propagate`).  Kernels: csrc/propagate.hip.  Everything is integer arithmetic on bytes and equals

@@ -37,6 +37,13 @@ latent of the frame (ccedit_amd/tiles.py, csrc/tile.hip); everything else — in
 every tile), --noise_seed, --gpu_io, masks, the writers — runs on the large latent as on a small one, first-stage encode / decode on whole
 frames in groups sized so that no tensor outgrows a plain clip's at tile size.  Exact arithmetic and known shapes are what is claimed;
 image quality against a direct evaluation at the large size has not been measured.
+`--region_prompt TEXT --region_mask PATH` (a pair per region, up to 7) gives masked regions of the frame prompts of their own — "the bear
+becomes a panda, the background becomes a snow field" in ONE run: at every sampler evaluation the unchanged network is evaluated once
+per prompt (`--prompt` stays the base prompt and covers whatever the regions leave) and the K + 1 denoised latents are fused into one by a
+fixed per-cell blend, feathered over `--region_feather` latent cells (ccedit_amd/regions.py, csrc/region.hip), so there is one latent
+and no seam at any step; a region mask is what --mask_path accepts, or with `--region_track` ONE image painted on source frame
+`--region_frame` and followed through the clip; everything else — inpainting, SDEdit, the prior mix, --window_frames, --tile_h / --tile_w,
+the writers — runs as before.  One clip per invocation; K + 1 network evaluations per sampler evaluation; image quality is not claimed.
 Launched under torch.distributed (RANK / WORLD_SIZE), the chunks are dealt round-robin to the ranks (BASELINE.json config 5:
 independent clips, one per GPU, no collective — ccedit_amd.parallel.shard_clips).
 `--propagate` (job mode, --save_type gif, mjpeg or png) adds the frames BETWEEN the keyframes: every source frame from the first to the last keyframe
@@ -154,6 +161,19 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--tile_overlap", type=int, default=None,
                    help="(not in the reference script) pixels (a multiple of 8, less than the tile) shared by neighbouring tiles, on both axes "
                         "(default: a quarter of the tile per axis, rounded down to a multiple of 8)")
+    p.add_argument("--region_prompt", action="append", default=None,
+                   help="(not in the reference script) the prompt of a masked region of the frame; repeatable, region r is the r-th "
+                        "--region_prompt / --region_mask pair, 1 ... 7 of them.  --prompt stays the base prompt and covers what the regions "
+                        "leave.  Every sampler evaluation runs the network once per prompt and fuses the results (ccedit_amd/regions.py)")
+    p.add_argument("--region_mask", action="append", default=None,
+                   help="the mask of a region, what --mask_path accepts: one image, a .gif / .png sequence or a directory with one mask per "
+                        "frame of the video.  White = this region's prompt.  --mask_dilate / --mask_invert do not apply")
+    p.add_argument("--region_feather", type=int, default=1,
+                   help="latent cells (8 pixels each), 0 ... 8, over which the blend between regions is feathered (default 1; 0 = a hard split)")
+    p.add_argument("--region_track", action="store_true",
+                   help="every --region_mask is ONE image painted on source frame --region_frame and followed through the clip on the device "
+                        "(ccedit_amd/masktrack.py), like --mask_track.  Needs a video and --H, --W multiples of 64")
+    p.add_argument("--region_frame", type=int, default=0, help="with --region_track: the source frame the region masks were painted on")
     p.add_argument("--propagate", action="store_true",
                    help="(not in the reference script) full-frame-rate output: after a clip's keyframes are saved, every source frame from the "
                         "first to the last keyframe gets an edited frame — the two neighbouring edited keyframes carried along the source's "
@@ -217,6 +237,7 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
     if args.save_type == "mjpeg" and (args.H % 16 or args.W % 16):
         p.error(f"--save_type mjpeg codes 16 x 16 MCUs: --H and --W must be multiples of 16 (got {args.H}x{args.W})")
     check_mask_options(args)                 # (--mask_track and its kin: ValueError, here and again where the masks are made)
+    check_region_options(args)               # (--region_prompt and its kin: ValueError; nothing is imported or checked without the flags)
 
 
 def windowing(args) -> bool:
@@ -569,9 +590,109 @@ def all_frame_masks(args, video_path: str, n_all: int, dev):
                                               device=dev, all_frames=True)).contiguous()
 
 
-def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None):
+# ------------------------------------------------------------------------------------------
+# Region prompts: --region_prompt / --region_mask pairs (ccedit_amd/regions.py)
+# ------------------------------------------------------------------------------------------
+def regions_on(args) -> bool:
+    """Regions are active when a region flag was given; otherwise the plain path runs untouched (no import, no launch)."""
+    return bool(getattr(args, "region_prompt", None) or getattr(args, "region_mask", None))
+
+
+def check_region_options(args, with_ref: bool = False) -> None:
+    """Before any GPU work, from the flags alone: what regions cannot do is refused with what to do instead (ValueError;
+    NotImplementedError with a reference image).  Without region flags everything passes."""
+    if not regions_on(args):
+        return
+    if with_ref:
+        raise NotImplementedError("--region_prompt / --region_mask are not available with a reference image (sampling_tv2v_ref.py): the "
+                                  "reference image conditions the whole frame, not a region")
+    from ccedit_amd import regions
+    prompts, masks = list(args.region_prompt or []), list(args.region_mask or [])
+    regions.check_counts(len(prompts), len(masks))
+    regions.check_feather(args.region_feather)
+    if args.H % 8 or args.W % 8:
+        raise ValueError(f"--H {args.H} --W {args.W}: region masks are counted per latent cell of 8 x 8 pixels — frame sides must be multiples of 8")
+    for m in masks:
+        if not os.path.exists(m):
+            raise ValueError(f"--region_mask {m} does not exist: give one image, a .gif / .png sequence or a directory of masks per region")
+    if getattr(args, "region_track", False):
+        from ccedit_amd import masktrack, video_io
+        masktrack.check_size(args.H, args.W, "--region_track")
+        if args.region_frame < 0:
+            raise ValueError(f"--region_frame {args.region_frame} is outside the video: frames count from 0")
+        for m in masks:
+            if video_io.kind_of(m, missing_ok=True) is not None:
+                raise ValueError(f"--region_track follows ONE mask image per region through the clip, but {m} is a mask sequence: give the "
+                                 "mask of frame --region_frame as one image, or drop --region_track to use the sequence as it is")
+        if not (args.video_path or args.video_listpath or args.videos_directory or args.json_path):
+            raise ValueError("--region_track follows the region masks along the source video: give --video_path")
+
+
+def check_region_jobs(args, num_jobs: int) -> None:
+    """Before any GPU work: region masks belong to ONE video, so one job per invocation and one clip per chunk (ValueError)."""
+    if not regions_on(args):
+        return
+    if num_jobs > 1:
+        raise ValueError(f"--region_prompt / --region_mask with {num_jobs} jobs: region masks belong to one video — run one --prompt / "
+                         "--video_path job per invocation")
+    if args.batch_size > 1 and num_jobs * args.num_samples > 1:
+        raise ValueError(f"--region_prompt / --region_mask with --batch_size {args.batch_size} and {num_jobs * args.num_samples} clips: a chunk "
+                         "of several clips shares one conditioning batch, region masks belong to one clip — add --batch_size 1")
+
+
+def region_pixel_masks(args, video_path: str, dev):
+    """The K region masks of the clip -> uint8 (K, T, H, W) on `dev`, 0 / 255, with the keyframe index rule and nearest resize of the edit
+    mask (load_video_mask); --region_track: each ONE image painted on --region_frame, tracked through all source frames (the refusals
+    of --mask_track), the keyframes' masks taken at keyframe_indices.  --mask_dilate / --mask_invert do not apply."""
+    from scripts.sampling.util import count_video_frames, keyframe_indices, load_video_frames_u8, load_video_mask
+    check_region_options(args)
+    video = resolve_video(video_path) if video_path else ""
+    out = []
+    if getattr(args, "region_track", False):
+        from ccedit_amd import masktrack
+        if not video:
+            raise ValueError("--region_track follows the region masks along the source video: give --video_path")
+        source = load_video_frames_u8(video, (args.H, args.W), dev, **_gif_decoder(args))
+        masktrack.chain(source.shape[0], args.region_frame)                              # (--region_frame outside the video: refused here)
+        idx = keyframe_indices(source.shape[0], args.original_fps, args.target_fps, args.num_keyframes)
+        idx = torch.from_numpy(idx.astype("int64")).to(dev)
+        for m in args.region_mask:
+            anchor = load_video_mask(m, args.original_fps, args.target_fps, 1, (args.H, args.W), device=dev)[0]
+            out.append(masktrack.track_clip(source, anchor.contiguous(), args.region_frame)[idx])
+    else:
+        n_all = count_video_frames(video) if video and (os.path.isdir(video) or video.endswith((".gif", ".avi"))) else None
+        for m in args.region_mask:
+            out.append(load_video_mask(m, args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all, **_io_device(args)))
+    return torch.stack([m.to(dev) for m in out], dim=0).contiguous()
+
+
+def region_setup(args, model, dev, batch, batch_uc, c, video_path: str) -> dict:
+    """regions= of sample_one for one clip: {} without region flags, else the K + 1 conditional contexts (the base prompt's first; the
+    region prompts through job_text and the conditioner like the main prompt) and the device table of blend coefficients."""
+    if not regions_on(args):
+        return {}
+    from ccedit_amd import regions
+    if c["crossattn"].shape[0] != 1:
+        raise ValueError(f"--region_prompt / --region_mask with a chunk of {c['crossattn'].shape[0]} clips: region masks belong to one clip — "
+                         "add --batch_size 1")
+    contexts = [c["crossattn"]]
+    for q in args.region_prompt:
+        txt, _ = job_text(args, [q], dev, args.context_dim)
+        cr, _ = model.conditioner.get_unconditional_conditioning(dict(batch, txt=txt), batch_uc=batch_uc)
+        contexts.append(cr["crossattn"][:1].to(dev))
+    coef = regions.weights(region_pixel_masks(args, video_path, dev), args.region_feather)
+    return dict(contexts=contexts, coef=coef)
+
+
+def region_log(args) -> list:
+    """log_info.json `regions`: what every region was given."""
+    return [dict(prompt=q, mask=m, feather=int(args.region_feather), tracked=bool(getattr(args, "region_track", False)))
+            for q, m in zip(args.region_prompt, args.region_mask)]
+
+
+def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, regions=None):
     """sampling_tv2v.py:361-468 for one chunk: the sampled latent.  `mask`: the uint8 LATENT mask (bs, T, H / 8, W / 8) of
-    --inpainting_mode (ops.mask_latent of the pixel masks; 1 = edit)."""
+    --inpainting_mode (ops.mask_latent of the pixel masks; 1 = edit).  `regions`: region_setup's dict (region prompts), or nothing."""
     from scripts.sampling.util import init_sampling, prior_latent, sdedit_start
 
     def denoiser(inp, sigma, cc):
@@ -596,6 +717,12 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
         denoiser = tiles.TiledDenoiser(denoiser, (lth, ltw), (loh, low), wrapper=model.model,
                                        window=args.window_frames if windowing(args) else 0, window_overlap=args.window_overlap)
         model = GroupedFirstStage(model, first_stage_frames(args))
+
+    if regions:                  # a prompt per region: the OUTERMOST wrapper, around the plain, the windowed or the tiled closure
+        from ccedit_amd.regions import RegionDenoiser
+        if ref is not None:
+            raise NotImplementedError("--region_prompt / --region_mask are not available with a reference image: it conditions the whole frame")
+        denoiser = RegionDenoiser(denoiser, regions["contexts"], regions["coef"], wrapper=model.model)      # (the grouped first stage hands .model on)
 
     inpaint = getattr(args, "inpainting_mode", False)
     if inpaint and mask is None:
@@ -629,10 +756,11 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
         return run(sampler, sdedit_start(model, sampler, keyframes))
 
 
-def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, mask_px=None):
+def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, mask_px=None, regions=None):
     """sampling_tv2v.py:361-470 for one chunk: sample, decode and — with --mask_composite and the pixel masks `mask_px` — put the
     original pixels back outside the mask (ccedit_mask_composite)."""
-    z = sample_latent(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=prior_type, mask=mask)
+    extra = dict(regions=regions) if regions else {}
+    z = sample_latent(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=prior_type, mask=mask, **extra)
     if tiling(args) or windowing(args):
         from ccedit_amd.windows import GroupedFirstStage
         model = GroupedFirstStage(model, first_stage_frames(args) if tiling(args) else args.window_frames)
@@ -801,11 +929,13 @@ def run_jobs(args, with_ref: bool = False) -> None:
     import json
     check_windowing(args, with_ref)
     check_tiling(args, with_ref)
+    check_region_options(args, with_ref)
     from ccedit_amd.parallel import shard_clips
     from scripts.sampling.util import chunk, load_img, load_video_keyframes, model_load_ckpt, perform_save_locally_video
     prompts, video_paths, video_save_paths, ref_paths = expand_jobs(args, with_ref)
     num_samples, batch_size = args.num_samples, args.batch_size
     check_propagate(args, video_paths)
+    check_region_jobs(args, len(prompts))
     print("\nNumber of prompts: {}".format(len(prompts)))
     print("Generate {} samples for each prompt".format(num_samples))
     rep = lambda lst: [item for item in lst for _ in range(num_samples)]
@@ -888,9 +1018,10 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 from ccedit_amd import ops
                 mask_px = clip_masks(args, cvideos, dev)
                 mask_lat = ops.mask_latent(mask_px)
+            region_kw = dict(regions=region_setup(args, model, dev, batch, batch_uc, c, cvideos[0])) if regions_on(args) else {}
             t0 = time.time()
             samples = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref,
-                                 prior_type=getattr(args, "prior_type", "video"), mask=mask_lat, mask_px=mask_px)
+                                 prior_type=getattr(args, "prior_type", "video"), mask=mask_lat, mask_px=mask_px, **region_kw)
             torch.cuda.synchronize()
             print(f"chunk {idx}: {bs} clip(s) of {T} frames {H}x{W} in {time.time() - t0:.2f}s")
             to01 = lambda v: (torch.clamp(v.float(), -1.0, 1.0) + 1.0) / 2.0
@@ -913,6 +1044,8 @@ def run_jobs(args, with_ref: bool = False) -> None:
             print("Saved samples to {}. Enjoy.".format(save_path))
             log_info["video_paths"] += cvideos
             log_info["keyframes_paths"] += keyframes_paths
+            if regions_on(args):
+                log_info["regions"] = region_log(args)
             os.makedirs(os.path.dirname(log_path), exist_ok=True)
             for out in {log_path, os.path.join(save_path, log_name)}:    # (the reference writes it under save_path; the loop reads it per base model)
                 os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -944,6 +1077,7 @@ def main():
         return run_jobs(args)
     check_windowing(args)
     check_tiling(args)
+    check_region_jobs(args, 1)
     from scripts.sampling.util import ResumeLog, save_frames
     model, dev = build_model(args)
     T, h, w = args.num_keyframes, args.H // 8, args.W // 8
@@ -957,6 +1091,8 @@ def main():
     batch_uc = {"txt": txt_uc, "control_hint": hint.clone()}                              # uc keeps the SAME hint (:339-344)
     c, uc = model.conditioner.get_unconditional_conditioning(batch, batch_uc=batch_uc)
     keyframes = cond["keyframes"].to(dev) if need_frames else None
+    if regions_on(args):
+        masks["regions"] = region_setup(args, model, dev, batch, batch_uc, c, args.video_path)
     log = ResumeLog(args.save_path)
     for i in range(args.num_samples):
         tag = f"sample_{i:04d}"
@@ -968,6 +1104,8 @@ def main():
         torch.cuda.synchronize()
         save_result(args, tag, x)
         print(f"{tag}: {T} frames {args.H}x{args.W} in {time.time() - t0:.2f}s")
+        if regions_on(args):
+            log.log["regions"] = region_log(args)
         log.add(tag)
 
 
