@@ -26,6 +26,8 @@ bool cc_attn_short_applicable(const CcAttnDesc& a);      // attnshort.hip
 int cc_attn_short_launch(const CcAttnDesc& a, hipStream_t s);
 bool cc_attn_text_applicable(const CcAttnDesc& a);       // attntext.hip
 int cc_attn_text_launch(const CcAttnDesc& a, hipStream_t s);
+bool cc_attn_text_long_applicable(const CcAttnDesc& a);  // attntextlong.hip
+int cc_attn_text_long_launch(const CcAttnDesc& a, hipStream_t s);
 bool cc_attn_spatial_applicable(const CcAttnDesc& a);    // attnspatial.hip
 int cc_attn_spatial_launch(const CcAttnDesc& a, hipStream_t s);
 
@@ -398,6 +400,8 @@ extern "C" int ccedit_attention(const CcAttnDesc* desc, void* stream) {
     if (cc_policy().attn_short && plain_q && cc_attn_short_applicable(a)) return cc_attn_short_launch(a, s);
     // text cross-attention (<= 96 keys shared by the frames of a clip): bound by streaming the query rows, own kernel (attntext.hip)
     if (cc_policy().attn_text && plain_q && cc_attn_text_applicable(a)) return cc_attn_text_launch(a, s);
+    // ... and onto the 154 / 231 / 308 keys of a long prompt, under the same switch (attntextlong.hip)
+    if (cc_policy().attn_text && plain_q && cc_attn_text_long_applicable(a)) return cc_attn_text_long_launch(a, s);
     // long self-attention at d = 40 (the 64x96 level): the softmax arithmetic is the bound, own kernel (attnspatial.hip)
     if (cc_policy().attn_spatial && cc_attn_spatial_applicable(a)) return cc_attn_spatial_launch(a, s);
     switch (a.d) {

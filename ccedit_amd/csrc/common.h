@@ -194,6 +194,9 @@ int cc_tile_fuse(const float* const* yt, float* out, const int32_t* starts, cons
 int cc_region_weights(const uint8_t* masks, float* coef, int32_t K, int32_t T, int32_t H, int32_t W, int32_t F, hipStream_t s);
 int cc_region_fuse(const float* const* yr, float* out, const float* coef, int32_t K, int64_t BC, int32_t T, int64_t P, hipStream_t s);
 
+// Weighted prompts (prompt.hip); entry point and argument checks in core.cpp
+int cc_prompt_weight(const float* z, const float* e, const float* w, float* out, int64_t R, int32_t C, hipStream_t s);
+
 // Propagation launchers (propagate.hip); entry points and argument checks in core.cpp
 int cc_prop_pyramid(const uint8_t* rgb, uint8_t* pyr, int32_t F, int32_t H, int32_t W, hipStream_t s);
 int cc_prop_match(const uint8_t* lum, const int32_t* pairs, const int32_t* rank, const int32_t* parent, int32_t* out, int32_t P, int32_t F,

@@ -284,6 +284,18 @@ extern "C" int ccedit_region_fuse(const void* yr, float* out, const float* coef,
     return cc_region_fuse((const float* const*)yr, out, coef, K, (int64_t)B * C, T, P, (hipStream_t)stream);
 }
 
+// ---- weighted prompts (kernel and launcher: prompt.hip).  Everything the host can see is checked here, before any HIP call; the kernel
+// reads e at (row mod 77) and everything else at the output's own index.
+extern "C" int ccedit_prompt_weight(const float* z, const float* e, const float* w, float* out, int32_t B, int32_t L, int32_t C, void* stream) {
+    CC_CHECK_ARG(z && e && w && out, "ccedit_prompt_weight: null pointer");
+    CC_CHECK_ARG(B > 0 && C > 0 && L > 0 && L % 77 == 0, "ccedit_prompt_weight: B=%d L=%d C=%d (positive, L a multiple of 77: whole CLIP chunks)", B, L,
+                 C);
+    CC_CHECK_ARG((int64_t)B * L * C < kPixelMax * 4, "ccedit_prompt_weight: more than 2^33 elements in one call (B=%d L=%d C=%d)", B, L, C);
+    CC_CHECK_ARG(((uintptr_t)z & 3) == 0 && ((uintptr_t)e & 3) == 0 && ((uintptr_t)w & 3) == 0 && ((uintptr_t)out & 3) == 0,
+                 "ccedit_prompt_weight: z, e, w and out must be 4-byte aligned");
+    return cc_prompt_weight(z, e, w, out, (int64_t)B * L, C, (hipStream_t)stream);
+}
+
 // ---- propagation of edited keyframes to every source frame (kernels and launchers: propagate.hip).  Everything the host can see is
 // checked here, before any HIP call; the device tables (pairs, rank, g, the block vectors) are held in range by the kernels themselves.
 static int prop_shape_ok(const char* fn, int32_t P, int32_t F, int32_t H, int32_t W) {

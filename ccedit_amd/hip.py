@@ -161,6 +161,8 @@ _SIGS = {
     # region prompts (csrc/region.hip): added within ABI 12, nothing existing changed
     "ccedit_region_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ccedit_region_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
+    # weighted prompts (csrc/prompt.hip): added within ABI 12, nothing existing changed
+    "ccedit_prompt_weight": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     # propagation of edited keyframes (csrc/propagate.hip): added within ABI 12, nothing existing changed
     "ccedit_prop_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ccedit_prop_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -1057,6 +1057,30 @@ def region_fuse(ys, coef: torch.Tensor, out: Optional[torch.Tensor] = None) -> t
 
 
 # ------------------------------------------------------------------------------------------
+# Weighted prompts (csrc/prompt.hip): the emphasis rule on the text encoder's output (ccedit_amd/prompt.py)
+# ------------------------------------------------------------------------------------------
+def prompt_weight(z: torch.Tensor, e: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z fp32 (B, 77 n, C), e fp32 (77, C) the empty chunk's encoding, w fp32 (B, 77 n) -> e[t mod 77] + w * (z - e[t mod 77]) per row:
+    fp32 subtract, multiply, add, bit-equal to tests/_prompt_numpy.py; a row with w == 1 is a bit copy of z.  `out` may be z itself.
+    Weights that are not finite are refused here (one reduction of 77 n B floats and one read-back, once per prompt)."""
+    for name, tns in (("z", z), ("e", e), ("w", w), ("out", out)):
+        if tns is not None and (tns.dtype != torch.float32 or not tns.is_cuda or not tns.is_contiguous()):
+            raise ValueError(f"prompt_weight: {name} must be a contiguous cuda fp32 tensor, got {tns.dtype} {tns.device} "
+                             f"contiguous={tns.is_contiguous()}")
+    if z.dim() != 3 or z.shape[1] % 77 or tuple(e.shape) != (77, z.shape[2]) or tuple(w.shape) != tuple(z.shape[:2]):
+        raise ValueError(f"prompt_weight: z (B, 77 n, C), e (77, C) and w (B, 77 n) expected; got {tuple(z.shape)}, {tuple(e.shape)}, {tuple(w.shape)}")
+    if out is not None and tuple(out.shape) != tuple(z.shape):
+        raise ValueError(f"prompt_weight: out {tuple(out.shape)} is not z's shape {tuple(z.shape)}")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("prompt_weight: a weight is NaN or infinite")
+    b, l, c = z.shape
+    y = torch.empty_like(z) if out is None else out
+    _launch_mem("prompt_weight", 4.0 * (2 * z.numel() + e.numel() + w.numel()), lambda: hip.check(hip.lib().ccedit_prompt_weight(
+        z.data_ptr(), e.data_ptr(), w.data_ptr(), y.data_ptr(), b, l, c, _stream()), "ccedit_prompt_weight"), (b, l, c))
+    return y
+
+
+# ------------------------------------------------------------------------------------------
 # Propagation of edited keyframes to every source frame (csrc/propagate.hip; plan, tables and the clip loop: ccedit_amd/propagate.py)
 # ------------------------------------------------------------------------------------------
 def _chk_u8(t: torch.Tensor, name: str, dims: int):

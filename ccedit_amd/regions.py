@@ -67,7 +67,7 @@ def weights(masks: torch.Tensor, feather: int = DEFAULT_FEATHER) -> torch.Tensor
 
 class RegionDenoiser:
     """`denoiser(input, sigma, cond)` with a text context per region: input (2, 4, T, h, w), CFG-doubled by the guider; `contexts` the
-    K + 1 conditional `crossattn` tensors (1, 77, C), region 0 (the base prompt) first; `coef` the device table of weights().
+    K + 1 conditional `crossattn` tensors (1, L, C) of ONE length L (77, or 77 n with long prompts), region 0 (the base prompt) first; `coef` the device table of weights().
 
     Per clip, not per evaluation: K + 1 stable doubled `crossattn` tensors — the unconditional half of cond['crossattn'] followed by
     region r's context — made once per source tensor (keyed by identity + in-place version, the entry pins the source: the discipline

@@ -556,6 +556,21 @@ int ccedit_region_weights(const void* masks, float* coef, int32_t K, int32_t T, 
 int ccedit_region_fuse(const void* yr, float* out, const float* coef, int32_t K, int32_t B, int32_t C, int32_t T, int64_t P, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Prompts (added without an ABI bump: one new function, CCEDIT_ABI_VERSION stays 12).  Long and weighted prompts: a prompt is cut into
+ * n <= 4 chunks of 77 CLIP tokens, every chunk goes through the text encoder on its own and the rows are laid side by side — a context
+ * of L = 77 n rows (ccedit_amd/prompt.py; `--prompt_chunks`, `--prompt_syntax weighted`).  Kernel: csrc/prompt.hip.  All pointers are
+ * device pointers.
+ *
+ * ccedit_prompt_weight: out[b][t][c] = e[t mod 77][c] + w[b][t] * (z[b][t][c] - e[t mod 77][c]); z and out fp32 [B][L][C], L a multiple
+ *   of 77; e fp32 [77][C], the encoding of the empty chunk (BOS, EOS x 76); w fp32 [B][L], the weight of every token.  fp32 subtract,
+ *   multiply, add in that order, each rounded, never an fma: bit-equal to tests/_prompt_numpy.py.  A row with w == 1.0f is a BIT COPY of
+ *   z (e + (z - e) is not z in floating point).  No reduction: a row depends on nothing but itself.  out may be z.  w is data: it must
+ *   be finite (the Python wrapper refuses NaN / inf; the kernel has no index that depends on it).  One launch; 16-byte accesses where
+ *   C % 4 == 0 and the pointers allow, one element per access otherwise.
+ */
+int ccedit_prompt_weight(const float* z, const float* e, const float* w, float* out, int32_t B, int32_t L, int32_t C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Propagation (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  Full-frame-rate output: the edited
  * keyframes are carried to every source frame between them along motion estimated on the source frames (ccedit_amd/propagate.py:
  * plan, tables, propagate_clip; `--propagate`).  Kernels: csrc/propagate.hip.  Everything is integer arithmetic on bytes and equals

@@ -44,6 +44,12 @@ fixed per-cell blend, feathered over `--region_feather` latent cells (ccedit_amd
 and no seam at any step; a region mask is what --mask_path accepts, or with `--region_track` ONE image painted on source frame
 `--region_frame` and followed through the clip; everything else — inpainting, SDEdit, the prior mix, --window_frames, --tile_h / --tile_w,
 the writers — runs as before.  One clip per invocation; K + 1 network evaluations per sampler evaluation; image quality is not claimed.
+`--prompt_chunks N` (1 ... 4) lets every prompt of the run — positive, negative, region prompts, the job lists' — use up to N chunks of
+77 tokens instead of being truncated at 75 tokens: chunks end after a nearby comma or at the word BREAK, every chunk is encoded on its
+own and the network sees a context of 77 n rows, one n for all prompts of a clip (ccedit_amd/prompt.py); a prompt that needs more is
+refused.  `--prompt_syntax weighted` reads `(x)`, `[x]`, `(x:1.3)` as emphasis, applied to the text encoder's output (csrc/prompt.hip).
+Conditioning files may hold `tokens` / `tokens_uc` of (1, 77 n) and `token_weights` / `token_weights_uc`; log_info.json gains `prompts`.
+With the defaults (1, plain) the text path is the one it was; a prompt it truncates is announced by one `[prompt]` line on stderr.
 Launched under torch.distributed (RANK / WORLD_SIZE), the chunks are dealt round-robin to the ranks (BASELINE.json config 5:
 independent clips, one per GPU, no collective — ccedit_amd.parallel.shard_clips).
 `--propagate` (job mode, --save_type gif, mjpeg or png) adds the frames BETWEEN the keyframes: every source frame from the first to the last keyframe
@@ -119,6 +125,15 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="directory with the CLIP tokenizer files (vocab.json, merges.txt) of openai/clip-vit-large-patch14: with it "
                         "--prompt / --negative_prompt / --add_prompt are tokenised here as in the reference script; without it the "
                         "conditioning tensors must carry token ids or embeddings (--cond_path)")
+    p.add_argument("--prompt_chunks", type=int, default=1, choices=[1, 2, 3, 4],
+                   help="(not in the reference script, which truncates at 75 tokens) the largest number of 77-token chunks a prompt may use, "
+                        "1 ... 4: a longer prompt is cut into chunks (after a comma where one is near, or at the word BREAK), every chunk is "
+                        "encoded on its own and the network sees a context of 77 n rows (ccedit_amd/prompt.py).  A prompt that needs more "
+                        "chunks is refused, never truncated.  Applies to every prompt of the run.  1 (default): the path as before")
+    p.add_argument("--prompt_syntax", type=str, default="plain", choices=["plain", "weighted"],
+                   help="(not in the reference script) weighted: (x) multiplies the emphasis of x by 1.1, [x] divides it by 1.1, (x:1.3) sets "
+                        "a factor in [0, 8], nesting multiplies, a backslash before a bracket or a backslash makes it a literal; the weights "
+                        "act on the text encoder's output (csrc/prompt.hip).  plain (default): brackets are text, as before")
     p.add_argument("--sample_steps", type=int, default=50)
     p.add_argument("--sampler_name", type=str, default="EulerEDMSampler")       # the reference script's default
     p.add_argument("--discretization_name", type=str, default="LegacyDDPMDiscretization")
@@ -414,7 +429,8 @@ def conditioning_tensors(args, g: torch.Generator, need_frames: bool, need_ref: 
         cond = load_conditioning(args.cond_path)
     else:
         if args.context_dim == 768:      # shipped configs: seeded random token ids through the CLIP text encoder
-            text = dict(tokens=torch.randint(0, 49406, (1, 77), generator=g), tokens_uc=torch.randint(0, 49406, (1, 77), generator=g))
+            nl = 77 * int(getattr(args, "prompt_chunks", 1) or 1)       # --prompt_chunks N: ids of N chunks
+            text = dict(tokens=torch.randint(0, 49406, (1, nl), generator=g), tokens_uc=torch.randint(0, 49406, (1, nl), generator=g))
         else:                            # reduced test configs: a precomputed embedding of the network's context width
             text = dict(crossattn=torch.randn(1, 77, args.context_dim, generator=g),
                         crossattn_uc=torch.randn(1, 77, args.context_dim, generator=g))
@@ -460,6 +476,120 @@ def text_inputs(cond, dev, args=None):
     if "tokens" in cond:
         return cond["tokens"].to(dev), cond["tokens_uc"].to(dev)
     return cond["crossattn"].to(dev), cond["crossattn_uc"].to(dev)
+
+
+# ------------------------------------------------------------------------------------------
+# Long and weighted prompts: --prompt_chunks / --prompt_syntax (ccedit_amd/prompt.py)
+# ------------------------------------------------------------------------------------------
+def prompts_on(args) -> bool:
+    """The new text path runs when a flag asks for it; with the defaults (1 chunk, plain) nothing of it is imported or called."""
+    return int(getattr(args, "prompt_chunks", 1) or 1) != 1 or getattr(args, "prompt_syntax", "plain") != "plain"
+
+
+def _text_embedder(model):
+    """The conditioner's CLIP embedder (input key `txt`)."""
+    for emb in model.conditioner.embedders:
+        if getattr(emb, "input_key", None) == "txt" and hasattr(emb, "encode_long"):
+            return emb
+    raise NotImplementedError("--prompt_chunks / --prompt_syntax: the config has no CLIP text embedder on `txt`")
+
+
+def compose_prompt(args, q: str) -> str:
+    """sampling_tv2v.py:334-347: add_prompt + ", " + prompt."""
+    return args.add_prompt + ", " + q if args.add_prompt else q
+
+
+def warn_truncated(args, model, texts) -> None:
+    """The old path (1 chunk, plain, a tokenizer): a prompt whose tokens exceed 75 is truncated as in the reference — one line on
+    stderr says so.  Nothing else changes."""
+    if prompts_on(args) or not getattr(args, "tokenizer_path", ""):
+        return
+    tok = _text_embedder(model).tokenizer()
+    for t in texts:
+        count = len(tok(t, add_special_tokens=False)["input_ids"])
+        if count > 75:
+            print(f"[prompt] {count} tokens, the text encoder sees 75: the rest of {t[:40]!r}... is dropped — --prompt_chunks "
+                  f"{min(-(-count // 75), 4)} keeps it", file=sys.stderr)
+
+
+def long_text(args, model, dev, full, neg, region=()):
+    """The new text path for one chunk of clips.  `full`, `neg`: the composed prompts and the negative prompts, one per clip; `region`:
+    the composed region prompts of the clip.  Every prompt is cut into chunks, all get ONE length 77 n, and the embedder encodes them
+    chunk by chunk (weighted: with the emphasis rule).  Returns (txt, txt_uc, [txt of every region], per-clip log entries): txt are
+    finished (bs, 77 n, C) embeddings, which the conditioner hands through.  Every refusal is raised before the first launch."""
+    import zlib
+    from ccedit_amd import prompt
+    prompt.check_options(args.prompt_chunks, args.prompt_syntax)
+    weighted = args.prompt_syntax == "weighted"
+    names = ([f"--prompt ({i + 1} of {len(full)})" if len(full) > 1 else "--prompt" for i in range(len(full))]
+             + [f"--negative_prompt ({i + 1} of {len(neg)})" if len(neg) > 1 else "--negative_prompt" for i in range(len(neg))]
+             + [f"--region_prompt {r + 1}" for r in range(len(region))])
+    texts = list(full) + list(neg) + list(region)
+    if args.tokenizer_path:
+        emb = _text_embedder(model)
+        enc = prompt.encode_prompts(emb.tokenizer(), dict(zip(names, texts)), args.prompt_chunks, args.prompt_syntax)
+        n = enc["n"]
+
+        def encode(sel):
+            tokens = torch.cat([enc[k]["tokens"] for k in sel]).to(dev)
+            weights = torch.cat([enc[k]["weights"] for k in sel]).to(dev) if weighted else None
+            return emb.encode_long(tokens, weights)
+        counts = {k: (enc[k]["prompt_tokens"], enc[k]["prompt_chunks"]) for k in names}
+    else:
+        if not args.synthetic:
+            raise SystemExit("prompts need --tokenizer_path (vocab.json / merges.txt of openai/clip-vit-large-patch14), or --synthetic")
+        n = int(args.prompt_chunks)
+        for k, t in zip(names, texts):                       # the grammar is still checked; without a vocabulary there are no weights
+            try:
+                prompt.parse(t, args.prompt_syntax)
+            except ValueError as e:
+                raise ValueError(f"{k}: {e}") from None
+        by_name = dict(zip(names, texts))
+
+        def encode(sel):
+            rows = []
+            for k in sel:
+                g = torch.Generator().manual_seed(zlib.crc32(by_name[k].encode("utf-8")) & 0x7FFFFFFF)
+                if args.context_dim == 768:
+                    rows.append(torch.randint(0, 49406, (1, 77 * n), generator=g))
+                else:
+                    rows.append(torch.randn(1, 77 * n, args.context_dim, generator=g))
+            rows = torch.cat(rows).to(dev)
+            return _text_embedder(model).encode_long(rows) if args.context_dim == 768 else rows
+        counts = {k: (None, n) for k in names}
+    nf = len(full)
+    txt = encode(names[:nf]) if nf else None
+    txt_uc = encode(names[nf:nf + len(neg)]) if neg else None
+    region_txt = [encode([k]) for k in names[nf + len(neg):]]
+    log = [dict(prompt_tokens=counts[names[i]][0], prompt_chunks=counts[names[i]][1], negative_prompt_tokens=counts[names[nf + i]][0],
+                negative_prompt_chunks=counts[names[nf + i]][1], context_rows=77 * n) for i in range(nf)]
+    return txt, txt_uc, region_txt, log
+
+
+def cond_text(args, model, cond, dev):
+    """The text of the tensor mode through the new path when ids of a conditioning file ask for it: `tokens` / `tokens_uc` of (1, 77 n),
+    n <= 4, optionally `token_weights` / `token_weights_uc` fp32 of the same shape.  The halves are padded to one n with empty chunks.
+    Returns (txt, txt_uc, log entries) or None: the old path."""
+    if "tokens" not in cond or getattr(args, "tokenizer_path", ""):
+        return None
+    long = cond["tokens"].shape[-1] != 77 or cond["tokens_uc"].shape[-1] != 77 or "token_weights" in cond or "token_weights_uc" in cond
+    if not (long or prompts_on(args)):
+        return None
+    from ccedit_amd import prompt
+    emb = _text_embedder(model)
+    tc, wc = cond["tokens"], cond.get("token_weights")
+    tu, wu = cond["tokens_uc"], cond.get("token_weights_uc")
+    nc, nu = prompt.check_tokens(tc, wc, "tokens / token_weights"), prompt.check_tokens(tu, wu, "tokens_uc / token_weights_uc")
+    n = max(nc, nu)
+    bos, eos = emb.special_ids()
+    if (wc is None) != (wu is None):                         # one half weighted: the other's tokens all weigh 1
+        wc = torch.ones(tc.shape, dtype=torch.float32) if wc is None else wc
+        wu = torch.ones(tu.shape, dtype=torch.float32) if wu is None else wu
+    tc, wc = prompt.pad_tokens(tc, wc, n, bos, eos)
+    tu, wu = prompt.pad_tokens(tu, wu, n, bos, eos)
+    txt = emb.encode_long(tc.to(dev), None if wc is None else wc.to(dev))
+    txt_uc = emb.encode_long(tu.to(dev), None if wu is None else wu.to(dev))
+    return txt, txt_uc, [dict(prompt_tokens=None, prompt_chunks=nc, negative_prompt_tokens=None, negative_prompt_chunks=nu, context_rows=77 * n)]
 
 
 def save_result(args, tag, x):
@@ -666,7 +796,7 @@ def region_pixel_masks(args, video_path: str, dev):
     return torch.stack([m.to(dev) for m in out], dim=0).contiguous()
 
 
-def region_setup(args, model, dev, batch, batch_uc, c, video_path: str) -> dict:
+def region_setup(args, model, dev, batch, batch_uc, c, video_path: str, region_txt=None) -> dict:
     """regions= of sample_one for one clip: {} without region flags, else the K + 1 conditional contexts (the base prompt's first; the
     region prompts through job_text and the conditioner like the main prompt) and the device table of blend coefficients."""
     if not regions_on(args):
@@ -676,8 +806,8 @@ def region_setup(args, model, dev, batch, batch_uc, c, video_path: str) -> dict:
         raise ValueError(f"--region_prompt / --region_mask with a chunk of {c['crossattn'].shape[0]} clips: region masks belong to one clip — "
                          "add --batch_size 1")
     contexts = [c["crossattn"]]
-    for q in args.region_prompt:
-        txt, _ = job_text(args, [q], dev, args.context_dim)
+    for r, q in enumerate(args.region_prompt):               # (region_txt: long_text's, one length for all the clip's prompts)
+        txt = region_txt[r] if region_txt is not None else job_text(args, [q], dev, args.context_dim)[0]
         cr, _ = model.conditioner.get_unconditional_conditioning(dict(batch, txt=txt), batch_uc=batch_uc)
         contexts.append(cr["crossattn"][:1].to(dev))
     coef = regions.weights(region_pixel_masks(args, video_path, dev), args.region_feather)
@@ -996,7 +1126,14 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 continue
             keyframes = torch.cat(kfs, dim=0).to(dev)                    # (bs, 3, T, H, W) in [-1, 1]
             depth = torch.cat([depth_frames(args, v, k) for v, k in zip(cvideos, kfs)], dim=0).to(dev)
-            txt, txt_uc = job_text(args, cprompts, dev, args.context_dim)
+            region_txt = prompt_log = None
+            if prompts_on(args):     # every prompt of the chunk in chunks of 77 tokens, one length for all (refusals before any launch)
+                txt, txt_uc, region_txt, prompt_log = long_text(args, model, dev, [compose_prompt(args, q) for q in cprompts],
+                                                                [args.negative_prompt for _ in cprompts],
+                                                                [compose_prompt(args, q) for q in (args.region_prompt or [])])
+            else:
+                txt, txt_uc = job_text(args, cprompts, dev, args.context_dim)
+                warn_truncated(args, model, txt + txt_uc[:1] if args.tokenizer_path else [])
             if args.gpu_io:          # raw depth -> finished hint by the kernels; the embedder passes a finished hint through
                 depth = _hint_embedder(model).normalize_gpu(depth)
             batch = {"txt": txt, "control_hint": depth}
@@ -1018,7 +1155,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 from ccedit_amd import ops
                 mask_px = clip_masks(args, cvideos, dev)
                 mask_lat = ops.mask_latent(mask_px)
-            region_kw = dict(regions=region_setup(args, model, dev, batch, batch_uc, c, cvideos[0])) if regions_on(args) else {}
+            region_kw = dict(regions=region_setup(args, model, dev, batch, batch_uc, c, cvideos[0], region_txt)) if regions_on(args) else {}
             t0 = time.time()
             samples = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref,
                                  prior_type=getattr(args, "prior_type", "video"), mask=mask_lat, mask_px=mask_px, **region_kw)
@@ -1046,6 +1183,9 @@ def run_jobs(args, with_ref: bool = False) -> None:
             log_info["keyframes_paths"] += keyframes_paths
             if regions_on(args):
                 log_info["regions"] = region_log(args)
+            if prompt_log is not None:
+                log_info.setdefault("prompts", [])
+                log_info["prompts"] += prompt_log
             os.makedirs(os.path.dirname(log_path), exist_ok=True)
             for out in {log_path, os.path.join(save_path, log_name)}:    # (the reference writes it under save_path; the loop reads it per base model)
                 os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -1086,13 +1226,28 @@ def main():
     masks = single_clip_masks(args, dev)
     cond = conditioning_tensors(args, g, need_frames)
     hint = cond["control_hint"].to(dev)
-    txt, txt_uc = text_inputs(cond, dev, args)
+    region_txt = prompt_log = None
+    if prompts_on(args) and args.tokenizer_path:
+        txt, txt_uc, region_txt, prompt_log = long_text(args, model, dev, [compose_prompt(args, args.prompt)], [args.negative_prompt],
+                                                        [compose_prompt(args, q) for q in (args.region_prompt or [])])
+    else:
+        long = cond_text(args, model, cond, dev)         # ids of (1, 77 n) from --cond_path or --synthetic; None: the path as before
+        if long is None:
+            txt, txt_uc = text_inputs(cond, dev, args)
+            warn_truncated(args, model, txt + txt_uc if args.tokenizer_path else [])
+        else:
+            txt, txt_uc, prompt_log = long
+            if regions_on(args):
+                if txt.shape[1] != 77 * args.prompt_chunks:
+                    raise ValueError(f"--region_prompt with ids of {txt.shape[1] // 77} chunks: the region prompts get --prompt_chunks "
+                                     f"{args.prompt_chunks} chunks here — all contexts of a clip need one length")
+                region_txt = long_text(args, model, dev, [], [], [compose_prompt(args, q) for q in args.region_prompt])[2]
     batch = {"txt": txt, "control_hint": hint}
     batch_uc = {"txt": txt_uc, "control_hint": hint.clone()}                              # uc keeps the SAME hint (:339-344)
     c, uc = model.conditioner.get_unconditional_conditioning(batch, batch_uc=batch_uc)
     keyframes = cond["keyframes"].to(dev) if need_frames else None
     if regions_on(args):
-        masks["regions"] = region_setup(args, model, dev, batch, batch_uc, c, args.video_path)
+        masks["regions"] = region_setup(args, model, dev, batch, batch_uc, c, args.video_path, region_txt)
     log = ResumeLog(args.save_path)
     for i in range(args.num_samples):
         tag = f"sample_{i:04d}"
@@ -1106,6 +1261,8 @@ def main():
         print(f"{tag}: {T} frames {args.H}x{args.W} in {time.time() - t0:.2f}s")
         if regions_on(args):
             log.log["regions"] = region_log(args)
+        if prompt_log is not None:
+            log.log["prompts"] = prompt_log
         log.add(tag)
 
 

@@ -21,7 +21,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from scripts.sampling.sampling_tv2v import (add_common_args, build_model, check_args, check_region_options, check_tiling, check_windowing, conditioning_tensors, job_mode, run_jobs,  # noqa: E402
+from scripts.sampling.sampling_tv2v import (add_common_args, build_model, check_args, check_region_options, check_tiling, check_windowing, cond_text, conditioning_tensors, job_mode, run_jobs,  # noqa: E402
                                             sample_one, save_result, single_clip_masks, text_inputs)
 
 
@@ -62,7 +62,8 @@ def main():
     masks = single_clip_masks(args, dev)
     cond = conditioning_tensors(args, g, need_frames, need_ref=True)
     hint, ref = cond["control_hint"].to(dev), cond["cond_img"].to(dev)
-    txt, txt_uc = text_inputs(cond, dev)
+    long = cond_text(args, model, cond, dev)             # ids of (1, 77 n): --prompt_chunks / a conditioning file (ccedit_amd/prompt.py)
+    txt, txt_uc = text_inputs(cond, dev) if long is None else long[:2]
     batch = {"txt": txt, "control_hint": hint, "cond_img": ref}
     batch_uc = {"txt": txt_uc, "control_hint": hint.clone(), "cond_img": ref.clone()}
     c, uc = model.conditioner.get_unconditional_conditioning(batch, batch_uc=batch_uc)     # two VAE encodes (two RNG draws)
@@ -78,6 +79,8 @@ def main():
         torch.cuda.synchronize()
         save_result(args, tag, x)
         print(f"{tag}: {T} frames {args.H}x{args.W} in {time.time() - t0:.2f}s")
+        if long is not None:
+            log.log["prompts"] = long[2]
         log.add(tag)
 
 

@@ -91,7 +91,8 @@ class FrozenCLIPEmbedder(AbstractEmbModel):
         self.transformer.pack(device)
         return self
 
-    def tokenize(self, text) -> torch.Tensor:
+    def tokenizer(self):
+        """The CLIP tokenizer of `tokenizer_path`, loaded on first use (NotImplementedError where its files are not on this machine)."""
         if self._tokenizer is None:
             try:
                 from transformers import CLIPTokenizer
@@ -110,8 +111,11 @@ class FrozenCLIPEmbedder(AbstractEmbModel):
                 raise NotImplementedError(
                     f"FrozenCLIPEmbedder: the tokenizer files of {self.tokenizer_path!r} are not on this machine "
                     f"({type(e).__name__}); point tokenizer_path / CCEDIT_CLIP_TOKENIZER / --tokenizer_path at them, or pass token ids (B,{self.max_length}) int64 or a precomputed (B,{self.max_length},768) embedding as batch['txt']")
-        enc = self._tokenizer(text, truncation=True, max_length=self.max_length, return_length=True,
-                              return_overflowing_tokens=False, padding="max_length", return_tensors="pt")
+        return self._tokenizer
+
+    def tokenize(self, text) -> torch.Tensor:
+        enc = self.tokenizer()(text, truncation=True, max_length=self.max_length, return_length=True,
+                               return_overflowing_tokens=False, padding="max_length", return_tensors="pt")
         return enc["input_ids"]
 
     def forward(self, text):
@@ -124,6 +128,45 @@ class FrozenCLIPEmbedder(AbstractEmbModel):
 
     def encode(self, text):
         return self(text)
+
+    # ---- long and weighted prompts (ccedit_amd/prompt.py): contexts of 77 n rows.  `forward` above is untouched.
+    def special_ids(self):
+        """(BOS, EOS): the CLIP ViT-L/14 vocabulary's, or the loaded tokenizer's where tests swapped the vocabulary."""
+        if self._expected_vocab is not None:
+            return int(self._expected_vocab[1]), int(self._expected_vocab[2])
+        tok = self.tokenizer()
+        return int(tok.bos_token_id), int(tok.eos_token_id)
+
+    def empty_chunk_encoding(self) -> torch.Tensor:
+        """The encoding (77, 768) of the empty chunk (BOS, EOS x 76): where a token of weight 0 goes.  Computed once per packed set of
+        weights: the key is the identity of the packed embedding table, which the entry pins (ccedit_amd/caches.py)."""
+        from ccedit_amd.caches import PinnedCache, tensor_key
+        if getattr(self, "_empty_cache", None) is None:
+            self._empty_cache = PinnedCache(1)
+        table = self.transformer._tok
+        if table is None:
+            raise RuntimeError("call .pack() after loading weights")
+        bos, eos = self.special_ids()
+        key = (tensor_key(table), bos, eos)
+        e = self._empty_cache.get(key)
+        if e is None:
+            ids = torch.tensor([[bos] + [eos] * 76], dtype=torch.int64, device=table.device)
+            e = self.transformer(ids)[0].contiguous()
+            self._empty_cache.put(key, table, e)
+        return e
+
+    def encode_long(self, tokens: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Token ids (B, 77 n) int64, n <= 4 -> (B, 77 n, 768): ONE call of the text transformer on the (B n, 77) view — every chunk is
+        encoded on its own, `[BOS] ... [EOS]` as the model was trained — and, with `weights` (B, 77 n), the emphasis rule on the result
+        (ccedit_prompt_weight: e + w (z - e) against the empty chunk's encoding e; rows of weight 1 are bit copies)."""
+        from ccedit_amd import ops, prompt
+        n = prompt.check_tokens(tokens, weights, "encode_long")
+        b = tokens.shape[0]
+        z = self.transformer(tokens.reshape(b * n, prompt.CHUNK)).reshape(b, n * prompt.CHUNK, -1)
+        if weights is None:
+            return z
+        w = weights.to(device=z.device, dtype=torch.float32).contiguous()
+        return ops.prompt_weight(z.contiguous(), self.empty_chunk_encoding(), w)
 
 
 class DepthMidasEncoder(_Precomputed):
