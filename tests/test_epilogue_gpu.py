@@ -15,8 +15,9 @@ Every case asserts the kernel that ran, writes into a sentinel-filled wider buff
 and prints its largest |err| / bound and where it occurred.  tests/test_epilogue_ref.py shows on the CPU that the planted defects
 (another GELU, a missing clamp, a truncating or ties-away store, the activation after the residual, ...) miss these bounds.
 
-ff320 is held with ln = False only: its `ln = True` path and the block tail normalise inside the kernel, which is not exact on any
-grid; they stay with their tests in tests/test_ops_gpu.py and tests/test_fullsize_gpu.py.
+ff320 is held here with ln = False only.  Its `ln = True` path, both block-tail forms, lin320 / lin320s with ln_eps and the ln_stats /
+ln_sums consumers normalise inside the kernel; on rows whose LayerNorm is exact in fp32 they are held per element as well, in
+tests/test_fused_layernorm_gpu.py.
 """
 import ctypes
 import os

@@ -174,3 +174,184 @@ def test_ff320_emulation_and_defects(m):
     bad = P.outside(P.emu_ff320(o, "quick"), o.ref, o.bound)
     print(f"   quick-GELU for erf-GELU: {bad} of {o.ref.numel()} elements outside their bound")
     assert bad > 0
+
+
+# ------------------------------------------------------------------------------------------ LayerNorm inside the kernels
+FF_LN_M = P.FF_M + (P.ff_rounds_m(),)
+LIN_LN_M = tuple(m for m, _ in P.LIN_LN_SMALL) + (P.LIN_LN_RAGGED_M, P.LIN_LN_WRAP_M)
+
+
+@pytest.mark.parametrize("zeros", [False, True], ids=["plain", "zeros"])
+def test_ln_rows_generator(zeros):
+    r = P.ln_rows(200, 3, zeros)
+    for row in (0, 5, 100, 199):
+        vals, counts = torch.unique(r.z[row], return_counts=True)
+        want = {-4.0: 21, -2.0: 59, -1.0: 68, 0.0: 24, 1.0: 68, 2.0: 59, 4.0: 21} if zeros else {-4.0: 20, -2.0: 60, -1.0: 80, 1.0: 80, 2.0: 60, 4.0: 20}
+        assert dict(zip(vals.tolist(), counts.tolist())) == want
+    assert not torch.equal(r.perm[0], r.perm[1]) and torch.equal(r.x, r.s[:, None] * r.z + r.mean[:, None])
+    assert set(r.s.tolist()) == set(P.LN_SCALES) and len(set(r.mean.tolist())) >= 8
+    assert r.big == [5, 100, 198] and r.mean[r.big].abs().tolist() == [96.0] * 3 and r.s[r.big].tolist() == [0.5] * 3
+    assert len({(a, b) for a, b in zip(r.s.tolist(), r.mean.tolist())}) >= 25
+    mu = r.x.sum(dim=1) / 320.0
+    var = ((r.x - mu[:, None]) ** 2).sum(dim=1) / 320.0
+    assert torch.equal(mu, r.mean) and torch.equal(var, 4.0 * r.s * r.s) and torch.equal((r.x - mu[:, None]) / var.sqrt()[:, None], r.zn)
+
+
+@pytest.mark.parametrize("m", FF_LN_M)
+def test_ff320_layernorm_is_exact_on_every_row(m):
+    """eps = 1e-5, rsqrtf anywhere within +-4 ulp, the variance with or without the fma: the bf16 operand equals z / 2 bit for bit on every row
+    the GPU tests of ff320 and its block tail use (the |mean| = 96 rows included)."""
+    r = P.ln_rows(m, 0)
+    for ulps in (range(-P.LN_RSQRT_ULPS, P.LN_RSQRT_ULPS + 1) if m <= 200 else (-P.LN_RSQRT_ULPS, 0, P.LN_RSQRT_ULPS)):
+        for contract in (False, True):
+            assert torch.equal(P.emu_ln_ff320(r.x, ulps=ulps, contract=contract).double(), r.zn), (ulps, contract)
+
+
+@pytest.mark.parametrize("m", LIN_LN_M)
+def test_lin320_layernorm_is_exact_on_every_row(m):
+    r = P.ln_rows(m, 100, zeros=True)
+    for ulps in (range(-P.LN_RSQRT_ULPS, P.LN_RSQRT_ULPS + 1) if m <= 200 else (-P.LN_RSQRT_ULPS, 0, P.LN_RSQRT_ULPS)):
+        for contract in (False, True):
+            assert torch.equal(P.emu_ln_lin320(r.x, ulps=ulps, contract=contract).double(), r.zn), (ulps, contract)
+
+
+@pytest.mark.parametrize("m", [48, 200])
+def test_layernorm_planted_defects(m):
+    """Each planted defect changes at least one normalised element — on the whole case and on its |mean| = 96 rows alone (eps and the
+    neighbour's statistics excepted there: see below).
+
+    The one-pass variance E[x^2] - mean^2 is the exception, and the rows cannot show it: x and x^2 are multiples of s and s^2 with
+    sum x^2 = 320 (4 s^2 + mean^2) < 2^24 s^2, so the one-pass sums are as exact in fp32 as the two-pass ones, in either kernel's order,
+    at |mean| = 96 too (320 * 9217 * 4 = 1.2e7 quarter units), and fl(9217 (1 + 2^-26)) - 9216 is 1 exactly.  A row on which fp32 loses
+    the variance needs sum x^2 beyond 2^24 units, i.e. |mean| / std near 128 = the limit of 8 significant bits, and then the loss is
+    under 1e-3 relative: below what a bf16 operand at a power of two resolves.  It is asserted as what it is — invisible here."""
+    rf, rl = P.ln_rows(m, 0), P.ln_rows(m, 100, zeros=True)
+    for emu, r, defects in ((P.emu_ln_ff320, rf, P.LN_DEFECTS_FF), (P.emu_ln_lin320, rl, P.LN_DEFECTS_LIN)):
+        for name, kw in defects:
+            diff = emu(r.x, **kw).double() != r.zn
+            big = int(diff[r.big].sum())
+            print(f"{emu.__name__} M={m}, {name}: {int(diff.sum())} of {diff.numel()} elements differ ({big} on the |mean| = 96 rows)")
+            assert int(diff.sum()) > 0, name
+            assert big > 0 or "eps" in name, name       # eps = 1e-2 against variance 1 moves rstd by 5e-3: seen at s = 1/4, not on those rows
+        assert torch.equal(emu(r.x, one_pass=True).double(), r.zn), "the one-pass variance became visible: say so in the docstring"
+
+
+# ------------------------------------------------------------------------------------------ ff320, ln = True
+def test_ff320_ln_pack_is_exact():
+    """pack_ff320 folds gamma and beta: its stream equals the stream of the exact W1 diag(gamma), b1 + W1 beta packed without a LayerNorm,
+    and differs when gamma is indexed by the wrong axis position (reversed here)."""
+    from ccedit_amd.packing import pack_ff320
+    wt = P.ff320_ln_weights()
+    folded = pack_ff320(wt.w1.float(), wt.b1.float(), wt.w2.float(), wt.b2.float(), wt.gamma.float(), wt.beta.float())
+    exact = pack_ff320(wt.g1.float(), wt.b1p.float(), wt.w2.float(), wt.b2.float(), None, None)
+    assert torch.equal(folded.stream, exact.stream) and torch.equal(folded.b2p, exact.b2p)
+    swapped = pack_ff320(wt.w1.float(), wt.b1.float(), wt.w2.float(), wt.b2.float(), wt.gamma.flip(0).float(), wt.beta.float())
+    assert not torch.equal(swapped.stream, exact.stream)
+
+
+@pytest.mark.parametrize("m", P.FF_M)
+def test_ff320_ln_emulation_and_defects(m):
+    """LayerNorm emulation -> z / 2, then the chain of test_ff320_emulation_and_defects inside the UNCHANGED bound (nothing added for the
+    LayerNorm); a defective LayerNorm (the neighbour's statistics) and quick-GELU leave it."""
+    o = P.ff320_ln_case(m)
+    rh, at = P.worst(P.emu_geglu_pipe(o.value, o.gate), o.h, o.bh)
+    ro, at2 = P.worst(P.emu_ff_tokens(o.wt, o.x), o.ref, o.bound)
+    print(f"ff320 ln M={m}: gates per range {o.counts}; max |ref| {o.ref.abs().max().item():.1f}; hidden max |err| / bh {rh:.4f} at {at}; "
+          f"output max |err| / bound {ro:.4f} at {at2}")
+    assert rh <= 1.0 and ro <= 1.0
+    for name, kw in (("statistics of row r + 1", dict(ln=dict(stats_row=1))), ("no shuffle between the lane halves", dict(ln=dict(half_only=True))),
+                     ("quick-GELU for erf-GELU", dict(gelu="quick"))):
+        bad = P.outside(P.emu_ff_tokens(o.wt, o.x, **kw), o.ref, o.bound)
+        print(f"   {name}: {bad} of {o.ref.numel()} elements outside their bound")
+        assert bad > 0, name
+    # ln = False on the integers z with the pre-folded weights: the same hidden values, the residual z
+    ref, bnd = P.ff_with_residual(o, o.z)
+    acc = P.emu_ff_tokens(o.wt, o.z, operand=o.z / 2.0)
+    assert P.worst(acc, ref, bnd)[0] <= 1.0
+
+
+def test_ff320_case_past_one_round():
+    """M = 128 CUs + 200: the case builds (its grid and gate-coverage assertions run), every row is distinct, the last round is ragged."""
+    m = P.ff_rounds_m()
+    o = P.ff320_ln_case(m)
+    assert m % 128 == 72 and m // 128 + 1 > P.FF_CUS and torch.unique(o.x, dim=0).shape[0] == m
+    print(f"ff320 ln M={m}: gates per range {o.counts}; max |ref| {o.ref.abs().max().item():.1f}, largest bound {o.bound.max().item():.4f}")
+
+
+# ------------------------------------------------------------------------------------------ ff320 block tail
+@pytest.mark.parametrize("m", P.FF_M)
+@pytest.mark.parametrize("epi", [False, True], ids=["to_out+FF", "to_out+FF+proj_out"])
+def test_ff320_tail_emulation_and_defects(m, epi):
+    """The whole tail in fp32 stays inside; every planted defect leaves for at least one element.  The feed-forward result passed to
+    proj_out WITHOUT its bf16 rounding cannot be seen: delta_j, the bound on the rounded t_j, already contains that half ulp, so the
+    unrounded value is inside a fortiori — the count is printed, not asserted (the rounding is held by `to_out + FF`, whose output it is)."""
+    c = P.ff320_tail_case(m)
+    ref, bnd = (c.ref3, c.bound3) if epi else (c.ref2, c.bound2)
+    tok = P._chain(c.tw.bo.float()[None, :].expand(m, P.FF_DIM), c.a.float(), c.tw.oidx, c.tw.oval) + c.res.float()
+    assert torch.equal(P.store(tok).double(), c.ff.x) and torch.equal(tok.double(), c.ff.x)      # the fp32 chain lands on the ln_rows row; nothing rounds
+    ratio, at = P.worst(P.emu_ff320_tail(c, epi), ref, bnd)
+    print(f"block tail M={m} epi={epi}: max |res| {c.res.abs().max().item()}, emulation max |err| / bound {ratio:.4f} at {at}")
+    assert ratio <= 1.0
+    defects = P.TAIL_DEFECTS + ((("x_in of row r + 128", dict(xin_row=128)),) if epi else ())
+    for name, kw in defects:
+        bad = P.outside(P.emu_ff320_tail(c, epi, **kw), ref, bnd)
+        print(f"   {name}: {bad} of {ref.numel()} elements outside their bound")
+        assert bad > 0, name
+    if epi:
+        print(f"   no bf16 rounding before proj_out: {P.outside(P.emu_ff320_tail(c, True, round_t=False), ref, bnd)} outside (cannot be seen)")
+
+
+def test_ff320_tail_case_past_one_round():
+    c = P.ff320_tail_case(P.ff_rounds_m())
+    print(f"block tail M={c.m}: max |res| {c.res.abs().max().item()}, largest bound {c.bound3.max().item():.4f}")
+    assert c.ref3.shape == c.bound3.shape == (c.m, P.FF_DIM)
+
+
+# ------------------------------------------------------------------------------------------ lin320 with ln_eps
+@pytest.mark.parametrize("n", P.LIN_LN_N)
+def test_lin320_ln_fold_is_exact_and_rounding_case(n):
+    from ccedit_amd.packing import fold_layernorm
+    wt = P.lin320_ln_weights(n)
+    pw = fold_layernorm([wt.w.float()], [wt.b.float()], wt.gamma.float(), wt.beta.float())
+    assert torch.equal(pw.w[:n, :P.FF_DIM].double(), wt.wf) and torch.equal(pw.bias[:n].double(), wt.bf)
+    assert not torch.equal(fold_layernorm([wt.w.float()], [wt.b.float()], wt.gamma.flip(0).float(), wt.beta.float()).w[:n, :P.FF_DIM].double(), wt.wf)
+    for m, _ in P.LIN_LN_SMALL:
+        o = P.lin320_ln_case(m, n)
+        t, even, odd = P.assert_ties(o.total, f"lin320 ln {m}x{n}")
+        want = P.bf16_rne(o.total).view(torch.int16)
+        # the kernel's operand is z / 2 exactly (above) and every sum exact: its fp32 value IS total
+        got = (P.emu_ln_lin320(o.x).double() @ wt.wf.t()).float() + wt.bf.float()[None, :]
+        assert torch.equal(got.double(), o.total)
+        print(f"lin320 ln {m}x{n}: {t} exact ties ({even} even, {odd} odd) of {o.total.numel()}")
+        for how in ("trunc", "away"):
+            assert int((P.store(got, how).view(torch.int16) != want).sum()) > 0, how
+        bad = ((P.emu_ln_lin320(o.x, stats_row=1).double() @ wt.wf.t()).float() + wt.bf.float()[None, :])
+        assert int((P.store(bad).view(torch.int16) != want).sum()) > 0
+
+
+def test_lin320_ln_large_cases_hold_their_premises():
+    for m in (P.LIN_LN_RAGGED_M, P.LIN_LN_WRAP_M):
+        P.assert_ties(P.lin320_ln_case(m, 320).total, f"lin320 ln {m}x320")
+    assert P.LIN_LN_WRAP_M // 32 // 256 == P.LIN320S_SLOTS + 1 and P.LIN_LN_WRAP_M % 32 == 0 and P.LIN_LN_RAGGED_M % 32 == 13
+
+
+# ------------------------------------------------------------------------------------------ the ln_sums consumer
+@pytest.mark.parametrize("shape", [(m, n, 640) for (m, n) in P.LNF640] + [P.LNF_SHAPE], ids=lambda s: "x".join(map(str, s)))
+def test_ln_sums_emulation_and_defects(shape):
+    """Statistics rebuilt from the double sums: the emulation at the exact rstd and at both ends of the allowance stays inside; a dropped
+    colsum, rstd on the bias, a mean read from q and the sums of a neighbouring row fall outside."""
+    m, n, k = shape
+    o = P.lnf_case(m, n, k, False, P.LNF640.get((m, n), 0))
+    P.assert_ties(o.p, "LayerNorm fold")
+    ref, bnd = P.bound_lnf_sums(o)
+    s = P.ln_sums(o, k)
+    assert torch.equal(s[:, 0] / k, o.mean) and torch.equal((s[:, 1] / k - (s[:, 0] / k) ** 2) ** -0.5, o.rstd)
+    for side in (-1.0, 0.0, 1.0):
+        ratio, at = P.worst(P.emu_lnf_sums(o, k, side), ref, bnd)
+        print(f"ln_sums {shape} rstd at {side:+.0f} x allowance: emulation max |err| / bound {ratio:.4f} at {at}")
+        assert ratio <= 1.0
+    for name, kw in (("mean * colsum dropped", dict(drop_colsum=True)), ("rstd applied to the bias as well", dict(rstd_on_bias=True)),
+                     ("mean taken from q", dict(mean_from_q=True)), ("sums of row r + 1", dict(stats_row=1)), ("sums of row r - 1", dict(stats_row=-1))):
+        bad = P.outside(P.emu_lnf_sums(o, k, **kw), ref, bnd)
+        print(f"   {name}: {bad} of {ref.numel()} elements outside their bound")
+        assert bad > 0, name
