@@ -46,6 +46,14 @@ class PinnedCache:
     def clear(self) -> None:
         self._entries.clear()
 
+    def snapshot(self) -> dict:
+        """The entries as they are now (a shallow copy: the pins stay held by it), for `restore`."""
+        return dict(self._entries)
+
+    def restore(self, snap: dict) -> None:
+        """Put back the entries of `snapshot`, in their order; whatever was stored since is dropped."""
+        self._entries = dict(snap)
+
     def values(self):
         """The stored values, oldest first (the pins are nobody's business)."""
         return (value for _, value in self._entries.values())

@@ -194,6 +194,12 @@ int cc_tile_fuse(const float* const* yt, float* out, const int32_t* starts, cons
 int cc_region_weights(const uint8_t* masks, float* coef, int32_t K, int32_t T, int32_t H, int32_t W, int32_t F, hipStream_t s);
 int cc_region_fuse(const float* const* yr, float* out, const float* coef, int32_t K, int64_t BC, int32_t T, int64_t P, hipStream_t s);
 
+// Automatic-mask launchers (automask.hip); entry points and argument checks in core.cpp
+int cc_automask_accumulate(const float* y, float* acc, int32_t B, int32_t C, int64_t P, int32_t first, hipStream_t s);
+int cc_automask_binarize(const float* acc, const float* scale, float theta, uint8_t* bin, int32_t B, int64_t P, hipStream_t s);
+int cc_automask_vote(const uint8_t* bin, uint8_t* out, int32_t B, int32_t T, int32_t h, int32_t w, int32_t votes, hipStream_t s);
+int cc_automask_expand(const uint8_t* lat, uint8_t* px, int64_t N, int32_t h, int32_t w, hipStream_t s);
+
 // Weighted prompts (prompt.hip); entry point and argument checks in core.cpp
 int cc_prompt_weight(const float* z, const float* e, const float* w, float* out, int64_t R, int32_t C, hipStream_t s);
 

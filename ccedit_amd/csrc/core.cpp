@@ -284,6 +284,49 @@ extern "C" int ccedit_region_fuse(const void* yr, float* out, const float* coef,
     return cc_region_fuse((const float* const*)yr, out, coef, K, (int64_t)B * C, T, P, (hipStream_t)stream);
 }
 
+// ---- automatic edit masks (kernels and launchers: automask.hip).  Everything the host can see is checked here, before any HIP call;
+// no kernel has an index that depends on data: `scale` is read at [b] and only compared against.
+extern "C" int ccedit_automask_accumulate(const float* y, float* acc, int32_t B, int32_t C, int64_t P, int32_t first, void* stream) {
+    CC_CHECK_ARG(y && acc, "ccedit_automask_accumulate: null pointer");
+    CC_CHECK_ARG(B > 0 && P > 0, "ccedit_automask_accumulate: B=%d P=%lld (positive)", B, (long long)P);
+    CC_CHECK_ARG(C >= 1 && C <= 16, "ccedit_automask_accumulate: C=%d channels (1 ... 16)", C);
+    CC_CHECK_ARG(P < kPixelMax * 4 && 2 * (int64_t)B * C * P < kPixelMax * 4,
+                 "ccedit_automask_accumulate: more than 2^33 elements in one call (B=%d C=%d P=%lld)", B, C, (long long)P);
+    CC_CHECK_ARG(first == 0 || first == 1, "ccedit_automask_accumulate: first=%d (1: store, 0: add)", first);
+    CC_CHECK_ARG(((uintptr_t)y & 3) == 0 && ((uintptr_t)acc & 3) == 0, "ccedit_automask_accumulate: y and acc must be 4-byte aligned");
+    return cc_automask_accumulate(y, acc, B, C, P, first, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_automask_binarize(const float* acc, const float* scale, float theta, void* bin, int32_t B, int64_t P, void* stream) {
+    CC_CHECK_ARG(acc && scale && bin, "ccedit_automask_binarize: null pointer");
+    CC_CHECK_ARG(B > 0 && P > 0 && P < kPixelMax * 4 && (int64_t)B * P < kPixelMax * 4,
+                 "ccedit_automask_binarize: B=%d P=%lld (positive, at most 2^33 elements)", B, (long long)P);
+    CC_CHECK_ARG(theta >= 0.0f && theta <= 3.0e38f, "ccedit_automask_binarize: theta=%g (finite, not negative)", (double)theta);
+    CC_CHECK_ARG(((uintptr_t)acc & 3) == 0 && ((uintptr_t)scale & 3) == 0, "ccedit_automask_binarize: acc and scale must be 4-byte aligned");
+    return cc_automask_binarize(acc, scale, theta, (uint8_t*)bin, B, P, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_automask_vote(const void* bin, void* out, int32_t B, int32_t T, int32_t h, int32_t w, int32_t votes, void* stream) {
+    CC_CHECK_ARG(bin && out, "ccedit_automask_vote: null pointer");
+    CC_CHECK_ARG(B > 0 && T >= 1 && h >= 1 && w >= 1, "ccedit_automask_vote: B=%d clips of T=%d frames of %dx%d cells (positive)", B, T, h, w);
+    CC_CHECK_ARG((int64_t)B * T * h * w < kPixelMax, "ccedit_automask_vote: more than 2^31 cells in one call (B=%d T=%d %dx%d)", B, T, h, w);
+    CC_CHECK_ARG(votes >= 1 && votes <= 27, "ccedit_automask_vote: votes=%d of the 27 neighbours (1 ... 27)", votes);
+    {
+        const int64_t n = (int64_t)B * T * h * w;
+        const uintptr_t a = (uintptr_t)bin, b = (uintptr_t)out;
+        CC_CHECK_ARG(a + (uintptr_t)n <= b || b + (uintptr_t)n <= a, "ccedit_automask_vote: out must not alias bin (a cell reads its 26 neighbours)");
+    }
+    return cc_automask_vote((const uint8_t*)bin, (uint8_t*)out, B, T, h, w, votes, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_automask_expand(const void* lat, void* px, int64_t N, int32_t h, int32_t w, void* stream) {
+    CC_CHECK_ARG(lat && px, "ccedit_automask_expand: null pointer");
+    CC_CHECK_ARG(N > 0 && h >= 1 && w >= 1, "ccedit_automask_expand: N=%lld masks of %dx%d cells (positive)", (long long)N, h, w);
+    CC_CHECK_ARG(N < kPixelMax && N * 64 * h * w < kPixelMax * 4, "ccedit_automask_expand: more than 2^33 pixels in one call");
+    CC_CHECK_ARG(((uintptr_t)px & 7) == 0, "ccedit_automask_expand: the pixel mask must be 8-byte aligned (a row of a cell is one 8-byte store)");
+    return cc_automask_expand((const uint8_t*)lat, (uint8_t*)px, N, h, w, (hipStream_t)stream);
+}
+
 // ---- weighted prompts (kernel and launcher: prompt.hip).  Everything the host can see is checked here, before any HIP call; the kernel
 // reads e at (row mod 77) and everything else at the output's own index.
 extern "C" int ccedit_prompt_weight(const float* z, const float* e, const float* w, float* out, int32_t B, int32_t L, int32_t C, void* stream) {

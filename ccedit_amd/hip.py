@@ -161,6 +161,11 @@ _SIGS = {
     # region prompts (csrc/region.hip): added within ABI 12, nothing existing changed
     "ccedit_region_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ccedit_region_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
+    # automatic edit masks (csrc/automask.hip): added within ABI 12, nothing existing changed
+    "ccedit_automask_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "ccedit_automask_binarize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "ccedit_automask_vote": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_automask_expand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     # weighted prompts (csrc/prompt.hip): added within ABI 12, nothing existing changed
     "ccedit_prompt_weight": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     # propagation of edited keyframes (csrc/propagate.hip): added within ABI 12, nothing existing changed

@@ -1262,6 +1262,24 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
         for cache in (self._hint_val, self._hint_dup, self._hint_slices, self._twin_val, self._tkv_val, self._graphs):
             cache.clear()
 
+    _RESERVED = ("_windows", "_contexts", "_graph_slots", "_hint_slots", "_tkv_slots", "_graph_pool", "graph_counts")
+
+    def _caches(self):
+        return (self._hint_val, self._hint_dup, self._hint_slices, self._twin_val, self._tkv_val, self._graphs)
+
+    def cache_state(self):
+        """The per-clip caches, their reserved sizes and the graph counters as they are now, for `restore_cache_state`: a guest that
+        evaluates the network between two clips' samplers (ccedit_amd/automask.py) leaves no trace."""
+        return ([cache.snapshot() for cache in self._caches()],
+                {n: (dict(getattr(self, n)) if isinstance(getattr(self, n), dict) else getattr(self, n)) for n in self._RESERVED})
+
+    def restore_cache_state(self, state) -> None:
+        snaps, reserved = state
+        for cache, snap in zip(self._caches(), snaps):
+            cache.restore(snap)
+        for n, v in reserved.items():
+            setattr(self, n, v)
+
     def _guided_hint(self, hint5d: torch.Tensor, rows=None, half: bool = False):
         """hint_stem(1 - (hint+1)/2), cached per source tensor."""
         net = self.diffusion_model.controlnet

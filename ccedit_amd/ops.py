@@ -1057,6 +1057,79 @@ def region_fuse(ys, coef: torch.Tensor, out: Optional[torch.Tensor] = None) -> t
 
 
 # ------------------------------------------------------------------------------------------
+# Automatic edit masks (csrc/automask.hip): from the two halves of a denoiser output to a pixel mask (ccedit_amd/automask.py)
+# ------------------------------------------------------------------------------------------
+def _chk_cuda(t: torch.Tensor, dtype, name: str, what: str):
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous cuda {dtype} {what}, got {t.dtype} {t.device} {tuple(t.shape)} "
+                         f"contiguous={t.is_contiguous()}")
+
+
+def automask_accumulate(y: torch.Tensor, acc: Optional[torch.Tensor] = None, first: Optional[bool] = None) -> torch.Tensor:
+    """y fp32 (2B, C, T, h, w), the source-prompt half first -> acc fp32 (B, T, h, w): the sum over the channels, ascending, of
+    |y[B + b, c] - y[b, c]|, every operation rounded to fp32 (tests/_automask_numpy.py: accumulate).  Without `acc` the sum is stored
+    into a new tensor; with it, added to it in place (`first=True`: stored into it)."""
+    _chk_latent(y, "automask_accumulate")
+    b2, c, t, h, w = y.shape
+    if b2 % 2 or b2 < 2:
+        raise ValueError(f"automask_accumulate: y {tuple(y.shape)} is not a doubled batch (source-prompt half, target-prompt half)")
+    b = b2 // 2
+    first = (acc is None) if first is None else bool(first)
+    if acc is None:
+        if not first:
+            raise ValueError("automask_accumulate: first=False adds to `acc`, which was not given")
+        acc = torch.empty((b, t, h, w), dtype=torch.float32, device=y.device)
+    _chk_cuda(acc, torch.float32, "automask_accumulate", "acc")
+    if tuple(acc.shape) != (b, t, h, w) or acc.device != y.device:
+        raise ValueError(f"automask_accumulate: acc {tuple(acc.shape)} on {acc.device} for y {tuple(y.shape)}: expected {(b, t, h, w)} on {y.device}")
+    _launch_mem("automask_accumulate", 4.0 * (y.numel() + (1 if first else 2) * acc.numel()), lambda: hip.check(
+        hip.lib().ccedit_automask_accumulate(y.data_ptr(), acc.data_ptr(), b, c, t * h * w, int(first), _stream()),
+        "ccedit_automask_accumulate"), (b, c, t, h, w))
+    return acc
+
+
+def automask_binarize(acc: torch.Tensor, scale: torch.Tensor, theta: float) -> torch.Tensor:
+    """acc fp32 (B, T, h, w), scale fp32 (B,) ON THE DEVICE -> uint8 (B, T, h, w): 1 where acc > float32(theta) * scale[b], strictly.
+    Nothing is read back."""
+    _chk_cuda(acc, torch.float32, "automask_binarize", "acc (B, T, h, w)")
+    _chk_cuda(scale, torch.float32, "automask_binarize", "scale (B,)")
+    if acc.dim() != 4 or tuple(scale.shape) != (acc.shape[0],) or scale.device != acc.device:
+        raise ValueError(f"automask_binarize: acc {tuple(acc.shape)} with scale {tuple(scale.shape)}: expected (B, T, h, w) and (B,) on one device")
+    b = acc.shape[0]
+    out = torch.empty(acc.shape, dtype=torch.uint8, device=acc.device)
+    _launch_mem("automask_binarize", 5.0 * acc.numel(), lambda: hip.check(hip.lib().ccedit_automask_binarize(
+        acc.data_ptr(), scale.data_ptr(), float(theta), out.data_ptr(), b, acc[0].numel(), _stream()), "ccedit_automask_binarize"),
+        tuple(acc.shape))
+    return out
+
+
+def automask_vote(mask: torch.Tensor, votes: int) -> torch.Tensor:
+    """uint8 (B, T, h, w) -> uint8 (B, T, h, w): 1 where at least `votes` (1 ... 27) of the 27 cells around a cell — t, y, x each one step
+    either way, clamped into the clip — are set."""
+    _chk_cuda(mask, torch.uint8, "automask_vote", "mask (B, T, h, w)")
+    if mask.dim() != 4:
+        raise ValueError(f"automask_vote: mask {tuple(mask.shape)}: expected (B, T, h, w)")
+    b, t, h, w = mask.shape
+    out = torch.empty_like(mask)
+    _launch_mem("automask_vote", 2.0 * mask.numel(), lambda: hip.check(hip.lib().ccedit_automask_vote(
+        mask.data_ptr(), out.data_ptr(), b, t, h, w, int(votes), _stream()), "ccedit_automask_vote"), (b, t, h, w, int(votes)))
+    return out
+
+
+def automask_expand(mask_lat: torch.Tensor) -> torch.Tensor:
+    """Latent mask uint8 (B, T, h, w) (!= 0 = edit) -> pixel mask uint8 (B, T, 8h, 8w) in {0, 255}; mask_latent of it is the input's set
+    cells as 1."""
+    _chk_cuda(mask_lat, torch.uint8, "automask_expand", "latent mask (B, T, h, w)")
+    if mask_lat.dim() != 4:
+        raise ValueError(f"automask_expand: latent mask {tuple(mask_lat.shape)}: expected (B, T, h, w)")
+    b, t, h, w = mask_lat.shape
+    out = torch.empty((b, t, 8 * h, 8 * w), dtype=torch.uint8, device=mask_lat.device)
+    _launch_mem("automask_expand", 65.0 * mask_lat.numel(), lambda: hip.check(hip.lib().ccedit_automask_expand(
+        mask_lat.data_ptr(), out.data_ptr(), b * t, h, w, _stream()), "ccedit_automask_expand"), (b, t, h, w))
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # Weighted prompts (csrc/prompt.hip): the emphasis rule on the text encoder's output (ccedit_amd/prompt.py)
 # ------------------------------------------------------------------------------------------
 def prompt_weight(z: torch.Tensor, e: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -556,6 +556,30 @@ int ccedit_region_weights(const void* masks, float* coef, int32_t K, int32_t T, 
 int ccedit_region_fuse(const void* yr, float* out, const float* coef, int32_t K, int32_t B, int32_t C, int32_t T, int64_t P, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Automatic masks (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  The edit mask of `--inpainting_mode`
+ * from a source and a target prompt: the noised source latent is evaluated with (source prompt, target prompt) in the two halves of one
+ * CFG-doubled batch, and where the two predictions disagree is where the edit happens (DiffEdit's mask step; ccedit_amd/automask.py;
+ * `--mask_auto`, `--source_prompt`).  Kernels: csrc/automask.hip; definition: tests/_automask_numpy.py, reproduced bit for bit.  All
+ * pointers are device pointers.  An invalid argument returns CCEDIT_EINVAL and launches nothing.
+ *
+ * ccedit_automask_accumulate: y fp32 [2B][C][P] (the source-prompt half first), acc fp32 [B][P], P = T h w, 1 <= C <= 16.
+ *   s = ((|y[B+b][0][p] - y[b][0][p]| + |...[1]...|) + |...[2]...|) + ..., channels ascending, every subtract and add rounded to fp32;
+ *   acc[b][p] = s with first = 1, acc[b][p] + s with first = 0.  A NaN in either half gives NaN.  16-byte accesses where P % 4 == 0 and
+ *   y and acc are 16-byte aligned, one element per access otherwise.
+ * ccedit_automask_binarize: bin[b][p] = acc[b][p] > theta * scale[b] ? 1 : 0, uint8 [B][P]; one fp32 multiply, strictly greater (a
+ *   cell equal to the threshold, and a NaN, stay clear).  scale fp32 [B] is read from DEVICE memory (the result of ccedit_kth_values
+ *   stays where it is: no host sync); theta finite and not negative.
+ * ccedit_automask_vote: out[b][t][y][x] = (sum of bin[b][t+dt][y+dy][x+dx] != 0 over dt, dy, dx in {-1, 0, 1}, every coordinate clamped
+ *   into the volume) >= votes ? 1 : 0; bin and out uint8 [B][T][h][w]; 1 <= votes <= 27.  out must not overlap bin.
+ * ccedit_automask_expand: lat uint8 [N][h][w] (!= 0 is set) -> px uint8 [N][8h][8w] in {0, 255}, px 8-byte aligned; each lane writes the
+ *   8 bytes of a cell's pixel row as one store.  ccedit_mask_latent of the result is lat's set cells as 1, byte for byte.
+ */
+int ccedit_automask_accumulate(const float* y, float* acc, int32_t B, int32_t C, int64_t P, int32_t first, void* stream);
+int ccedit_automask_binarize(const float* acc, const float* scale, float theta, void* bin, int32_t B, int64_t P, void* stream);
+int ccedit_automask_vote(const void* bin, void* out, int32_t B, int32_t T, int32_t h, int32_t w, int32_t votes, void* stream);
+int ccedit_automask_expand(const void* lat, void* px, int64_t N, int32_t h, int32_t w, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Prompts (added without an ABI bump: one new function, CCEDIT_ABI_VERSION stays 12).  Long and weighted prompts: a prompt is cut into
  * n <= 4 chunks of 77 CLIP tokens, every chunk goes through the text encoder on its own and the rows are laid side by side — a context
  * of L = 77 n rows (ccedit_amd/prompt.py; `--prompt_chunks`, `--prompt_syntax weighted`).  Kernel: csrc/prompt.hip.  All pointers are

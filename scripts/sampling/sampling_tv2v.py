@@ -26,6 +26,12 @@ outside the mask after decoding; the mask as applied is saved under <save_path>/
 `--mask_track` (with ONE mask image, painted on source frame `--mask_frame`) gives every source frame its own mask, tracked along the
 source's motion on the device (ccedit_amd/masktrack.py, csrc/masktrack.hip); `--mask_dilate R` and `--mask_invert` apply afterwards,
 to untracked masks too.
+`--mask_auto --source_prompt TEXT` (job mode, with --inpainting_mode) needs no painted mask: the encoded clip is noised and evaluated with
+(source prompt, --prompt) in the two halves of one CFG-doubled batch, --mask_auto_samples times, and the mask is where the two predictions
+disagree — summed differences scaled by a quantile, thresholded, cleaned by a 3 x 3 x 3 vote over space and time (ccedit_amd/automask.py,
+csrc/automask.hip); it then goes where a painted mask goes (--mask_dilate, --mask_invert, --mask_composite, mask/).  --mask_auto_save DIR
+writes it as DIR/<video name>/%05d.png per source frame, which --mask_root DIR reads back; log_info.json gains `mask_auto`.  The quality
+of such masks on real footage has not been measured.
 `--window_frames T` (with `--window_overlap O`, default T // 2) lifts the limit of one window of keyframes: with `--num_keyframes N` > T the
 clip is covered by overlapping windows of T frames, each evaluated by the unchanged network at every sampler evaluation and fused into
 one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everything else — inpainting, SDEdit, the prior mix,
@@ -161,6 +167,26 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="grow every mask (tracked or not) by this many pixels, 0 ... 32: a (2R + 1) x (2R + 1) square maximum, after tracking")
     p.add_argument("--mask_invert", action="store_true",
                    help="swap edit and keep (255 - mask), after tracking and --mask_dilate: with --mask_track, edit everything but the subject")
+    p.add_argument("--mask_auto", action="store_true",
+                   help="(not in the reference script) no painted mask: the edit mask is computed from --source_prompt (what the video shows) and "
+                        "--prompt (what it should show) — the noised source latent is evaluated under both prompts and the mask is where the "
+                        "two predictions disagree, cleaned by a vote over space and time (ccedit_amd/automask.py, csrc/automask.hip).  Needs "
+                        "--inpainting_mode, --source_prompt and a video with a prompt; costs --mask_auto_samples network evaluations per clip")
+    p.add_argument("--source_prompt", type=str, default="", help="with --mask_auto: the prompt that describes the SOURCE video (\"a brown horse\")")
+    p.add_argument("--mask_auto_samples", type=int, default=4, help="noise samples of the difference map, 1 ... 16: one network evaluation each")
+    p.add_argument("--mask_auto_strength", type=float, default=0.5,
+                   help="noise level of the samples, in (0, 1]: the first sigma of the schedule --sdedit_denoise_strength of this value starts from")
+    p.add_argument("--mask_auto_quantile", type=float, default=0.99,
+                   help="the difference map of a clip is scaled by this quantile of its cells, in [0, 1] (below 1: a few outliers do not set the scale)")
+    p.add_argument("--mask_auto_threshold", type=float, default=0.5, help="a cell is set where its difference exceeds this fraction of the scale")
+    p.add_argument("--mask_auto_vote", type=int, default=14,
+                   help="a cell stays set where at least this many of the 27 cells around it — 3 x 3 in space, one frame either way in time — are "
+                        "set, 1 ... 27 (default 14, a majority: specks and one-frame flicker go); 0 = no vote")
+    p.add_argument("--mask_auto_seed", type=int, default=None, help="seed of the automatic mask's own noise generator (default: --seed)")
+    p.add_argument("--mask_auto_save", type=str, default="",
+                   help="directory: the final masks are written to <dir>/<video name>/%%05d.png, one per SOURCE frame (every frame gets its nearest "
+                        "keyframe's mask), a sequence --mask_root <dir> accepts as it is — compute once, retouch, reuse (then without "
+                        "--mask_dilate / --mask_invert, which the saved masks already hold)")
     p.add_argument("--window_frames", type=int, default=0,
                    help="(not in the reference script) keyframes per network evaluation; with --num_keyframes above it the clip is covered "
                         "by overlapping windows of this many frames whose denoised latents are fused at every sampler evaluation "
@@ -253,6 +279,7 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error(f"--save_type mjpeg codes 16 x 16 MCUs: --H and --W must be multiples of 16 (got {args.H}x{args.W})")
     check_mask_options(args)                 # (--mask_track and its kin: ValueError, here and again where the masks are made)
     check_region_options(args)               # (--region_prompt and its kin: ValueError; nothing is imported or checked without the flags)
+    check_mask_auto(args)                    # (--mask_auto and its kin: ValueError; nothing is imported or checked without the flag)
 
 
 def windowing(args) -> bool:
@@ -512,19 +539,21 @@ def warn_truncated(args, model, texts) -> None:
                   f"{min(-(-count // 75), 4)} keeps it", file=sys.stderr)
 
 
-def long_text(args, model, dev, full, neg, region=()):
+def long_text(args, model, dev, full, neg, region=(), source=None):
     """The new text path for one chunk of clips.  `full`, `neg`: the composed prompts and the negative prompts, one per clip; `region`:
     the composed region prompts of the clip.  Every prompt is cut into chunks, all get ONE length 77 n, and the embedder encodes them
     chunk by chunk (weighted: with the emphasis rule).  Returns (txt, txt_uc, [txt of every region], per-clip log entries): txt are
-    finished (bs, 77 n, C) embeddings, which the conditioner hands through.  Every refusal is raised before the first launch."""
+    finished (bs, 77 n, C) embeddings, which the conditioner hands through.  Every refusal is raised before the first launch.
+    `source` (--mask_auto): the composed source prompt of the chunk; it takes part in the one length, and its txt, repeated per clip, is
+    returned as a FIFTH element (only when `source` is given)."""
     import zlib
     from ccedit_amd import prompt
     prompt.check_options(args.prompt_chunks, args.prompt_syntax)
     weighted = args.prompt_syntax == "weighted"
     names = ([f"--prompt ({i + 1} of {len(full)})" if len(full) > 1 else "--prompt" for i in range(len(full))]
              + [f"--negative_prompt ({i + 1} of {len(neg)})" if len(neg) > 1 else "--negative_prompt" for i in range(len(neg))]
-             + [f"--region_prompt {r + 1}" for r in range(len(region))])
-    texts = list(full) + list(neg) + list(region)
+             + [f"--region_prompt {r + 1}" for r in range(len(region))] + (["--source_prompt"] if source is not None else []))
+    texts = list(full) + list(neg) + list(region) + ([source] if source is not None else [])
     if args.tokenizer_path:
         emb = _text_embedder(model)
         enc = prompt.encode_prompts(emb.tokenizer(), dict(zip(names, texts)), args.prompt_chunks, args.prompt_syntax)
@@ -560,9 +589,11 @@ def long_text(args, model, dev, full, neg, region=()):
     nf = len(full)
     txt = encode(names[:nf]) if nf else None
     txt_uc = encode(names[nf:nf + len(neg)]) if neg else None
-    region_txt = [encode([k]) for k in names[nf + len(neg):]]
+    region_txt = [encode([k]) for k in names[nf + len(neg):nf + len(neg) + len(region)]]
     log = [dict(prompt_tokens=counts[names[i]][0], prompt_chunks=counts[names[i]][1], negative_prompt_tokens=counts[names[nf + i]][0],
                 negative_prompt_chunks=counts[names[nf + i]][1], context_rows=77 * n) for i in range(nf)]
+    if source is not None:
+        return txt, txt_uc, region_txt, log, encode(["--source_prompt"] * max(nf, 1))
     return txt, txt_uc, region_txt, log
 
 
@@ -721,6 +752,120 @@ def all_frame_masks(args, video_path: str, n_all: int, dev):
 
 
 # ------------------------------------------------------------------------------------------
+# Automatic edit masks: --mask_auto from --source_prompt and --prompt (ccedit_amd/automask.py)
+# ------------------------------------------------------------------------------------------
+def mask_auto_on(args) -> bool:
+    """The automatic mask is active when --mask_auto was given; otherwise nothing of it is imported or called."""
+    return bool(getattr(args, "mask_auto", False))
+
+
+def check_mask_auto(args, with_ref: bool = False) -> None:
+    """Before any video is opened, from the flags alone: what --mask_auto needs and what it cannot be combined with (ValueError naming
+    the flags, with what to do).  Without the flag everything passes."""
+    if not mask_auto_on(args):
+        return
+    if with_ref:
+        raise ValueError("--mask_auto is not available with a reference image (sampling_tv2v_ref.py): the reference image conditions the "
+                         "whole frame — compute the mask with sampling_tv2v.py --mask_auto --mask_auto_save DIR and give it as --mask_root DIR")
+    if not args.inpainting_mode:
+        raise ValueError("--mask_auto computes the edit mask of --inpainting_mode: give both")
+    if not getattr(args, "source_prompt", ""):
+        raise ValueError("--mask_auto compares the network's prediction under --source_prompt (what the video shows) with the one under "
+                         "--prompt (what it should show): give --source_prompt")
+    if not job_mode(args):
+        raise ValueError("--mask_auto works on a video and its prompt: give --prompt with --video_path (or --prompt_listpath / "
+                         "--videos_directory / --json_path)")
+    for flag in ("mask_path", "mask_root", "mask_track"):
+        if getattr(args, flag, None):
+            raise ValueError(f"--mask_auto with --{flag}: two sources for one mask — drop one of them")
+    if regions_on(args):
+        raise ValueError("--mask_auto with --region_prompt / --region_mask: the automatic mask compares ONE source prompt with ONE target "
+                         "prompt — drop one of them")
+    if getattr(args, "propagate", False) and getattr(args, "mask_composite", False):
+        raise ValueError("--mask_auto with --propagate --mask_composite: compositing the frames between the keyframes needs every source "
+                         "frame's mask, the automatic mask has the keyframes' — drop --mask_composite, or save the masks with "
+                         "--mask_auto_save DIR and run again with --mask_root DIR")
+    if args.H % 8 or args.W % 8:
+        raise ValueError(f"--mask_auto with --H {args.H} --W {args.W}: the automatic mask is made per latent cell of 8 x 8 pixels — frame sides must be multiples of 8")
+    from ccedit_amd import automask
+    automask.check_options(args.mask_auto_samples, args.mask_auto_strength, args.mask_auto_quantile, args.mask_auto_threshold,
+                           args.mask_auto_vote)
+
+
+def mask_auto_seed(args) -> int:
+    return int(args.seed if getattr(args, "mask_auto_seed", None) is None else args.mask_auto_seed)
+
+
+def mask_auto_sigma(args) -> float:
+    """The noise level of the automatic mask: the first sigma of the schedule --sdedit_denoise_strength = --mask_auto_strength starts from."""
+    from scripts.sampling.util import init_sampling
+    sampler = init_sampling(sample_steps=args.sample_steps, sampler_name=args.sampler_name, discretization_name=args.discretization_name,
+                            guider_config_target=GUIDER, cfg_scale=args.cfg_scale, img2img_strength=args.mask_auto_strength)
+    return float(sampler.discretization(sampler.num_steps)[0])
+
+
+def _video_name(video_path: str) -> str:
+    """<video name> of --mask_root/<video name>/ (find_mask)."""
+    stem = video_path[:-4] if video_path.endswith((".mp4", ".gif", ".avi")) else video_path.rstrip("/")
+    return os.path.basename(stem)
+
+
+def save_auto_masks(args, video_path: str, masks) -> str:
+    """--mask_auto_save: `masks` uint8 (T, H, W), the final masks of one clip's keyframes -> <dir>/<video name>/%05d.png, one per source
+    frame, each frame its nearest keyframe's mask (a tie: the earlier keyframe's).  What --mask_root <dir> reads back.  -> the directory."""
+    from PIL import Image
+    from ccedit_amd.automask import nearest_keyframe
+    from scripts.sampling.util import count_video_frames, keyframe_indices
+    n_all = count_video_frames(resolve_video(video_path))
+    table = nearest_keyframe(keyframe_indices(n_all, args.original_fps, args.target_fps, args.num_keyframes), n_all)
+    out = os.path.join(args.mask_auto_save, _video_name(video_path))
+    os.makedirs(out, exist_ok=True)
+    host = masks.cpu().numpy()
+    for f, k in enumerate(table):
+        Image.fromarray(host[k]).save(os.path.join(out, f"{f:05d}.png"))
+    return out
+
+
+def auto_masks(args, model, dev, batch, batch_uc, c, cvideos, keyframes, source_txt):
+    """The pixel masks of a chunk from --source_prompt and --prompt, in place of clip_masks: uint8 (bs, T, H, W) on `dev`, 0 = keep /
+    255 = edit, --mask_dilate / --mask_invert applied last; and the chunk's part of log_info['mask_auto'].  `source_txt`: batch['txt'] of
+    the source prompt, made by the text route of the other prompts.  The conditioning differs from `c` in the text alone (the control
+    hint is the same object in both halves); the closure is the one the sampler will get."""
+    from ccedit_amd import automask
+    bs = keyframes.shape[0]
+    for v in cvideos:
+        found = find_mask(args, v)
+        if found is not None:
+            print(f"[automask] {found} is ignored: --mask_auto computes the mask of {v}", file=sys.stderr)
+    cs, _ = model.conditioner.get_unconditional_conditioning(dict(batch, txt=source_txt), batch_uc=batch_uc)
+    c_src = dict(c, crossattn=cs["crossattn"][:bs].to(dev))
+    closure, engine = make_closure(args, model, c)
+    gen = automask.generator(mask_auto_seed(args))
+    zc = model.first_stage_model.embed_dim
+    z = engine.encode_first_stage(keyframes, noise=torch.randn(bs * keyframes.shape[2], zc, args.H // 8, args.W // 8, generator=gen))
+    sigma = mask_auto_sigma(args)
+    if sigma == 0.0:
+        print(f"[automask] --mask_auto_strength {args.mask_auto_strength} of {args.sample_steps} steps starts at sigma 0: the latent is not "
+              "noised at all and the difference map comes from one deterministic evaluation — raise --mask_auto_strength or --sample_steps",
+              file=sys.stderr)
+    acc = automask.AutoMask(closure, wrapper=model.model)(z, sigma, c_src, c, args.mask_auto_samples, gen)
+    lat = automask.mask_from(acc, args.mask_auto_quantile, args.mask_auto_threshold, args.mask_auto_vote, names=cvideos, latent=True)
+    fractions = lat.float().flatten(1).mean(dim=1).cpu().tolist()
+    from ccedit_amd import ops
+    px = ops.automask_expand(lat)
+    final = torch.stack([finish_masks(args, px[b]) for b in range(bs)], dim=0).contiguous()
+    for b, v in enumerate(cvideos):
+        if fractions[b] == 0.0:
+            print(f"[automask] the mask of {v} is empty: the two prompts' predictions differ nowhere by more than the threshold", file=sys.stderr)
+        if getattr(args, "mask_auto_save", ""):
+            save_auto_masks(args, v, final[b])
+    log = dict(source_prompt=args.source_prompt, samples=int(args.mask_auto_samples), strength=float(args.mask_auto_strength), sigma=sigma,
+               quantile=float(args.mask_auto_quantile), threshold=float(args.mask_auto_threshold), vote=int(args.mask_auto_vote),
+               seed=mask_auto_seed(args))
+    return final, log, [float(f) for f in fractions]
+
+
+# ------------------------------------------------------------------------------------------
 # Region prompts: --region_prompt / --region_mask pairs (ccedit_amd/regions.py)
 # ------------------------------------------------------------------------------------------
 def regions_on(args) -> bool:
@@ -820,11 +965,10 @@ def region_log(args) -> list:
             for q, m in zip(args.region_prompt, args.region_mask)]
 
 
-def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, regions=None):
-    """sampling_tv2v.py:361-468 for one chunk: the sampled latent.  `mask`: the uint8 LATENT mask (bs, T, H / 8, W / 8) of
-    --inpainting_mode (ops.mask_latent of the pixel masks; 1 = edit).  `regions`: region_setup's dict (region prompts), or nothing."""
-    from scripts.sampling.util import init_sampling, prior_latent, sdedit_start
-
+def make_closure(args, model, c, ref=None, regions=None):
+    """The closure `denoiser(input, sigma, cond)` every sampler evaluation of a chunk goes through — plain, windowed (--window_frames),
+    tiled (--tile_h / --tile_w), region prompts outermost — and the engine whose first stage works in groups that fit it.  Used by
+    sample_latent and by the automatic mask (auto_masks): both evaluate the network the same way.  -> (closure, engine)."""
     def denoiser(inp, sigma, cc):
         return model.denoiser(model.model, inp, sigma, cc)
 
@@ -853,6 +997,14 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
         if ref is not None:
             raise NotImplementedError("--region_prompt / --region_mask are not available with a reference image: it conditions the whole frame")
         denoiser = RegionDenoiser(denoiser, regions["contexts"], regions["coef"], wrapper=model.model)      # (the grouped first stage hands .model on)
+    return denoiser, model
+
+
+def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, regions=None):
+    """sampling_tv2v.py:361-468 for one chunk: the sampled latent.  `mask`: the uint8 LATENT mask (bs, T, H / 8, W / 8) of
+    --inpainting_mode (ops.mask_latent of the pixel masks; 1 = edit).  `regions`: region_setup's dict (region prompts), or nothing."""
+    from scripts.sampling.util import init_sampling, prior_latent, sdedit_start
+    denoiser, model = make_closure(args, model, c, ref=ref, regions=regions)
 
     inpaint = getattr(args, "inpainting_mode", False)
     if inpaint and mask is None:
@@ -1060,6 +1212,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
     check_windowing(args, with_ref)
     check_tiling(args, with_ref)
     check_region_options(args, with_ref)
+    check_mask_auto(args, with_ref)
     from ccedit_amd.parallel import shard_clips
     from scripts.sampling.util import chunk, load_img, load_video_keyframes, model_load_ckpt, perform_save_locally_video
     prompts, video_paths, video_save_paths, ref_paths = expand_jobs(args, with_ref)
@@ -1126,14 +1279,20 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 continue
             keyframes = torch.cat(kfs, dim=0).to(dev)                    # (bs, 3, T, H, W) in [-1, 1]
             depth = torch.cat([depth_frames(args, v, k) for v, k in zip(cvideos, kfs)], dim=0).to(dev)
-            region_txt = prompt_log = None
+            region_txt = prompt_log = source_txt = None
             if prompts_on(args):     # every prompt of the chunk in chunks of 77 tokens, one length for all (refusals before any launch)
-                txt, txt_uc, region_txt, prompt_log = long_text(args, model, dev, [compose_prompt(args, q) for q in cprompts],
-                                                                [args.negative_prompt for _ in cprompts],
-                                                                [compose_prompt(args, q) for q in (args.region_prompt or [])])
+                source_kw = dict(source=compose_prompt(args, args.source_prompt)) if mask_auto_on(args) else {}
+                txt, txt_uc, region_txt, prompt_log, *source_txt = long_text(args, model, dev, [compose_prompt(args, q) for q in cprompts],
+                                                                             [args.negative_prompt for _ in cprompts],
+                                                                             [compose_prompt(args, q) for q in (args.region_prompt or [])],
+                                                                             **source_kw)
+                source_txt = source_txt[0] if source_txt else None
             else:
                 txt, txt_uc = job_text(args, cprompts, dev, args.context_dim)
                 warn_truncated(args, model, txt + txt_uc[:1] if args.tokenizer_path else [])
+                if mask_auto_on(args):          # the source prompt through the same route: add_prompt, the tokenizer or --synthetic's seeded ids
+                    source_txt = job_text(args, [args.source_prompt] * len(cprompts), dev, args.context_dim)[0]
+                    warn_truncated(args, model, source_txt[:1] if args.tokenizer_path else [])
             if args.gpu_io:          # raw depth -> finished hint by the kernels; the embedder passes a finished hint through
                 depth = _hint_embedder(model).normalize_gpu(depth)
             batch = {"txt": txt, "control_hint": depth}
@@ -1150,10 +1309,13 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 if isinstance(c[k], torch.Tensor):
                     c[k], uc[k] = c[k][:bs].to(dev), uc[k][:bs].to(dev)
             randn = torch.randn(bs, 4, T, H // 8, W // 8, generator=g).to(dev)
-            mask_px = mask_lat = None
+            mask_px = mask_lat = auto_log = None
             if args.inpainting_mode:                                      # (no mask: NotImplementedError, as the flag alone always was)
                 from ccedit_amd import ops
-                mask_px = clip_masks(args, cvideos, dev)
+                if mask_auto_on(args):                                    # the mask from the two prompts, in place of clip_masks
+                    mask_px, auto_log, auto_fractions = auto_masks(args, model, dev, batch, batch_uc, c, cvideos, keyframes, source_txt)
+                else:
+                    mask_px = clip_masks(args, cvideos, dev)
                 mask_lat = ops.mask_latent(mask_px)
             region_kw = dict(regions=region_setup(args, model, dev, batch, batch_uc, c, cvideos[0], region_txt)) if regions_on(args) else {}
             t0 = time.time()
@@ -1186,6 +1348,8 @@ def run_jobs(args, with_ref: bool = False) -> None:
             if prompt_log is not None:
                 log_info.setdefault("prompts", [])
                 log_info["prompts"] += prompt_log
+            if auto_log is not None:                                      # the settings once, the fraction of latent cells set per clip
+                log_info["mask_auto"] = dict(auto_log, fractions=log_info.get("mask_auto", {}).get("fractions", []) + auto_fractions)
             os.makedirs(os.path.dirname(log_path), exist_ok=True)
             for out in {log_path, os.path.join(save_path, log_name)}:    # (the reference writes it under save_path; the loop reads it per base model)
                 os.makedirs(os.path.dirname(out), exist_ok=True)
