@@ -26,6 +26,8 @@ bool cc_attn_short_applicable(const CcAttnDesc& a);      // attnshort.hip
 int cc_attn_short_launch(const CcAttnDesc& a, hipStream_t s);
 bool cc_attn_text_applicable(const CcAttnDesc& a);       // attntext.hip
 int cc_attn_text_launch(const CcAttnDesc& a, hipStream_t s);
+bool cc_attn_text_frame_applicable(const CcAttnDesc& a); // attntext.hip: K / V per frame (CCEDIT_ATTN_KV_PER_FRAME)
+int cc_attn_text_frame_launch(const CcAttnDesc& a, hipStream_t s);
 bool cc_attn_text_long_applicable(const CcAttnDesc& a);  // attntextlong.hip
 int cc_attn_text_long_launch(const CcAttnDesc& a, hipStream_t s);
 bool cc_attn_spatial_applicable(const CcAttnDesc& a);    // attnspatial.hip
@@ -393,6 +395,7 @@ extern "C" int ccedit_attention(const CcAttnDesc* desc, void* stream) {
     CC_UNSUPPORTED(a.ldq % 8 || a.ldk % 8 || a.ldv % 8 || a.ldo % 4, "ccedit_attention: row strides must be multiples of 8");
     CC_CHECK_ARG(a.seg1_len >= 0 && a.seg1_len <= a.Lk && (a.seg1_len == 0 || a.seg1_div > 0), "ccedit_attention: bad leading segment");
     CC_CHECK_ARG(!a.causal || (a.Lq == a.Lk && a.seg1_len == 0), "ccedit_attention: causal needs Lq == Lk and no leading segment");
+    CC_CHECK_ARG(!(a.flags & CCEDIT_ATTN_KV_PER_FRAME) || a.kv_div == 1, "ccedit_attention: CCEDIT_ATTN_KV_PER_FRAME needs kv_div == 1, got %d", a.kv_div);
     CC_UNSUPPORTED(((int64_t)a.batches * a.heads + 8) * ((a.Lq + 31) / 32) > 2147483647LL, "ccedit_attention: grid too large");
     hipStream_t s = (hipStream_t)stream;
     // temporal self-attention (T <= 32 keyframes per pixel): HBM-bound, own kernel organised around whole-row loads
@@ -400,6 +403,8 @@ extern "C" int ccedit_attention(const CcAttnDesc* desc, void* stream) {
     if (cc_policy().attn_short && plain_q && cc_attn_short_applicable(a)) return cc_attn_short_launch(a, s);
     // text cross-attention (<= 96 keys shared by the frames of a clip): bound by streaming the query rows, own kernel (attntext.hip)
     if (cc_policy().attn_text && plain_q && cc_attn_text_applicable(a)) return cc_attn_text_launch(a, s);
+    // ... with K / V of its own for every frame (a prompt schedule): the same kernel split by (frame, group, row split)
+    if (cc_policy().attn_text && plain_q && cc_attn_text_frame_applicable(a)) return cc_attn_text_frame_launch(a, s);
     // ... and onto the 154 / 231 / 308 keys of a long prompt, under the same switch (attntextlong.hip)
     if (cc_policy().attn_text && plain_q && cc_attn_text_long_applicable(a)) return cc_attn_text_long_launch(a, s);
     // long self-attention at d = 40 (the 64x96 level): the softmax arithmetic is the bound, own kernel (attnspatial.hip)

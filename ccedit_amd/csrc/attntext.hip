@@ -40,7 +40,10 @@ __device__ __forceinline__ void at_swap(float& x, float& y) {      // see g8_swa
     y = __uint_as_float(r[1]);
 }
 
-template <int D>
+// PF (CCEDIT_ATTN_KV_PER_FRAME: K / V of its own for every frame, kv_div = 1): the work is split by (frame, group, row split) instead —
+// a workgroup stages the K / V^T of ITS frame and group once and its eight waves walk only that frame's 32-row tiles inside its split;
+// `nkvb` is then S, the number of row splits of a frame, and the grid is frames x ngroups x S workgroups.
+template <int D, bool PF>
 __global__ __launch_bounds__(kNT, 1) void attn_text_kernel(const CcAttnDesc a, int ngroups, int nkvb) {
     constexpr int HPG = kG / D;                     // heads per group
     constexpr int KS = (D + 15) / 16;               // k-steps of Q K^T
@@ -56,11 +59,14 @@ __global__ __launch_bounds__(kNT, 1) void attn_text_kernel(const CcAttnDesc a, i
     // workgroup b runs on XCD b % 8; the 32 workgroups of an XCD = (32 / ngroups) row lanes x ngroups channel groups, so the groups
     // of a query row run beside each other on one L2
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int group = j % ngroups, qlane = j / ngroups;
+    // PF: workgroup b = (frame, group, split), splits fastest — the S workgroups that stage one frame's K / V follow each other
+    const int split = PF ? (int)(blockIdx.x % (unsigned)nkvb) : 0, fg = PF ? (int)(blockIdx.x / (unsigned)nkvb) : 0;
+    const int group = PF ? fg % ngroups : j % ngroups, qlane = j / ngroups;
     const int nlanes = (int)(gridDim.x >> 3) / ngroups;
-    if (qlane >= nlanes) return;
-    const int stride = nlanes * 8 * 8;              // 32-row tiles between two tiles of one wave
-    const int first = (qlane * 8 + wave) * 8 + xcd;
+    if (!PF && qlane >= nlanes) return;
+    const int stride = PF ? 8 : nlanes * 8 * 8;     // 32-row tiles between two tiles of one wave (PF: the eight waves take the split's tiles in turn)
+    const int first = PF ? wave : (qlane * 8 + wave) * 8 + xcd;      // (PF: relative to the split's first tile)
+    const int kvb0 = PF ? fg / ngroups : 0, kvb1 = PF ? kvb0 + 1 : nkvb;
     const int ch0 = group * kG;
     const float c2 = a.scale * 1.4426950408889634f;
     const int64_t rows_per_kvb = (int64_t)a.kv_div * a.Lq;
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(kNT, 1) void attn_text_kernel(const CcAttnDesc a, i
     for (int r = 0; r < 16; ++r) mask2[r] = (64 + 16 * (r >> 3) + 8 * hi + (r & 7)) < a.Lk ? 0.f : -1e30f;
     const bf16x8 ones = {1, 1, 1, 1, 1, 1, 1, 1};
 
-    for (int kvb = 0; kvb < nkvb; ++kvb) {
+    for (int kvb = kvb0; kvb < kvb1; ++kvb) {
         // ---- stage K (zero-padded rows / columns) and V^T of (kvb, group) ----
         __syncthreads();
         // (requesting all sixteen 16-byte loads of a thread before the first store was slower: 128 / 58 / 59 us against 120 / 50 / 38)
@@ -99,7 +105,10 @@ __global__ __launch_bounds__(kNT, 1) void attn_text_kernel(const CcAttnDesc a, i
         __syncthreads();
 
         const int64_t row0 = (int64_t)kvb * rows_per_kvb;
-        const int ntiles = (int)((rows_per_kvb + 31) / 32);
+        // PF: this split's tiles [tfirst - wave, ntiles) = [split * n / S, (split + 1) * n / S): floor or ceiling of n / S tiles each
+        const int ntiles_kvb = (int)((rows_per_kvb + 31) / 32);
+        const int ntiles = PF ? (int)((int64_t)(split + 1) * ntiles_kvb / nkvb) : ntiles_kvb;
+        const int tfirst = PF ? first + (int)((int64_t)split * ntiles_kvb / nkvb) : first;
         // Q fragments of head h of tile t (B operand): channels 16 ks + 8 hi .. + 7 of this lane's row
         auto load_q = [&](int t, int h, bf16x8(&q)[KS]) {
             const int64_t rloc = (int64_t)t * 32 + l31;
@@ -118,11 +127,11 @@ __global__ __launch_bounds__(kNT, 1) void attn_text_kernel(const CcAttnDesc a, i
         // soon as this tile's head h has used them, so every load has eight head iterations (~8 us) to land.  (One head ahead was
         // not enough: an iteration is ~1 us of work, a loaded-HBM round trip several — the kernel ran at the memory latency.)
         bf16x8 qa[HPG][KS];
-        if (first < ntiles) {
+        if (tfirst < ntiles) {
 #pragma unroll
-            for (int h = 0; h < HPG; ++h) load_q(first, h, qa[h]);
+            for (int h = 0; h < HPG; ++h) load_q(tfirst, h, qa[h]);
         }
-        for (int t = first; t < ntiles; t += stride) {
+        for (int t = tfirst; t < ntiles; t += stride) {
             const int64_t rloc = (int64_t)t * 32 + l31;
             const bool rok = rloc < rows_per_kvb;
             // row of (batch, i): contiguous token rows (q_outer_rows == Lq is checked by the launcher)
@@ -221,12 +230,29 @@ __global__ __launch_bounds__(kNT, 1) void attn_text_kernel(const CcAttnDesc a, i
 template <int D>
 int launch_text(const CcAttnDesc& a, hipStream_t s) {
     static unsigned long long attr_done = 0;
-    if (int rc = cc_max_dynamic_lds((const void*)attn_text_kernel<D>, kLds, &attr_done, "attn_text")) return rc;
+    if (int rc = cc_max_dynamic_lds((const void*)attn_text_kernel<D, false>, kLds, &attr_done, "attn_text")) return rc;
     const int ngroups = a.heads * a.d / kG;
     const int nkvb = a.batches / a.kv_div;
     cc_note_kernel("attn_text_kernel d=%d", D);
-    hipLaunchKernelGGL((attn_text_kernel<D>), dim3(256), dim3(kNT), kLds, s, a, ngroups, nkvb);
+    hipLaunchKernelGGL((attn_text_kernel<D, false>), dim3(256), dim3(kNT), kLds, s, a, ngroups, nkvb);
     return cc_launch_status("attn_text_kernel");
+}
+
+// K / V per frame: frames x groups x S workgroups, S row splits of a frame chosen so that the grid is about one workgroup per CU (256)
+// and no workgroup has fewer tiles than waves unless the whole frame has
+template <int D>
+int launch_text_frame(const CcAttnDesc& a, hipStream_t s) {
+    static unsigned long long attr_done = 0;
+    if (int rc = cc_max_dynamic_lds((const void*)attn_text_kernel<D, true>, kLds, &attr_done, "attn_text_frame")) return rc;
+    const int ngroups = a.heads * a.d / kG;
+    const int ntiles = (a.Lq + 31) / 32;
+    const int64_t fg = (int64_t)a.batches * ngroups;
+    int64_t S = 256 / fg;
+    if (S > ntiles / 8) S = ntiles / 8;
+    if (S < 1) S = 1;
+    cc_note_kernel("attn_text_frame_kernel d=%d", D);
+    hipLaunchKernelGGL((attn_text_kernel<D, true>), dim3((unsigned)(fg * S)), dim3(kNT), kLds, s, a, ngroups, (int)S);
+    return cc_launch_status("attn_text_frame_kernel");
 }
 
 }  // namespace
@@ -234,8 +260,12 @@ int launch_text(const CcAttnDesc& a, hipStream_t s) {
 // text cross-attention geometry: few keys shared by all frames of a clip, contiguous token rows, whole 320-channel groups.
 // Measured against the general kernel (34 frames, 77 keys, cold): d = 40 at 6144 rows per frame 120 / 127 us, d = 80 at 1536 50 / 75,
 // d = 160 at 384 38 / 34 — the staging of two clips' K / V per workgroup is a fifth of that launch: d = 160 stays on the general kernel.
+// CCEDIT_ATTN_KV_PER_FRAME (K / V of its own for every frame, kv_div = 1): never the arm above, whose every workgroup stages every kv
+// batch in turn while its waves stride over that batch's row tiles — with one kv batch per frame that is 34 K / V sets staged in each of
+// 256 workgroups for a tenth of the waves to find a tile.  Such a descriptor takes the per-frame arm (cc_attn_text_frame_applicable)
+// or the general kernels.
 bool cc_attn_text_applicable(const CcAttnDesc& a) {
-    return (a.d == 40 || a.d == 80) && a.Lk <= kKeys && a.Lk >= 64 && a.seg1_len == 0 && !a.causal &&
+    return !(a.flags & CCEDIT_ATTN_KV_PER_FRAME) && (a.d == 40 || a.d == 80) && a.Lk <= kKeys && a.Lk >= 64 && a.seg1_len == 0 && !a.causal &&
            (a.heads * a.d) % kG == 0 && 32 % (a.heads * a.d / kG) == 0 && a.q_inner == 1 && a.q_seq_rows == 1 && a.q_outer_rows == a.Lq &&
            a.kv_inner == 1 && a.kv_seq_rows == 1 && a.kv_outer_rows >= a.Lk && a.batches % a.kv_div == 0 && a.ldo % 8 == 0 &&
            (int64_t)a.kv_div * a.Lq >= 2048;
@@ -247,4 +277,21 @@ int cc_attn_text_launch(const CcAttnDesc& a, hipStream_t s) {
         case 80: return launch_text<80>(a, s);
         default: return launch_text<160>(a, s);
     }
+}
+
+// the per-frame arm: the geometry above without the rows-per-clip condition (a frame is a kv batch).  Kept where it was measured to win
+// over the general kernel by more than the run-to-run spread (34 frames, 77 keys, cold operands, the arms alternating, two processes;
+// DESIGN 3.25): d = 80 at 1536 rows per frame 45.3 / 46.6 us against 74.4 / 72.8.  d = 40 at 6144 rows 118.4 / 116.9 against
+// 122.2 / 116.4 is no win, and at 384 rows and below the staging of a frame's K / V per workgroup loses (d = 80: 29.9 against 23.0;
+// d = 40: 36.0 against 15.1): d = 40 and fewer than kMinFrameRows rows stay on the general kernel.
+constexpr int kMinFrameRows = 1536;
+bool cc_attn_text_frame_applicable(const CcAttnDesc& a) {
+    return (a.flags & CCEDIT_ATTN_KV_PER_FRAME) && a.kv_div == 1 && a.d == 80 && a.Lk <= kKeys && a.Lk >= 64 && a.seg1_len == 0 &&
+           !a.causal && (a.heads * a.d) % kG == 0 && a.q_inner == 1 && a.q_seq_rows == 1 && a.q_outer_rows == a.Lq && a.kv_inner == 1 &&
+           a.kv_seq_rows == 1 && a.kv_outer_rows >= a.Lk && a.ldo % 8 == 0 && a.Lq >= kMinFrameRows &&
+           (int64_t)a.batches * (a.heads * a.d / kG) * 32 < 2147483647LL;
+}
+
+int cc_attn_text_frame_launch(const CcAttnDesc& a, hipStream_t s) {
+    return launch_text_frame<80>(a, s);
 }

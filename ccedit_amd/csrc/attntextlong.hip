@@ -234,8 +234,9 @@ int launch_long_d(const CcAttnDesc& a, hipStream_t s) {
 
 // the geometry of cc_attn_text_applicable (attntext.hip) with 80-channel groups (whole 320-channel groups of them), d = 80 (see the head
 // of the file), and exactly the key counts of 2, 3 and 4 prompt chunks: every one of them ends in the last 32-key tile of its padded count.
+// Like that kernel it stages every kv batch in every workgroup: K / V per frame (CCEDIT_ATTN_KV_PER_FRAME) go to the general kernels.
 bool cc_attn_text_long_applicable(const CcAttnDesc& a) {
-    return a.d == 80 && (a.Lk == 154 || a.Lk == 231 || a.Lk == 308) && a.seg1_len == 0 && !a.causal &&
+    return !(a.flags & CCEDIT_ATTN_KV_PER_FRAME) && a.d == 80 && (a.Lk == 154 || a.Lk == 231 || a.Lk == 308) && a.seg1_len == 0 && !a.causal &&
            (a.heads * a.d) % 320 == 0 && 32 % (a.heads * a.d / kG) == 0 && a.q_inner == 1 && a.q_seq_rows == 1 && a.q_outer_rows == a.Lq &&
            a.kv_inner == 1 && a.kv_seq_rows == 1 && a.kv_outer_rows >= a.Lk && a.batches % a.kv_div == 0 && a.ldo % 8 == 0 &&
            (int64_t)a.kv_div * a.Lq >= 2048;

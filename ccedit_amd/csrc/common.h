@@ -202,6 +202,8 @@ int cc_automask_expand(const uint8_t* lat, uint8_t* px, int64_t N, int32_t h, in
 
 // Weighted prompts (prompt.hip); entry point and argument checks in core.cpp
 int cc_prompt_weight(const float* z, const float* e, const float* w, float* out, int64_t R, int32_t C, hipStream_t s);
+int cc_prompt_schedule(const float* c, const int32_t* k0, const int32_t* k1, const float* a, float* out, int32_t N, int32_t L, int32_t C,
+                       hipStream_t s);
 
 // Propagation launchers (propagate.hip); entry points and argument checks in core.cpp
 int cc_prop_pyramid(const uint8_t* rgb, uint8_t* pyr, int32_t F, int32_t H, int32_t W, hipStream_t s);

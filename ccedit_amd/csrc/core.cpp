@@ -339,6 +339,27 @@ extern "C" int ccedit_prompt_weight(const float* z, const float* e, const float*
     return cc_prompt_weight(z, e, w, out, (int64_t)B * L, C, (hipStream_t)stream);
 }
 
+// ---- prompt schedules (kernel and launcher: prompt.hip).  k0, k1 and a are HOST tables: every index is checked here, and the launcher
+// passes the checked values to the kernel by value, so a bad index is this status and never an address.
+extern "C" int ccedit_prompt_schedule(const float* c, const int32_t* k0, const int32_t* k1, const float* a, float* out, int32_t P, int32_t N,
+                                      int32_t L, int32_t C, void* stream) {
+    CC_CHECK_ARG(c && k0 && k1 && a && out, "ccedit_prompt_schedule: null pointer");
+    CC_CHECK_ARG(P > 0 && N > 0 && L > 0 && C > 0, "ccedit_prompt_schedule: P=%d N=%d L=%d C=%d (positive)", P, N, L, C);
+    CC_CHECK_ARG((int64_t)P * L * C < kPixelMax * 4 && (int64_t)N * L * C < kPixelMax * 4,
+                 "ccedit_prompt_schedule: more than 2^33 elements in one call (P=%d N=%d L=%d C=%d)", P, N, L, C);
+    CC_CHECK_ARG(((uintptr_t)c & 3) == 0 && ((uintptr_t)out & 3) == 0, "ccedit_prompt_schedule: c and out must be 4-byte aligned");
+    for (int32_t f = 0; f < N; ++f) {
+        CC_CHECK_ARG(k0[f] >= 0 && k0[f] < P && k1[f] >= 0 && k1[f] < P, "ccedit_prompt_schedule: frame %d: k0=%d k1=%d outside the %d prompts", f,
+                     k0[f], k1[f], P);
+        CC_CHECK_ARG(a[f] >= 0.0f && a[f] <= 1.0f, "ccedit_prompt_schedule: frame %d: a=%g (0 ... 1)", f, (double)a[f]);
+    }
+    {
+        const uintptr_t cb = (uintptr_t)c, ce = cb + (uintptr_t)((int64_t)P * L * C * 4), ob = (uintptr_t)out, oe = ob + (uintptr_t)((int64_t)N * L * C * 4);
+        CC_CHECK_ARG(ce <= ob || oe <= cb, "ccedit_prompt_schedule: out must not alias c (a frame reads prompts other frames' rows overlap)");
+    }
+    return cc_prompt_schedule(c, k0, k1, a, out, N, L, C, (hipStream_t)stream);
+}
+
 // ---- propagation of edited keyframes to every source frame (kernels and launchers: propagate.hip).  Everything the host can see is
 // checked here, before any HIP call; the device tables (pairs, rank, g, the block vectors) are held in range by the kernels themselves.
 static int prop_shape_ok(const char* fn, int32_t P, int32_t F, int32_t H, int32_t W) {

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("CCEDIT_HIP_LIB") or os.path.join(_HERE, "libccedit_hi
 
 ABI_VERSION = 12
 ATTN_Q_LOG2 = 1          # CcAttnDesc.flags: CCEDIT_ATTN_Q_LOG2
+ATTN_KV_PER_FRAME = 2    # CcAttnDesc.flags: CCEDIT_ATTN_KV_PER_FRAME
 
 GEMM_LINEAR, GEMM_CONV2D, GEMM_TEMPORAL = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU = 0, 1, 2, 3
@@ -168,6 +169,9 @@ _SIGS = {
     "ccedit_automask_expand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     # weighted prompts (csrc/prompt.hip): added within ABI 12, nothing existing changed
     "ccedit_prompt_weight": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    # prompt schedules (csrc/prompt.hip): added within ABI 12, nothing existing changed; k0, k1 and a are host tables
+    "ccedit_prompt_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     # propagation of edited keyframes (csrc/propagate.hip): added within ABI 12, nothing existing changed
     "ccedit_prop_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ccedit_prop_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

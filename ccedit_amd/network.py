@@ -417,8 +417,12 @@ class BasicTransformerBlock(nn.Module):
         q = ln_linear(tok, self.norm2, a2.to_q.pw, self.q2_ln)
         # [B*L, 2C]: once per clip, shared by its T frames; normally a column slice of the network's batched projection (TextKV)
         kv = ctx_kv_src.of(self) if isinstance(ctx_kv_src, TextKV) else ops.linear(ctx_kv_src, a2.kv)
+        # ... or [B*T*L, 2C]: a context per frame (a prompt schedule, ccedit_amd/schedule.py) — every frame attends to its own keys
+        per_frame = frames_per_clip > 1 and kv.shape[0] == frames * ctx_len
+        if not per_frame and kv.shape[0] * frames_per_clip != frames * ctx_len:
+            raise ValueError(f"text context of {kv.shape[0]} rows: expected {frames // frames_per_clip} clips or {frames} frames of {ctx_len} rows")
         o = ops.attention(q, kv[:, :c], kv[:, c:], a2.heads, a2.dim_head, batches=frames, lq=hw, lk=ctx_len,
-                          kv_div=frames_per_clip)
+                          kv_div=1 if per_frame else frames_per_clip, kv_per_frame=per_frame)
         if tail is not None:
             return transformer_tail(self.ff, self.norm3, a2.to_out[0], o, tok, *tail)
         tok = linear_ln_producer(o, a2.to_out[0].pw, res1=tok)
@@ -809,6 +813,15 @@ class EmbOut:
         return self.e_all[:, sl[0]:sl[0] + sl[1]]
 
 
+def context_per_frame(context: torch.Tensor, b: int, t: int) -> bool:
+    """`cond["crossattn"]` is (B, L, C): one context per clip, or (B*T, L, C) in (b t) order: one per frame (True).  With T == 1 the two
+    are the same thing and it is the former."""
+    if context.dim() != 3 or context.shape[0] not in (b, b * t):
+        raise ValueError(f"crossattn {tuple(context.shape)}: expected ({b}, L, C), one context per clip, or ({b * t}, L, C), one per frame "
+                         f"of {b} clips of {t} frames")
+    return t > 1 and context.shape[0] == b * t
+
+
 class TextKV:
     """Text-conditioning keys / values of one network evaluation.  Every BasicTransformerBlock projects the SAME (B * 77, 768) context
     with its own to_k / to_v (attention.py:392-467; 16 blocks in the UNet, 7 in a ControlNet): they run as ONE GEMM against the
@@ -1085,6 +1098,7 @@ class ControlNet2D(UNetModel):
             return [ops.nhwc_to_ncthw(r, b, 1, r.shape[-1])[:, :, 0] for r in res]
         b, _, t, _, _ = x.shape
         geo = Geometry(b, t)
+        context_per_frame(context, b, t)
         ctx2d = context.to(torch.bfloat16).reshape(-1, context.shape[-1]).contiguous()
         guided = self.hint_stem(ops.ncthw_to_nhwc(hint.float().contiguous(), 8))
         res = self.run(ops.ncthw_to_nhwc(x.float().contiguous(), 8), guided, timesteps, ctx2d, context.shape[1], geo)
@@ -1179,6 +1193,7 @@ class ControlledUNetModel3DTV2V(UNetModel3D):
             raise NotImplementedError("only_mid_control / control=None")
         b, _, t, _, _ = x.shape
         geo = Geometry(b, t)
+        context_per_frame(context, b, t)
         ctx2d = context.to(torch.bfloat16).reshape(-1, context.shape[-1]).contiguous()
         ctrl = [ops.ncthw_to_nhwc(c.float().contiguous(), c.shape[1]) for c in control]
         del control[:]
@@ -1262,7 +1277,7 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
         for cache in (self._hint_val, self._hint_dup, self._hint_slices, self._twin_val, self._tkv_val, self._graphs):
             cache.clear()
 
-    _RESERVED = ("_windows", "_contexts", "_graph_slots", "_hint_slots", "_tkv_slots", "_graph_pool", "graph_counts")
+    _RESERVED = ("_windows", "_contexts", "_graph_slots", "_hint_slots", "_tkv_slots", "_graph_pool", "graph_counts", "_window_contexts")
 
     def _caches(self):
         return (self._hint_val, self._hint_dup, self._hint_slices, self._twin_val, self._tkv_val, self._graphs)
@@ -1381,14 +1396,17 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
     _graph_pool = None
     _windows = 1
     _contexts = 1
+    _window_contexts = False    # per-frame text contexts: every window has its own slice (reserve_windows)
     graph_counts = None         # {"eager", "capture", "replay"}: evaluations of _forward_graphed by kind since reserve_windows / first use
 
-    def reserve_windows(self, windows: int) -> None:
+    def reserve_windows(self, windows: int, frame_contexts: bool = False) -> None:
         """Size the per-clip caches for `windows` conditioning keys evaluated in turn (0: back to a plain clip's limits, text contexts
-        included; 1 or more: per text context of reserve_contexts)."""
+        included; 1 or more: per text context of reserve_contexts).  frame_contexts: the text context is one per frame (a prompt
+        schedule), so every window has a slice of its own and the text K / V cache holds windows x contexts entries per network."""
         if int(windows) <= 0:
             self._contexts = 1
         self._windows = max(int(windows), 1)
+        self._window_contexts = bool(frame_contexts) and int(windows) > 0
         self._reserve()
 
     def reserve_contexts(self, contexts: int) -> None:
@@ -1400,7 +1418,7 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
         w, keys = self._windows, self._windows * self._contexts
         self._graph_slots = max(2, keys)
         self._hint_slots = max(4, 2 * w)           # per window: one stem output per kind of evaluation (shared CFG prefix or not)
-        self._tkv_slots = max(6, 2 * self._contexts)
+        self._tkv_slots = max(6, 2 * self._contexts * (w if self._window_contexts else 1))
         self._graph_pool = torch.cuda.graph_pool_handle() if keys > 1 and torch.cuda.is_available() else None
         self.graph_counts = dict(eager=0, capture=0, replay=0)
 
@@ -1504,7 +1522,9 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
             OpenAIWrapperControlLDM3DTV2V._half_stream = torch.cuda.Stream()
         hs = OpenAIWrapperControlLDM3DTV2V._half_stream
         hs.wait_stream(main)
-        halves = [{k: (v[i:i + 1].contiguous() if torch.is_tensor(v) else v) for k, v in c.items()} for i in range(2)]
+        nt = x.shape[2] if context_per_frame(c["crossattn"], 2, x.shape[2]) else 1       # (a per-frame context: T rows to a half)
+        halves = [{k: ((v[i * nt:(i + 1) * nt] if k == "crossattn" else v[i:i + 1]).contiguous() if torch.is_tensor(v) else v)
+                   for k, v in c.items()} for i in range(2)]
         def half(i):        # (its slices of x and t are made on the stream it runs on)
             return self._evaluate(x[i:i + 1].contiguous(), t[i:i + 1].contiguous(), halves[i], frame_shard=frame_shards[i],
                                   row_shard=row_shards[i], half=True, twins=False)
@@ -1585,6 +1605,8 @@ class OpenAIWrapperControlLDM3DTV2V(IdentityWrapper):
                              f"skips are concatenated with the 2x-upsampled decoder tensors, controlmodel.py:539-543)")
         if tuple(c["control_hint"].shape[-2:]) != (8 * lh, 8 * lw):
             raise ValueError(f"control_hint {tuple(c['control_hint'].shape)} does not match latent {lh}x{lw} (x8)")
+        if context_per_frame(c["crossattn"], b, nt) and (sh is not None or rs is not None):      # (before anything is sliced or launched)
+            raise NotImplementedError("a per-frame text context (crossattn of B*T rows) is not implemented for sharded evaluations")
         xs, hint5, cond_feat = self._shard_inputs(x, c, sh, rs)
         geo = Geometry(b, xs.shape[2], sh, rows=rs)
         context = c["crossattn"]

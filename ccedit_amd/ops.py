@@ -563,9 +563,12 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: 
               kv_div: int = 1, kv_inner: int = 1, kv_outer_rows: Optional[int] = None, kv_inner_rows: int = 0,
               kv_seq_rows: int = 1, out: Optional[torch.Tensor] = None,
               seg1_len: int = 0, seg1_div: int = 1, seg1_mul: int = 0, seg1_add: int = 0, causal: bool = False,
-              q_log2: bool = False, scale: Optional[float] = None) -> torch.Tensor:
+              q_log2: bool = False, scale: Optional[float] = None, kv_per_frame: bool = False) -> torch.Tensor:
     """q/k/v: 2-D row-major views [rows, >= heads*d] (may be column slices of a fused buffer).  q_log2: q already carries
-    d^-0.5 * log2(e) (folded into the to_q weights by the packer).  scale: the softmax scale, None = d^-0.5 (ignored with q_log2)."""
+    d^-0.5 * log2(e) (folded into the to_q weights by the packer).  scale: the softmax scale, None = d^-0.5 (ignored with q_log2).
+    kv_per_frame: text K/V of its own for every batch (CCEDIT_ATTN_KV_PER_FRAME; kv_div must be 1)."""
+    if kv_per_frame and kv_div != 1:
+        raise ValueError(f"attention: kv_per_frame means one kv batch per batch, got kv_div={kv_div}")
     for tns in (q, k, v):
         assert tns.dtype == BF16 and tns.is_cuda and tns.stride(-1) == 1
     if out is None:
@@ -580,7 +583,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: 
     a.scale = float(d) ** -0.5 if scale is None else float(scale)
     a.seg1_len, a.seg1_div, a.seg1_mul, a.seg1_add = seg1_len, seg1_div, seg1_mul, seg1_add
     a.causal = int(causal)
-    a.flags = hip.ATTN_Q_LOG2 if q_log2 else 0
+    a.flags = (hip.ATTN_Q_LOG2 if q_log2 else 0) | (hip.ATTN_KV_PER_FRAME if kv_per_frame else 0)
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -1151,6 +1154,33 @@ def prompt_weight(z: torch.Tensor, e: torch.Tensor, w: torch.Tensor, out: Option
     _launch_mem("prompt_weight", 4.0 * (2 * z.numel() + e.numel() + w.numel()), lambda: hip.check(hip.lib().ccedit_prompt_weight(
         z.data_ptr(), e.data_ptr(), w.data_ptr(), y.data_ptr(), b, l, c, _stream()), "ccedit_prompt_weight"), (b, l, c))
     return y
+
+
+def prompt_schedule(contexts: torch.Tensor, k0, k1, a, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """contexts fp32 (P, L, C) on the device; k0, k1 int32 [N] and a float32 [N]: the HOST table of ccedit_amd/schedule.py's plan ->
+    fp32 (N, L, C): contexts[k0] where a == 0, contexts[k1] where a == 1 (bit copies), else c0 + a * (c1 - c0) in fp32 subtract,
+    multiply, add: bit-equal to tests/_schedule_numpy.py.  The library checks every index before it launches."""
+    import numpy as np
+    if contexts.dtype != torch.float32 or not contexts.is_cuda or contexts.dim() != 3:
+        raise ValueError(f"prompt_schedule: contexts must be a cuda fp32 tensor (P, L, C), got {contexts.dtype} {contexts.device} {tuple(contexts.shape)}")
+    if not contexts.is_contiguous():
+        raise ValueError("prompt_schedule: contexts must be contiguous")
+    k0 = np.ascontiguousarray(k0, dtype=np.int32)
+    k1 = np.ascontiguousarray(k1, dtype=np.int32)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if k0.ndim != 1 or k0.shape != k1.shape or k0.shape != a.shape or k0.size == 0:
+        raise ValueError(f"prompt_schedule: k0, k1 and a must be vectors of one length N >= 1, got {k0.shape}, {k1.shape}, {a.shape}")
+    p, l, c = contexts.shape
+    n = int(k0.size)
+    if out is None:
+        out = torch.empty((n, l, c), dtype=torch.float32, device=contexts.device)
+    elif tuple(out.shape) != (n, l, c) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"prompt_schedule: out must be a contiguous cuda fp32 tensor {(n, l, c)}, got {out.dtype} {tuple(out.shape)}")
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    _launch_mem("prompt_schedule", 4.0 * 3 * out.numel(), lambda: hip.check(hip.lib().ccedit_prompt_schedule(
+        contexts.data_ptr(), k0.ctypes.data_as(i32p), k1.ctypes.data_as(i32p), a.ctypes.data_as(f32p), out.data_ptr(), p, n, l, c, _stream()),
+        "ccedit_prompt_schedule"), (p, n, l, c))
+    return out
 
 
 # ------------------------------------------------------------------------------------------

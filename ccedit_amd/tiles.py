@@ -142,14 +142,18 @@ class TiledDenoiser:
         self._hints = None                                       # (source, version, [crops])
         self._windowed = {}                                      # tile index -> its WindowedDenoiser
 
-    def tables(self, lh: int, lw: int, num_frames: int, device):
-        key = (int(lh), int(lw), int(num_frames), str(device))
+    def tables(self, lh: int, lw: int, num_frames: int, device, frame_contexts: bool = False):
+        key = (int(lh), int(lw), int(num_frames), str(device)) + ((True,) if frame_contexts else ())
         if key not in self._tables:
             starts, coef = plan2d(lh, lw, self.th, self.tw, self.oh, self.ow)
             self._tables[key] = (starts, torch.tensor(starts, dtype=torch.int32, device=device).reshape(len(starts), 2),
                                  torch.from_numpy(coef).to(device))
             if self.wrapper is not None and hasattr(self.wrapper, "reserve_windows"):
-                self.wrapper.reserve_windows(len(starts) * window_count(num_frames, self.window, self.window_overlap))
+                nw = window_count(num_frames, self.window, self.window_overlap)
+                if frame_contexts and nw > 1:        # a per-frame text context is sliced per window inside every tile (windows.py)
+                    self.wrapper.reserve_windows(len(starts) * nw, frame_contexts=True)
+                else:
+                    self.wrapper.reserve_windows(len(starts) * nw)
         return self._tables[key]
 
     def _tile_hints(self, hint: torch.Tensor, starts) -> List[torch.Tensor]:
@@ -187,7 +191,11 @@ class TiledDenoiser:
         hint = cond["control_hint"]
         if tuple(hint.shape[2:]) != (n, 8 * lh, 8 * lw):
             raise ValueError(f"control_hint {tuple(hint.shape)} does not match a latent of {n} frames of {lh}x{lw} (x8)")
-        starts, starts_dev, coef_dev = self.tables(lh, lw, n, x.device)
+        ctx = cond.get("crossattn")
+        if torch.is_tensor(ctx) and ctx.dim() == 3 and n > 1 and ctx.shape[0] == x.shape[0] * n:      # (one text context per frame)
+            starts, starts_dev, coef_dev = self.tables(lh, lw, n, x.device, True)
+        else:
+            starts, starts_dev, coef_dev = self.tables(lh, lw, n, x.device)
         hints = self._tile_hints(hint, starts)
         xt = ops.tile_gather(x, starts_dev, self.th, self.tw)
         twins = ops.get_mark(input, "_cfg_twin_halves") is True

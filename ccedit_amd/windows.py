@@ -93,15 +93,32 @@ class WindowedDenoiser:
         check_supported(wrapper=wrapper)
         self._tables = {}                                        # (N, device) -> (starts, starts_dev, coef_dev)
         self._hints = None                                       # (source, version, [slices])
+        self._ctxs = None                                        # (source, version, [slices]) of a per-frame text context
 
-    def tables(self, num_frames: int, device):
-        key = (int(num_frames), str(device))
+    def tables(self, num_frames: int, device, frame_contexts: bool = False):
+        key = (int(num_frames), str(device)) + ((True,) if frame_contexts else ())
         if key not in self._tables:
             starts, coef = plan(num_frames, self.window, self.overlap)
             self._tables[key] = (starts, torch.tensor(starts, dtype=torch.int32, device=device), torch.from_numpy(coef).to(device))
             if self.wrapper is not None and hasattr(self.wrapper, "reserve_windows"):
-                self.wrapper.reserve_windows(len(starts))
+                if frame_contexts:                               # (a slice of the text context per window: the text K / V cache grows)
+                    self.wrapper.reserve_windows(len(starts), frame_contexts=True)
+                else:
+                    self.wrapper.reserve_windows(len(starts))
         return self._tables[key]
+
+    def _window_contexts(self, ctx: torch.Tensor, b: int, n: int, starts: List[int]) -> List[torch.Tensor]:
+        """A per-frame text context (B * N, L, C) in (b t) order (a prompt schedule) is sliced along the frame axis exactly as
+        control_hint is: W stable tensors (B * T, L, C) per source tensor."""
+        ent = self._ctxs
+        if ent is None or ent[0] is not ctx or ent[1] != ctx._version or len(ent[2]) != len(starts):
+            c5 = ctx.view(b, n, *ctx.shape[1:])
+            slices = []
+            for s in starts:
+                sl = c5[:, s:s + self.window]
+                slices.append(ctx if sl.shape[1] == n else sl.reshape(b * sl.shape[1], *ctx.shape[1:]).contiguous())
+            ent = self._ctxs = (ctx, ctx._version, slices)
+        return ent[2]
 
     def _window_hints(self, hint: torch.Tensor, starts: List[int]) -> List[torch.Tensor]:
         from . import ops
@@ -128,8 +145,11 @@ class WindowedDenoiser:
         n = x.shape[2]
         if cond["control_hint"].shape[2] != n:
             raise ValueError(f"control_hint of {cond['control_hint'].shape[2]} frames for a latent of {n}")
-        starts, starts_dev, coef_dev = self.tables(n, x.device)
+        ctx = cond.get("crossattn")
+        per_frame = torch.is_tensor(ctx) and ctx.dim() == 3 and n > 1 and ctx.shape[0] == x.shape[0] * n
+        starts, starts_dev, coef_dev = self.tables(n, x.device, per_frame) if per_frame else self.tables(n, x.device)
         hints = self._window_hints(cond["control_hint"], starts)
+        ctxs = self._window_contexts(ctx, x.shape[0], n, starts) if per_frame else None
         xw = ops.window_gather(x, starts_dev, self.window)
         twins = ops.get_mark(input, "_cfg_twin_halves") is True
         ys = []
@@ -139,6 +159,8 @@ class WindowedDenoiser:
                 ops.set_mark(xi, "_cfg_twin_halves", True)
             ci = dict(cond)
             ci["control_hint"] = hints[i]
+            if ctxs is not None:
+                ci["crossattn"] = ctxs[i]
             ys.append(self.denoiser(xi, sigma, ci).float().contiguous())
         return ops.window_fuse(ys, starts_dev, coef_dev, n)
 

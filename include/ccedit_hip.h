@@ -302,6 +302,11 @@ typedef struct CcAttnDesc {
 /* q already carries scale * log2(e) (folded into the to_q weights by the packer, one rounding instead of two): kernels then take
  * p = 2^(q.k - reference) without multiplying, and `scale` is ignored */
 #define CCEDIT_ATTN_Q_LOG2 1
+/* kv_div == 1 on the text form: every batch (frame) has K/V of its own (a prompt schedule's per-frame context).  Keeps the descriptor
+ * off the text arms that stage the K/V a whole clip shares.  At d = 80, 64 <= Lk <= 96 and Lq >= 1536 contiguous rows per frame it is
+ * served by the per-frame arm of attn_text_kernel (work split by frame, 320-channel group and row split), otherwise by the general
+ * kernels.  With the flag, kv_div != 1 is an argument error. */
+#define CCEDIT_ATTN_KV_PER_FRAME 2
 
 int ccedit_attention(const CcAttnDesc* desc, void* stream);
 
@@ -593,6 +598,22 @@ int ccedit_automask_expand(const void* lat, void* px, int64_t N, int32_t h, int3
  *   C % 4 == 0 and the pointers allow, one element per access otherwise.
  */
 int ccedit_prompt_weight(const float* z, const float* e, const float* w, float* out, int32_t B, int32_t L, int32_t C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Prompt schedules (added without an ABI bump: one new function and one flag of CcAttnDesc.flags, CCEDIT_ABI_VERSION stays 12).  A
+ * prompt per time span of a clip (`--prompt_at`, `--prompt_ease`; ccedit_amd/schedule.py): the P distinct encoded prompts and a table
+ * per keyframe become one text context per frame, which the spatial transformers' text attention then reads with kv_div = 1 and
+ * CCEDIT_ATTN_KV_PER_FRAME.  Kernel: csrc/prompt.hip.
+ *
+ * ccedit_prompt_schedule: c fp32 [P][L][C] and out fp32 [N][L][C] are device pointers; k0, k1 (int32 [N], indices into the P prompts)
+ *   and a (fp32 [N], 0 ... 1) are HOST tables.  out[f] = c[k0[f]] where a[f] == 0, c[k1[f]] where a[f] == 1 (both BIT COPIES, signed
+ *   zeros included), otherwise c[k0[f]] + a[f] * (c[k1[f]] - c[k0[f]]): fp32 subtract, multiply, add in that order, each rounded, never
+ *   an fma: bit-equal to tests/_schedule_numpy.py.  No reduction.  An index outside [0, P), an a outside [0, 1] or NaN is status -1
+ *   before any launch (out is left untouched); the kernel receives the checked table by value.  One launch per 256 frames; 16-byte
+ *   accesses where C % 4 == 0 and the pointers allow, one element per access otherwise.  out must not overlap c.
+ */
+int ccedit_prompt_schedule(const float* c, const int32_t* k0, const int32_t* k1, const float* a, float* out, int32_t P, int32_t N, int32_t L,
+                           int32_t C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Propagation (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  Full-frame-rate output: the edited

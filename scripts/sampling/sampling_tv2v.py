@@ -215,6 +215,15 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="every --region_mask is ONE image painted on source frame --region_frame and followed through the clip on the device "
                         "(ccedit_amd/masktrack.py), like --mask_track.  Needs a video and --H, --W multiples of 64")
     p.add_argument("--region_frame", type=int, default=0, help="with --region_track: the source frame the region masks were painted on")
+    p.add_argument("--prompt_at", action="append", default=None, metavar="INDEX:TEXT",
+                   help="(not in the reference script) a prompt schedule: from keyframe INDEX (0 ... num_keyframes - 1, negative values count "
+                        "from the end, written --prompt_at=-1:TEXT) the prompt is TEXT (everything after the first colon); repeatable.  --prompt stays the base prompt and "
+                        "holds from keyframe 0 up to the first keyed index; --add_prompt is put in front of every scheduled text; "
+                        "--negative_prompt is not scheduled.  Between two keyed frames the text context moves from one prompt's to the next's "
+                        "(--prompt_ease); every frame attends to its own context in ONE network evaluation (ccedit_amd/schedule.py)")
+    p.add_argument("--prompt_ease", type=str, default="linear", choices=["linear", "smooth", "step"],
+                   help="how the context moves between two keyed frames f0 < f1 of --prompt_at: linear a = (f - f0) / (f1 - f0); smooth "
+                        "a^2 (3 - 2 a) of it; step: the earlier prompt before the midpoint, the later one from it on")
     p.add_argument("--propagate", action="store_true",
                    help="(not in the reference script) full-frame-rate output: after a clip's keyframes are saved, every source frame from the "
                         "first to the last keyframe gets an edited frame — the two neighbouring edited keyframes carried along the source's "
@@ -280,6 +289,7 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
     check_mask_options(args)                 # (--mask_track and its kin: ValueError, here and again where the masks are made)
     check_region_options(args)               # (--region_prompt and its kin: ValueError; nothing is imported or checked without the flags)
     check_mask_auto(args)                    # (--mask_auto and its kin: ValueError; nothing is imported or checked without the flag)
+    check_prompt_schedule(args)              # (--prompt_at: ValueError / NotImplementedError; nothing is imported or checked without the flag)
 
 
 def windowing(args) -> bool:
@@ -866,6 +876,72 @@ def auto_masks(args, model, dev, batch, batch_uc, c, cvideos, keyframes, source_
 
 
 # ------------------------------------------------------------------------------------------
+# Prompt schedules: --prompt_at INDEX:TEXT / --prompt_ease (ccedit_amd/schedule.py)
+# ------------------------------------------------------------------------------------------
+def schedule_on(args) -> bool:
+    """A schedule is active when --prompt_at was given; otherwise nothing of it is imported or called."""
+    return bool(getattr(args, "prompt_at", None))
+
+
+def check_prompt_schedule(args, with_ref: bool = False) -> None:
+    """Before any video is opened, from the flags alone: what --prompt_at needs and what it cannot be combined with (ValueError /
+    NotImplementedError naming the flags).  Without the flag everything passes."""
+    if not schedule_on(args):
+        return
+    if with_ref:
+        raise NotImplementedError("--prompt_at is not available with a reference image (sampling_tv2v_ref.py): the reference image belongs "
+                                  "to one centre frame, a prompt per time span does not go with it")
+    from ccedit_amd import schedule
+    schedule.parse(args.prompt_at, args.num_keyframes)               # an index outside the clip, a duplicate, an empty text
+    if not (args.prompt and args.video_path) or args.prompt_listpath or args.videos_directory or args.json_path:
+        raise ValueError("--prompt_at schedules the prompts of ONE video: give --prompt (the base prompt) with --video_path, not "
+                         "--prompt_listpath / --videos_directory / --json_path with their several jobs")
+    if regions_on(args):
+        raise NotImplementedError("--prompt_at with --region_prompt / --region_mask: region prompts take one context per clip and region — "
+                                  "a schedule per region is not implemented, drop one of them")
+    if mask_auto_on(args):
+        raise NotImplementedError("--prompt_at with --mask_auto: the automatic mask compares ONE source prompt with ONE target prompt — "
+                                  "save the mask with --mask_auto_save DIR in a run without --prompt_at and give it as --mask_root DIR")
+    if _dist_rank_world()[1] > 1:
+        raise NotImplementedError("--prompt_at is not available in the multi-GPU modes (WORLD_SIZE > 1; the frame- and row-sharded network "
+                                  "wrappers refuse a text context per frame themselves): a schedule is evaluated on one GPU")
+
+
+def check_schedule_jobs(args, num_jobs: int) -> None:
+    """Before any video is opened: a schedule belongs to ONE clip, so one job per invocation and one clip per chunk (ValueError)."""
+    if not schedule_on(args):
+        return
+    if num_jobs > 1:
+        raise ValueError(f"--prompt_at with {num_jobs} jobs: a schedule belongs to one video — run one --prompt / --video_path job per invocation")
+    if args.batch_size > 1 and num_jobs * args.num_samples > 1:
+        raise ValueError(f"--prompt_at with --batch_size {args.batch_size} and {num_jobs * args.num_samples} clips: a chunk of several clips "
+                         "shares one conditioning batch, a schedule belongs to one clip — add --batch_size 1")
+
+
+def schedule_texts(args):
+    """(texts, keys) of the run: the distinct composed-later texts (the base prompt first unless keyframe 0 is keyed) and the keyed
+    (keyframe, text id) pairs; ONE text: the schedule says what --prompt alone says, the plain path runs."""
+    from ccedit_amd import schedule
+    return schedule.distinct(args.prompt, schedule.parse(args.prompt_at, args.num_keyframes))
+
+
+def schedule_conditioning(args, model, dev, batch, batch_uc, c, uc, txt, keys):
+    """The per-frame text contexts of one clip: `txt` holds the P distinct prompts as batch['txt'] takes them (strings, ids or finished
+    embeddings); each goes through the conditioner like the main prompt (as a region prompt does), ccedit_prompt_schedule makes the N
+    contexts and the negative context is repeated N times — both ONCE per clip.  Returns the log entry; c / uc are updated in place."""
+    from ccedit_amd import schedule
+    if c["crossattn"].shape[0] != 1:
+        raise ValueError(f"--prompt_at with a chunk of {c['crossattn'].shape[0]} clips: a schedule belongs to one clip — add --batch_size 1")
+    ctxs = [c["crossattn"][:1]]
+    for p in range(1, len(txt)):
+        cp, _ = model.conditioner.get_unconditional_conditioning(dict(batch, txt=txt[p:p + 1]), batch_uc=batch_uc)
+        ctxs.append(cp["crossattn"][:1].to(dev))
+    k0, k1, a = table = schedule.plan(keys, args.num_keyframes, args.prompt_ease)
+    c["crossattn"], uc["crossattn"] = schedule.conditioning(torch.cat(ctxs).float().contiguous(), uc["crossattn"][:1], table)
+    return schedule.table_log(keys, k0, k1, a, args.prompt_ease)
+
+
+# ------------------------------------------------------------------------------------------
 # Region prompts: --region_prompt / --region_mask pairs (ccedit_amd/regions.py)
 # ------------------------------------------------------------------------------------------
 def regions_on(args) -> bool:
@@ -1213,12 +1289,15 @@ def run_jobs(args, with_ref: bool = False) -> None:
     check_tiling(args, with_ref)
     check_region_options(args, with_ref)
     check_mask_auto(args, with_ref)
+    check_prompt_schedule(args, with_ref)
     from ccedit_amd.parallel import shard_clips
     from scripts.sampling.util import chunk, load_img, load_video_keyframes, model_load_ckpt, perform_save_locally_video
     prompts, video_paths, video_save_paths, ref_paths = expand_jobs(args, with_ref)
     num_samples, batch_size = args.num_samples, args.batch_size
     check_propagate(args, video_paths)
     check_region_jobs(args, len(prompts))
+    check_schedule_jobs(args, len(prompts))
+    sched_texts, sched_keys = schedule_texts(args) if schedule_on(args) else ([], [])
     print("\nNumber of prompts: {}".format(len(prompts)))
     print("Generate {} samples for each prompt".format(num_samples))
     rep = lambda lst: [item for item in lst for _ in range(num_samples)]
@@ -1279,7 +1358,9 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 continue
             keyframes = torch.cat(kfs, dim=0).to(dev)                    # (bs, 3, T, H, W) in [-1, 1]
             depth = torch.cat([depth_frames(args, v, k) for v, k in zip(cvideos, kfs)], dim=0).to(dev)
-            region_txt = prompt_log = source_txt = None
+            region_txt = prompt_log = source_txt = sched_log = None
+            if len(sched_texts) > 1:         # a prompt schedule: its P distinct texts ride as P "clips" through the text route of the flags
+                cprompts = list(sched_texts)
             if prompts_on(args):     # every prompt of the chunk in chunks of 77 tokens, one length for all (refusals before any launch)
                 source_kw = dict(source=compose_prompt(args, args.source_prompt)) if mask_auto_on(args) else {}
                 txt, txt_uc, region_txt, prompt_log, *source_txt = long_text(args, model, dev, [compose_prompt(args, q) for q in cprompts],
@@ -1304,10 +1385,17 @@ def run_jobs(args, with_ref: bool = False) -> None:
                     raise NotImplementedError                            # as the reference: sampling_tv2v_ref.py:366-369
                 ref = torch.cat([load_img(r, (H, W), **_io_device(args)) for r in crefs], dim=0).to(dev)
                 batch["cond_img"], batch_uc["cond_img"] = ref, ref.clone()
+            if len(sched_texts) > 1:         # (the conditioner sees one clip: the base text's; the others follow in schedule_conditioning)
+                batch["txt"], batch_uc["txt"] = txt[:1], txt_uc[:1]
             c, uc = model.conditioner.get_unconditional_conditioning(batch, batch_uc=batch_uc)
             for k in c:
                 if isinstance(c[k], torch.Tensor):
                     c[k], uc[k] = c[k][:bs].to(dev), uc[k][:bs].to(dev)
+            if len(sched_texts) > 1:
+                sched_log = schedule_conditioning(args, model, dev, batch, batch_uc, c, uc, txt, sched_keys)
+            elif schedule_on(args):          # every keyed text is the base prompt: the plain path, logged
+                from ccedit_amd import schedule
+                sched_log = schedule.table_log(sched_keys, *schedule.plan(sched_keys, args.num_keyframes, args.prompt_ease), args.prompt_ease)
             randn = torch.randn(bs, 4, T, H // 8, W // 8, generator=g).to(dev)
             mask_px = mask_lat = auto_log = None
             if args.inpainting_mode:                                      # (no mask: NotImplementedError, as the flag alone always was)
@@ -1348,6 +1436,8 @@ def run_jobs(args, with_ref: bool = False) -> None:
             if prompt_log is not None:
                 log_info.setdefault("prompts", [])
                 log_info["prompts"] += prompt_log
+            if sched_log is not None:
+                log_info["prompt_schedule"] = sched_log
             if auto_log is not None:                                      # the settings once, the fraction of latent cells set per clip
                 log_info["mask_auto"] = dict(auto_log, fractions=log_info.get("mask_auto", {}).get("fractions", []) + auto_fractions)
             os.makedirs(os.path.dirname(log_path), exist_ok=True)
