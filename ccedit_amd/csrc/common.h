@@ -80,6 +80,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 // ("specialised kernels reproduce the generic ones", tests/test_fullsize_gpu.py), never a change of arithmetic.
 struct CcPolicy {
     int conv_halo = 1;      // 3x3 stride-1 convs on the LDS-halo kernel with the four-slot weight ring (2: the two-slot kernel of rounds 2-5; 0: tap-gather)
+    int conv_wide = 1;      // ... on 256-pixel (16 x 16) tiles: 1 where it measured faster (convhalo.hip: cc_conv_wide_auto), 2 wherever it applies, 0 never
     int g8 = 1;             // persistent eight-phase GEMM for long Linears (0: the tap_gemm block shapes)
     int g8_conv = 1;        // ... its tap-gather mode for 3x3 convs onto >= 1024 channels
     int g8_temporal = 1;    // ... and for Conv1d k3 over T at >= 640 channels

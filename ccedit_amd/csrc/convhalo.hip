@@ -257,20 +257,41 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_halo_kernel(const CcGemmDesc
 //   W half-tile rows are 64 bytes: granule g of row r sits at slot g ^ ((r >> 2) & 3) — the 16 lanes of a ds_read_b128 group hold
 //   rows {0-3, 12-15, 20-27} (+ k): every residue r % 4 four times with four different (r >> 2) & 3, i.e. 16 distinct 16-byte bank
 //   groups (MI355X_MICROARCH.md, LDS); the DMA writes a wave's 1 KB = rows 16 w .. 16 w + 15 lane-linearly.
-constexpr int kHaloBytes4 = 192 * 128;         // whole 32-row DMA issues: every wave issues exactly kHaloIssues loads (exact counted waits)
+//
+// The WIDE tile (TJ = 4: 256 pixels = 16 x 16, each wave 64 channels x 128 pixels; block shape 15, policy conv_wide): the K loop above is
+// bound by the bytes it stages (21.6 B/clk per CU against ~23 B/clk the L2 -> LDS path sustains, 86 % of them weights), so a
+// weight half tile here serves twice the pixels.  Same four 8 KB weight slots, same k-step order per accumulator (chunk, tap, half, k2: the
+// output bits are those of the 128-pixel tile); the halo rectangle is 18 x 18 = 324 rows in 11 whole issues = 45,056 B and there is ONE
+// buffer of it (32 KB + 44 KB = 77,824 B: two workgroups per CU as before).  The next chunk's rectangle is therefore requested after the
+// barrier of the chunk's last phase and waited for in front of the next chunk's first phase — it is older than that phase's weight request,
+// so the wait is counted (the weight half tile stays in flight) — and what covers its latency is the partner workgroup.  Halo offsets are
+// 32-bit, relative to the frame, and recomputed at every chunk boundary (128 accumulators + 48 fragment registers leave no room for 11
+// register pairs across the K loop: 238 registers, no scratch, two waves per SIMD).  An XCD takes an eighth of the workgroups, not of the
+// pixel tiles (see the block order below).  Measured, same process, cold operands (tools/exp/conv_wide_ab.py, profiles/conv_wide_ab.txt):
+// 34 x 64 x 96 320 -> 320 406.5 -> 372.8 us, 960 -> 320 1156 -> 1029, 34 x 32 x 48 640 -> 640 361.8 -> 327.3, 1920 -> 640 1027 -> 920: -8 ... -11 %
+// with 15 chunks no worse than with 5 (the chunk boundary is not what is left), 17 x 32 x 48 -30 % (one round instead of two),
+// 17 x 64 x 96 +2 % (three rounds of 512 slots against five half-size ones): cc_conv_wide_auto.
+constexpr int halo4_rows(int bnp) { return (bnp / 16 + 2) * 18; }                    // (TH + 2) x (TW + 2): 180 for 8 x 16 and 16 x 8, 324 for 16 x 16
+constexpr int halo4_issues(int bnp) { return (halo4_rows(bnp) + 31) / 32; }          // whole 32-row DMA issues: every wave issues exactly that many loads (exact counted waits)
+constexpr int halo4_bytes(int bnp) { return halo4_issues(bnp) * 32 * 128; }
+constexpr int halo4_bufs(int bnp) { return bnp == 128 ? 2 : 1; }
+constexpr int halo4_lds_main(int bmc, int bnp) { return 4 * bmc * 64 + halo4_bufs(bnp) * halo4_bytes(bnp); }
 
-template <int WM, int WN, int TI, int TJ>
-__global__ __launch_bounds__(WM* WN * 64) void conv_halo4_kernel(const CcGemmDesc d, int tw_log2_flags) {
-    const int tw_log2 = tw_log2_flags & 0xFF;
+template <int WM, int WN, int TI, int TJ>       // (two waves per SIMD: the wide tile's 128 accumulators + everything else within 256 registers)
+__global__ __launch_bounds__(WM* WN * 64, TJ == 4 ? 2 : 1) void conv_halo4_kernel(const CcGemmDesc d, int tw_log2_flags) {
     constexpr int NT = WM * WN * 64;
     constexpr int BMC = WM * TI * 32, BNP = WN * TJ * 32;
-    static_assert(NT == 256 && BNP == 128 && BMC == 128 && TI == 2, "tile geometry");
+    static_assert(NT == 256 && (BNP == 128 || BNP == 256) && BMC == 128 && TI == 2, "tile geometry");
+    constexpr bool WIDE = BNP == 256;              // 16 x 16 pixels only: the halo pitch and a lane's tile column are compile-time constants
+    const int tw_log2 = WIDE ? 4 : tw_log2_flags & 0xFF;
     constexpr int NS = 4;                          // weight ring slots
     constexpr int W_SUB = BMC * 64;                // 8 KB: 128 rows x 32 k
-    constexpr int LDS_MAIN = NS * W_SUB + 2 * kHaloBytes4;
+    constexpr int kRows = halo4_rows(BNP), kIssues = halo4_issues(BNP), kBytes = halo4_bytes(BNP), NH = halo4_bufs(BNP);
+    constexpr int LDS_MAIN = halo4_lds_main(BMC, BNP);
+    static_assert(LDS_MAIN <= 80 * 1024, "two workgroups per CU");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const sW = smem;                         // [NS][W_SUB]
-    char* const sH = smem + NS * W_SUB;            // [2][kHaloBytes4]
+    char* const sH = smem + NS * W_SUB;            // [NH][kBytes]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -282,17 +303,22 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_halo4_kernel(const CcGemmDes
 
     const int ct_n = (d.N + BMC - 1) / BMC;
     const int64_t pt_n = (int64_t)(d.M / (d.Hout * d.Wout)) * tpf;
-    const int64_t pt_per_xcd = (pt_n + 7) / 8;
+    // WIDE: the same walk (channel-tile groups outermost, pixel tiles, the group's channel tiles innermost), but an XCD takes an eighth of the
+    // WORKGROUPS of that walk instead of an eighth of the pixel tiles: 34 x 32 x 48 onto 640 channels is 204 tiles x 5 = 1020 workgroups for
+    // 512 slots — 26 tiles x 5 = 130 on 64 slots per XCD was a third round for two workgroups, 128 + 127 is two rounds
+    const int64_t pt_per_xcd = WIDE ? pt_n : (pt_n + 7) / 8;
     const int64_t bid = blockIdx.x;
     const int xcd = (int)(bid & 7);
-    const int64_t local = bid >> 3;
+    const int64_t wg_per_xcd = (pt_n * ct_n + 7) / 8;
+    const int64_t local = WIDE ? xcd * wg_per_xcd + (bid >> 3) : bid >> 3;
+    if (WIDE && local >= pt_n * ct_n) return;
     const int Q = d.cgroup > 0 ? d.cgroup : ct_n;
     const int64_t gsz = pt_per_xcd * Q;
     const int cg = (int)(local / gsz);
     const int64_t rr = local - cg * gsz;
     const int qn = min(Q, ct_n - cg * Q);
     const int64_t pl = rr / qn;
-    const int64_t pt = xcd * pt_per_xcd + pl;
+    const int64_t pt = WIDE ? pl : xcd * pt_per_xcd + pl;
     if (pt >= pt_n) return;
     const int ch0 = (cg * Q + (int)(rr - pl * qn)) * BMC;
     const int frame = (int)(pt / tpf);
@@ -308,15 +334,21 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_halo4_kernel(const CcGemmDes
     // ---- staging coordinates ----
     const int f_hy = (tw_log2 == 3) ? 1 : 0;
     const int p = tid & 7, rsub = tid >> 3;        // halo: 8 granules per 128-byte row
-    int64_t hoff[kHaloIssues];                     // halo issue i stages rows i * 32 + rsub: element offset without the chunk, or -1 (zero page)
-#pragma unroll
-    for (int i = 0; i < kHaloIssues; ++i) {
-        const int hrow = i * 32 + rsub;
+    // halo issue i stages rows i * 32 + rsub: the source of row `hrow`, without the chunk, as an element offset (int64 from d.A; WIDE: int from the
+    // frame's first element — the launcher checks that a frame has fewer than 2^31), or -1 for the zero page (outside the image; rows past kRows)
+    const bf16* const Ah = WIDE ? Ap + (int64_t)frame * d.Hin * d.Win * d.lda : Ap;
+    auto halo_src = [&](int hrow) -> int64_t {
         const int hy = hrow / HW_, hx = hrow - hy * HW_;
         const int iy = y0 + hy - 1, ix = x0 + hx - 1;
-        const bool v = hrow < kHaloRows && (unsigned)iy < (unsigned)d.Hin && (unsigned)ix < (unsigned)d.Win;
+        const bool v = hrow < kRows && (unsigned)iy < (unsigned)d.Hin && (unsigned)ix < (unsigned)d.Win;
         const int gsrc = p ^ (((hx >> 1) + ((hy & 1) << 2) * f_hy) & 7);
-        hoff[i] = v ? (((int64_t)frame * d.Hin + iy) * d.Win + ix) * d.lda + gsrc * 8 : -1;      // rows 180 .. 191: zero page (never read)
+        if constexpr (WIDE) return v ? (iy * d.Win + ix) * d.lda + gsrc * 8 : -1;
+        else return v ? (((int64_t)frame * d.Hin + iy) * d.Win + ix) * d.lda + gsrc * 8 : -1;
+    };
+    int64_t hoff[WIDE ? 1 : kIssues];              // WIDE recomputes them per chunk: 128 accumulators + 48 fragment registers leave no room for 11 pairs
+    if constexpr (!WIDE) {
+#pragma unroll
+        for (int i = 0; i < kIssues; ++i) hoff[i] = halo_src(i * 32 + rsub);
     }
     const int p4 = tid & 3, r4 = tid >> 2;         // weights: 4 granules per 64-byte row, rows r4 and r4 + 64
     const int gsrc_w = p4 ^ ((r4 >> 2) & 3);
@@ -324,10 +356,13 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_halo4_kernel(const CcGemmDes
     const size_t wsrc64 = (size_t)64 * d.Kpad;
 
     auto stageH = [&](int c, int buf) {
+        int r = rsub;
+        if constexpr (WIDE) asm volatile("" : "+v"(r));      // opaque per chunk: keeps the offsets from being hoisted out of the K loop
 #pragma unroll
-        for (int i = 0; i < kHaloIssues; ++i) {
-            const bf16* src = hoff[i] >= 0 ? Ap + hoff[i] + c * 64 : zp;
-            glds16(src, sH + buf * kHaloBytes4 + i * (32 * 128) + wave * 1024);
+        for (int i = 0; i < kIssues; ++i) {
+            const int64_t off = WIDE ? halo_src(i * 32 + r) : hoff[i];
+            const bf16* src = off >= 0 ? Ah + off + c * 64 : zp;
+            glds16(src, sH + buf * kBytes + i * (32 * 128) + wave * 1024);
         }
     };
 
@@ -367,9 +402,9 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_halo4_kernel(const CcGemmDes
         };
         auto wait_for = [&](int w_tiles, bool halo) {          // at most (w_tiles weight half tiles [+ the halo rectangle]) still in flight
             if (halo) {
-                if (w_tiles >= 2) wait_vmcnt_h<2 * WI + kHaloIssues>();
-                else if (w_tiles == 1) wait_vmcnt_h<WI + kHaloIssues>();
-                else wait_vmcnt_h<kHaloIssues>();
+                if (w_tiles >= 2) wait_vmcnt_h<2 * WI + kIssues>();
+                else if (w_tiles == 1) wait_vmcnt_h<WI + kIssues>();
+                else wait_vmcnt_h<kIssues>();
             } else {
                 if (w_tiles >= 2) wait_vmcnt_h<2 * WI>();
                 else if (w_tiles == 1) wait_vmcnt_h<WI>();
@@ -379,7 +414,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_halo4_kernel(const CcGemmDes
         // one phase = one weight half tile (two k-steps of 16) against the halo rows of tap (dy, dx)
         auto phase = [&](int sidx, int hbuf, int half, const int (&hr)[TJ], const int (&hsw)[TJ]) {
             const char* pa = fa + (sidx & (NS - 1)) * W_SUB;
-            const char* ph = sH + hbuf * kHaloBytes4;
+            const char* ph = sH + hbuf * kBytes;
             bf16x8 af[2][NTI], bfr[2][TJ];
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
@@ -423,13 +458,23 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_halo4_kernel(const CcGemmDes
                 for (int half = 0; half < 2; ++half, ++sidx) {
                     if (sidx + 3 < nsub) stageW(sidx + 3);
                     const bool first = (t == 0 && half == 0);
-                    if (first && more_chunks) stageH(c + 1, (c + 1) & 1);       // AFTER the weight request: the youngest loads of the queue
-                    phase(sidx, c & 1, half, hr, hsw);
+                    if constexpr (NH == 2) {
+                        if (first && more_chunks) stageH(c + 1, (c + 1) & 1);   // AFTER the weight request: the youngest loads of the queue
+                    } else if (first && c > 0) {
+                        // one halo buffer: this chunk's rectangle was requested after the previous phase's barrier, BEFORE the weight request
+                        // above (which a later chunk's first phase always makes: 18 phases follow) — all but that request must have landed
+                        wait_vmcnt_h<WI>();
+                        __syncthreads();
+                    }
+                    phase(sidx, NH == 2 ? c & 1 : 0, half, hr, hsw);
                     // half tile sidx + 1 must have landed; sidx + 2, sidx + 3 may stay in flight, and so may the next chunk's halo while
                     // it is younger than the half tile waited for (the three phases after it was requested)
                     const int left = nsub - 2 - sidx;                               // half tiles beyond sidx + 1
-                    wait_for(left < 0 ? 0 : left, more_chunks && t == 0 || (more_chunks && t == 1 && half == 0));
+                    wait_for(left < 0 ? 0 : left, NH == 2 && (more_chunks && t == 0 || (more_chunks && t == 1 && half == 0)));
                     __syncthreads();
+                    if constexpr (NH == 1) {
+                        if (t == 8 && half == 1 && more_chunks) stageH(c + 1, 0);   // every wave is past its last read of the rectangle
+                    }
                 }
             }
         }
@@ -475,7 +520,63 @@ bool cc_conv_halo_applicable(const CcGemmDesc& d) {
     return d.Hout % 8 == 0 || (d.Wout % 8 == 0 && d.Hout % 16 == 0);
 }
 
-int cc_conv_halo_launch(const CcGemmDesc& d, hipStream_t s) {
+// The 256-pixel tile of conv_halo4_kernel: whole 16 x 16 rectangles vertically (a ragged last column is masked), halo offsets in 32 bits
+bool cc_conv_wide_applicable(const CcGemmDesc& d) {
+    return cc_conv_halo_applicable(d) && d.Hout % 16 == 0 && (int64_t)d.Hin * d.Win * d.lda < (1LL << 31);
+}
+
+// conv_wide = 1: where the per-shape A/B measured the wide tile faster (profiles/conv_wide_ab.txt).  A wide workgroup takes
+// 1.82 times a 128-pixel one (ratios 0.89 ... 0.92 at equal slot fill), and what decides a launch is how the two workgroup counts quantise
+// on the chip's slots (two workgroups per CU): whole rounds of each, priced at 182 : 100.  34 x 64 x 96 onto 320: 5 rounds against 10 (wide),
+// 34 x 32 x 48 onto 640: 2 against 4 (wide), 17 x 32 x 48: 1 against 2 (wide, measured 0.70), 17 x 64 x 96 onto 320: 3 against 5 (stays:
+// measured 1.02); anything that fits one round of 128-pixel tiles stays (every launch below 16384 pixels does, and is excluded outright).
+bool cc_conv_wide_auto(const CcGemmDesc& d) {
+    if (d.M < 16384) return false;
+    int cus = 256;
+    {
+        int dev = 0;
+        static int cu_cache[64] = {0};
+        if (hipGetDevice(&dev) == hipSuccess && dev < 64) {
+            if (!cu_cache[dev]) {
+                int v = 0;
+                if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cu_cache[dev] = v;
+            }
+            if (cu_cache[dev]) cus = cu_cache[dev];
+        }
+    }
+    const int64_t slots = 2 * (int64_t)cus;
+    const int64_t wide = d.M / ((int64_t)d.Hout * d.Wout) * ((d.Wout + 15) / 16) * (d.Hout / 16) * ((d.N + 127) / 128);
+    const int64_t rounds_wide = (wide + slots - 1) / slots, rounds_128 = (2 * wide + slots - 1) / slots;
+    return 182 * rounds_wide < 100 * rounds_128;
+}
+
+static int conv_wide_launch(const CcGemmDesc& d, hipStream_t s) {
+    constexpr int WM = 2, WN = 2, TI = 2, TJ = 4;
+    constexpr int BMC = WM * TI * 32, BNP = WN * TJ * 32;
+    constexpr int lds = epi_lds_total(BMC, BNP, TJ, halo4_lds_main(BMC, BNP));
+    static_assert(lds <= 80 * 1024, "two workgroups per CU");
+    const int64_t frames = d.M / ((int64_t)d.Hout * d.Wout);
+    const int64_t pt_n = frames * ((d.Wout + 15) / 16) * (d.Hout / 16), ct_n = (d.N + BMC - 1) / BMC;
+    const int64_t nblk = 8 * ((pt_n * ct_n + 7) / 8);     // an eighth of the workgroups per XCD (see the kernel's block order)
+    if (nblk > 2147483647LL) {
+        cc_set_error("ccedit_gemm: grid too large");
+        return CCEDIT_EUNSUPPORTED;
+    }
+    CcGemmDesc dd = d;
+    dd.cgroup = 0;                                // channel tiles in groups of at most three, as cc_conv_halo_launch
+    if (ct_n > 3) {
+        const int ng = (int)((ct_n + 2) / 3);
+        dd.cgroup = (int)((ct_n + ng - 1) / ng);
+    }
+    static unsigned long long attr_done = 0;
+    if (int rc = cc_max_dynamic_lds((const void*)conv_halo4_kernel<WM, WN, TI, TJ>, lds, &attr_done, "conv_halo4 wide")) return rc;
+    cc_note_kernel("conv_halo_kernel, four-slot weight ring, 256-pixel tile");
+    hipLaunchKernelGGL((conv_halo4_kernel<WM, WN, TI, TJ>), dim3((unsigned)nblk), dim3(WM * WN * 64), lds, s, dd, 4 | (1 << 8));
+    return cc_launch_status("conv_halo4_kernel");
+}
+
+int cc_conv_halo_launch(const CcGemmDesc& d, hipStream_t s, bool wide) {
+    if (wide) return conv_wide_launch(d, s);
     constexpr int WM = 2, WN = 2, TI = 2, TJ = 2;
     constexpr int BMC = WM * TI * 32, BNP = WN * TJ * 32;
     constexpr int lds = epi_lds_total(BMC, BNP, TJ, 2 * BMC * 128 + 2 * kHaloBytes);
@@ -501,7 +602,7 @@ int cc_conv_halo_launch(const CcGemmDesc& d, hipStream_t s) {
         dd.cgroup = (int)((ct_n + ng - 1) / ng);
     }
     if (cc_policy().conv_halo != 2) {            // the four-slot weight ring (round 6; policy conv_halo = 2: the two-slot kernel of rounds 2-5, the A/B arm)
-        constexpr int lds4 = epi_lds_total(BMC, BNP, TJ, 4 * BMC * 64 + 2 * kHaloBytes4);
+        constexpr int lds4 = epi_lds_total(BMC, BNP, TJ, halo4_lds_main(BMC, BNP));
         static unsigned long long attr_done4 = 0;
         if (int rc = cc_max_dynamic_lds((const void*)conv_halo4_kernel<WM, WN, TI, TJ>, lds4, &attr_done4, "conv_halo4")) return rc;
         cc_note_kernel("conv_halo_kernel, four-slot weight ring");

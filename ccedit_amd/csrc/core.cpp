@@ -60,7 +60,7 @@ struct PolicyEntry {
     int CcPolicy::*field;
 };
 const PolicyEntry kPolicy[] = {
-    {"conv_halo", &CcPolicy::conv_halo},     {"g8", &CcPolicy::g8},           {"g8_conv", &CcPolicy::g8_conv},
+    {"conv_halo", &CcPolicy::conv_halo},     {"conv_wide", &CcPolicy::conv_wide},     {"g8", &CcPolicy::g8},           {"g8_conv", &CcPolicy::g8_conv},
     {"g8_temporal", &CcPolicy::g8_temporal}, {"g8_split", &CcPolicy::g8_split}, {"g8_mfma16", &CcPolicy::g8_mfma16}, {"lin320", &CcPolicy::lin320},
     {"lin320s", &CcPolicy::lin320s},         {"lin640", &CcPolicy::lin640},   {"temp320", &CcPolicy::temp320},
     {"attn_short", &CcPolicy::attn_short},   {"attn_text", &CcPolicy::attn_text}, {"attn_spatial", &CcPolicy::attn_spatial},

@@ -34,7 +34,9 @@
 #include <stdlib.h>
 
 bool cc_conv_halo_applicable(const CcGemmDesc& d);        // convhalo.hip
-int cc_conv_halo_launch(const CcGemmDesc& d, hipStream_t s);
+bool cc_conv_wide_applicable(const CcGemmDesc& d);        // ... its 256-pixel tile (block shape 15, policy conv_wide)
+bool cc_conv_wide_auto(const CcGemmDesc& d);
+int cc_conv_halo_launch(const CcGemmDesc& d, hipStream_t s, bool wide);
 bool cc_lin320_applicable(const CcGemmDesc& d);           // lin320.hip
 int cc_lin320_launch(const CcGemmDesc& d, hipStream_t s);
 bool cc_lin640_applicable(const CcGemmDesc& d);           // lin640.hip
@@ -492,7 +494,7 @@ extern "C" int ccedit_gemm(const CcGemmDesc* desc, void* stream) {
     if (d.gn_stats && !(d.tile >= 11 && d.tile <= 13)) {      // (the persistent Linear shapes refuse gn_stats themselves)
         CC_CHECK_ARG(d.gn_rows > 0 && d.gn_rows % 128 == 0 && d.M % d.gn_rows == 0,
                      "ccedit_gemm: gn_stats needs gn_rows %% 128 == 0 dividing M (gn_rows=%d)", d.gn_rows);
-        CC_CHECK_ARG(d.gn_rows % 256 == 0 || d.tile <= 1 || d.tile == 8 || d.tile == 14,
+        CC_CHECK_ARG(d.gn_rows % 256 == 0 || d.tile <= 1 || d.tile == 8 || d.tile == 14 || d.tile == 15,
                      "ccedit_gemm: gn_rows=%d is not a multiple of 256: only the 128-pixel block shape (tile 1) applies", d.gn_rows);
         CC_UNSUPPORTED(d.tile == 6, "ccedit_gemm: gn_stats is not available with the 320-channel block shape (tile 6)");
         CC_UNSUPPORTED(d.N % 32 != 0 || d.N < 256 || d.out_f32 || d.act == CCEDIT_ACT_GEGLU,
@@ -553,8 +555,18 @@ extern "C" int ccedit_gemm(const CcGemmDesc* desc, void* stream) {
     // 2 x 2 window (round 6).  16x24 -> 32x48 (13056 source pixels x 1280 channels, K = 5120: 255 tiles, one round of the chip) is taken
     // by the clause above, the 8x12 source by split-K; this one takes the 32x48 source (640 channels: 128ch x 512pix).
     if (d.tile == 0 && pol.g8_conv && pol.g8 && d.subpix && d.M >= 12000 && d.N >= 640 && cc_g8_applicable(d, 0)) return cc_g8_launch(d, s, 0);
+    // ... on 16 x 16-pixel tiles (a weight half tile staged serves twice the pixels): block shape 15; policy conv_wide = 1 where it measured
+    // faster (cc_conv_wide_auto), 2 wherever it applies, 0 never.  Same bits as the 128-pixel tile.
+    if (d.tile == 15) {
+        CC_UNSUPPORTED(d.vpad || !cc_conv_wide_applicable(d), "ccedit_gemm: tile 15 (LDS-halo 3x3 conv, 256-pixel tile: stride 1, Cin %% 64 == 0, "
+                       "Hout %% 16 == 0, fewer than 2^31 elements per source frame) does not apply to this descriptor");
+        return cc_conv_halo_launch(d, s, true);
+    }
     if ((d.tile == 0 && pol.conv_halo && !d.vpad) || d.tile == 8) {
-        if (!d.vpad && cc_conv_halo_applicable(d)) return cc_conv_halo_launch(d, s);
+        if (!d.vpad && cc_conv_halo_applicable(d)) {
+            const bool wide = d.tile == 0 && pol.conv_halo == 1 && pol.conv_wide && cc_conv_wide_applicable(d) && (pol.conv_wide == 2 || cc_conv_wide_auto(d));
+            return cc_conv_halo_launch(d, s, wide);
+        }
         CC_UNSUPPORTED(d.tile == 8, "ccedit_gemm: tile 8 (LDS-halo 3x3 conv) does not apply to this descriptor");
     }
     // K = 320 Linear over many pixels: weights resident in registers, activations streamed once (lin320.hip)

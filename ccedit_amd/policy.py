@@ -42,6 +42,7 @@ TABLE = {
                           "1: always fp32, also for a first stage built outside an engine; 0: always the bf16-storage kernels"),
     # ---- kernel library (csrc/common.h: CcPolicy) ----
     "conv_halo": (1, "lib", "0: 3x3 stride-1 convs on the tap-gather kernel; 2: the LDS-halo kernel with the two-slot weight ring of rounds 2-5"),
+    "conv_wide": (1, "lib", "0: the LDS-halo kernel on 128-pixel tiles everywhere; 2: on 256-pixel (16 x 16) tiles wherever they apply, not only where they measured faster"),
     "g8": (1, "lib", "0: long Linears on the tap_gemm block shapes"),
     "g8_conv": (1, "lib", "0: 3x3 convs onto >= 1024 channels not on the persistent kernel"),
     "g8_temporal": (1, "lib", "0: Conv1d k3 at >= 640 channels not on the persistent kernel"),

@@ -39,7 +39,7 @@ int ccedit_abi_version(void);
 const char* ccedit_last_error(void);
 /* name of the kernel template the last ccedit_gemm / ccedit_ff320 / ccedit_attention call of this thread dispatched to
  * ("g8_kernel 256x256", "conv_halo_kernel, four-slot weight ring" / "conv_halo_kernel, two-slot weight ring" by policy conv_halo,
- * "tap_gemm_kernel 128x128 s2", ...): bench.py's per-kernel roofline table */
+ * "conv_halo_kernel, four-slot weight ring, 256-pixel tile" by policy conv_wide, "tap_gemm_kernel 128x128 s2", ...): bench.py's per-kernel roofline table */
 const char* ccedit_last_kernel(void);
 /* fills name with hipDeviceProp_t.gcnArchName of the current device; returns CU count or <0 */
 int ccedit_device_info(char* name, int name_len);
@@ -47,7 +47,7 @@ int ccedit_device_info(char* name, int name_len);
 /* Dispatch policy: ONE table of named integer switches that choose between kernels computing the same fp32 sums in a different order
  * (A/B arms and the "specialised kernels reproduce the generic ones" tests).  All default to the fast path.  The library never reads
  * the environment; the host sets entries before launching (process-wide, not thread-safe against concurrent launches).  Names:
- *   conv_halo g8 g8_conv g8_temporal g8_split g8_mfma16 lin320 lin320s lin640 temp320 attn_short attn_text attn_spatial attn_pv16 attn_opt gn_flat
+ *   conv_halo conv_wide g8 g8_conv g8_temporal g8_split g8_mfma16 lin320 lin320s lin640 temp320 attn_short attn_text attn_spatial attn_pv16 attn_opt gn_flat
  *   gn_apply_flat f32_split
  *   (ccedit_policy_names() returns them comma-separated; semantics in csrc/common.h: CcPolicy)
  * Unknown name: CCEDIT_EINVAL. */
@@ -103,7 +103,9 @@ typedef struct CcGemmDesc {
                            * 10 = the same at K = 640 (Linear, N % 128 == 0, M % 16 == 0; bias, one residual, row_sums, ln_stats / ln_sums),
                            * 11-13 = persistent eight-phase GEMM (block shape by Cout / 256ch x 256pix / 128ch x 512pix),
                            * 14 = streaming Conv1d k3 over T with 320 input channels (TEMPORAL, N % 64 == 0, HW % 16 == 0, unsharded frames;
-                           *      bias, per-clip row bias, up to two residuals, gn_stats) */
+                           *      bias, per-clip row bias, up to two residuals, gn_stats),
+                           * 15 = LDS-halo 3x3 conv on 256-pixel (16 x 16) tiles (as 8, and Hout % 16 == 0, a source frame below 2^31 elements;
+                           *      gn_rows need not be a multiple of 256) */
     int32_t korder;       /* weight K order: 0 = [tap][Cin]; 1 = [Cin/64][tap][64] (needs Cin % 64 == 0) */
     int32_t gn_rows;      /* with gn_stats: output rows per frame (H*W), a multiple of 128 dividing M (not a
                            * multiple of 256: block shape 1 is used); else 0 */
