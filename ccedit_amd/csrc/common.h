@@ -179,6 +179,14 @@ int cc_mask_inpaint_blend(const float* x, const float* x0, const float* noise, c
                           float sigma, float s, hipStream_t st);
 int cc_mask_composite(const float* result, const float* original, const uint8_t* mask_px, float* out, int32_t B, int64_t P, hipStream_t st);
 int cc_mask_dilate(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int64_t N, int32_t H, int32_t W, int32_t R, int32_t invert, hipStream_t s);
+int cc_mask_inpaint_blend_level(const float* x, const float* x0, const float* noise, const uint8_t* strength, float* y, int32_t B, int32_t C,
+                                int64_t P, int32_t thr, float sigma, float s, hipStream_t st);
+
+// Graded edit-mask launchers (softmask.hip); entry points and argument checks in core.cpp
+int cc_mask_feather(const uint8_t* src, uint16_t* tmp16, uint8_t* dst, int64_t N, int32_t H, int32_t W, int32_t R, hipStream_t s);
+int cc_mask_latent_graded(const uint8_t* mask_px, uint8_t* strength_lat, int64_t N, int32_t H, int32_t W, hipStream_t s);
+int cc_mask_composite_graded(const float* result, const float* original, const uint8_t* strength_px, float* out, int32_t B, int64_t P,
+                             hipStream_t st);
 
 // Window launchers (window.hip); entry points and argument checks in core.cpp
 int cc_window_gather(const float* x, float* xw, const int32_t* starts, int32_t W, int32_t BC, int32_t N, int32_t T, int64_t P, hipStream_t s);

@@ -205,6 +205,46 @@ extern "C" int ccedit_mask_dilate(const void* src, void* tmp, void* dst, int64_t
     return cc_mask_dilate((const uint8_t*)src, (uint8_t*)tmp, (uint8_t*)dst, N, H, W, radius, invert, (hipStream_t)stream);
 }
 
+// ---- graded edit masks (kernels and launchers: softmask.hip; the level re-injection: mask.hip).  Everything is checked here, before any
+// HIP call.
+extern "C" int ccedit_mask_feather(const void* src, void* tmp16, void* dst, int64_t N, int32_t H, int32_t W, int32_t radius, void* stream) {
+    CC_CHECK_ARG(src && tmp16 && dst, "ccedit_mask_feather: null pointer");
+    CC_CHECK_ARG(N > 0 && H > 0 && W > 0 && W % 4 == 0, "ccedit_mask_feather: N=%lld maps of %dx%d (positive, W a multiple of 4)", (long long)N, H, W);
+    CC_CHECK_ARG(N < kPixelMax && N * H * W < kPixelMax * 4, "ccedit_mask_feather: more than 2^33 pixels in one call");
+    CC_CHECK_ARG(radius >= 0 && radius <= 64, "ccedit_mask_feather: radius=%d (0 ... 64)", radius);
+    CC_CHECK_ARG((((uintptr_t)src | (uintptr_t)tmp16 | (uintptr_t)dst) & 3) == 0, "ccedit_mask_feather: src, tmp16 and dst must be 4-byte aligned");
+    CC_CHECK_ARG(src != dst && tmp16 != dst && src != tmp16, "ccedit_mask_feather: src, tmp16 and dst must be different buffers");
+    return cc_mask_feather((const uint8_t*)src, (uint16_t*)tmp16, (uint8_t*)dst, N, H, W, radius, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_mask_latent_graded(const void* mask_px, void* strength_lat, int64_t N, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(mask_px && strength_lat, "ccedit_mask_latent_graded: null pointer");
+    CC_CHECK_ARG(N > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0,
+                 "ccedit_mask_latent_graded: N=%lld frames of %dx%d (positive, H and W multiples of 8)", (long long)N, H, W);
+    CC_CHECK_ARG(N < kPixelMax && N * H * W < kPixelMax * 4, "ccedit_mask_latent_graded: more than 2^33 pixels in one call");
+    CC_CHECK_ARG(((uintptr_t)mask_px & 7) == 0,
+                 "ccedit_mask_latent_graded: the strength map must be 8-byte aligned (a row of a cell is one 8-byte load)");
+    return cc_mask_latent_graded((const uint8_t*)mask_px, (uint8_t*)strength_lat, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_mask_composite_graded(const float* result, const float* original, const void* strength_px, float* out, int32_t B, int64_t P,
+                                            void* stream) {
+    CC_CHECK_ARG(result && original && strength_px && out, "ccedit_mask_composite_graded: null pointer");
+    CC_CHECK_ARG(B > 0 && P > 0 && P < kPixelMax * 4 && (int64_t)B * 3 * P < kPixelMax * 4,
+                 "ccedit_mask_composite_graded: B=%d P=%lld (positive, at most 2^33 elements)", B, (long long)P);
+    return cc_mask_composite_graded(result, original, (const uint8_t*)strength_px, out, B, P, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_inpaint_blend_level(const float* x, const float* x0, const float* noise, const void* strength, float* y, int32_t B, int32_t C,
+                                          int64_t P, int32_t thr, float sigma, float s, void* stream) {
+    CC_CHECK_ARG(x && x0 && noise && strength && y, "ccedit_inpaint_blend_level: null pointer");
+    CC_CHECK_ARG(B > 0 && C > 0 && P > 0 && P < kPixelMax * 4 && (int64_t)B * C * P < kPixelMax * 4,
+                 "ccedit_inpaint_blend_level: B=%d C=%d P=%lld (positive, at most 2^33 elements)", B, C, (long long)P);
+    CC_CHECK_ARG(thr >= 1 && thr <= 255, "ccedit_inpaint_blend_level: thr=%d (1 ... 255: strength 0 is never free, strength 255 always)", thr);
+    CC_CHECK_ARG(s > 0.0f, "ccedit_inpaint_blend_level: s=%g must be positive (s = sqrt(1 + sigma^2))", (double)s);
+    return cc_mask_inpaint_blend_level(x, x0, noise, (const uint8_t*)strength, y, B, C, P, thr, sigma, s, (hipStream_t)stream);
+}
+
 // ---- windows of a long clip (kernels and launchers: window.hip).  Everything the host can see is checked here, before any HIP call;
 // the device tables (starts, coef, the pointer table) are held inside their tensors by the kernels themselves.
 static int window_shape_ok(const char* fn, int32_t W, int32_t B, int32_t C, int32_t N, int32_t T, int64_t P) {

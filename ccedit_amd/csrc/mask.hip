@@ -2,6 +2,7 @@
 //   mask_resize_nearest   uint8 mask -> the clip's size by two index tables (Pillow's NEAREST), a gather
 //   mask_latent           pixel mask -> latent mask: an 8 x 8 cell is 1 when MORE than 32 of its pixels are set
 //   inpaint_blend         the per-step re-injection y = m ? x : (x0 + noise * sigma) / s, mask broadcast over the channels
+//   inpaint_blend_level   the same kernel with the caller's threshold on the byte: the re-injection of a graded run (softmask.hip)
 //   mask_composite        out = m ? result : original on the decoded frames
 //   mask_dilate           pixel mask -> its (2R + 1)^2 square maximum in two separable passes, optionally inverted (255 - m) on the way out
 // Convention everywhere: set (pixel masks: byte >= 128, latent masks: byte != 0) = edit, clear = keep the original.
@@ -243,6 +244,13 @@ int cc_mask_inpaint_blend(const float* x, const float* x0, const float* noise, c
                           float sigma, float s, hipStream_t st) {
     launch_select<true>(x, x0, noise, mask, y, B, C, P, 1u, sigma, s, st);
     return cc_launch_status("inpaint_blend");
+}
+
+// the re-injection of a graded run (softmask.hip): the same kernel, a cell is free where its strength byte is >= the step's threshold
+int cc_mask_inpaint_blend_level(const float* x, const float* x0, const float* noise, const uint8_t* strength, float* y, int32_t B, int32_t C,
+                                int64_t P, int32_t thr, float sigma, float s, hipStream_t st) {
+    launch_select<true>(x, x0, noise, strength, y, B, C, P, (uint32_t)thr, sigma, s, st);
+    return cc_launch_status("inpaint_blend_level");
 }
 
 int cc_mask_composite(const float* result, const float* original, const uint8_t* mask_px, float* out, int32_t B, int64_t P, hipStream_t st) {

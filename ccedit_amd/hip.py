@@ -184,6 +184,12 @@ _SIGS = {
     "ccedit_masktrack_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ccedit_masktrack_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ccedit_mask_dilate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    # graded edit masks (csrc/softmask.hip; the level re-injection: csrc/mask.hip): added within ABI 12, nothing existing changed
+    "ccedit_mask_feather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_mask_latent_graded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_mask_composite_graded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "ccedit_inpaint_blend_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                             C.c_float, C.c_float, C.c_void_p]),
     # Motion-JPEG output (csrc/mjpeg.hip): added within ABI 12, nothing existing changed
     "ccedit_mjpeg_segment_bytes": (C.c_int64, [C.c_int32]),
     "ccedit_mjpeg_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

@@ -1333,6 +1333,74 @@ def mask_dilate(mask: torch.Tensor, radius: int, invert: bool = False) -> torch.
 
 
 # ------------------------------------------------------------------------------------------
+# Graded edit masks (csrc/softmask.hip; thresholds and the flag check: ccedit_amd/softmask.py).  A strength map: uint8, byte g = g / 255
+# ------------------------------------------------------------------------------------------
+def mask_feather(mask: torch.Tensor, radius: int) -> torch.Tensor:
+    """uint8 maps (..., H, W) -> their mean over the (2 radius + 1)^2 square, the window clipped at the frame border, rounded half up
+    ((2 S + A) // (2 A) of the window's sum S and pixel count A).  Per map: nothing crosses frames.  radius 0 is the identity: the map
+    itself comes back and nothing is launched."""
+    if not 0 <= int(radius) <= 64:
+        raise ValueError(f"mask_feather: radius={radius} must be in 0 ... 64")
+    if int(radius) == 0:
+        return mask
+    _chk_u8(mask, "mask_feather", mask.dim())
+    assert mask.dim() >= 2 and mask.shape[-1] % 4 == 0, f"mask_feather: maps (..., H, W) with W a multiple of 4, got {tuple(mask.shape)}"
+    h, w = mask.shape[-2:]
+    out = torch.empty_like(mask)
+    tmp = torch.empty(mask.shape, dtype=torch.int16, device=mask.device)          # (the row sums, read as uint16)
+    hip.check(hip.lib().ccedit_mask_feather(mask.data_ptr(), tmp.data_ptr(), out.data_ptr(), mask.numel() // (h * w), h, w, int(radius), _stream()),
+              "ccedit_mask_feather")
+    return out
+
+
+def mask_latent_graded(mask_px: torch.Tensor) -> torch.Tensor:
+    """Pixel strengths uint8 (B, T, H, W) -> latent strengths uint8 (B, T, H / 8, W / 8): (sum of the cell's 64 bytes + 32) >> 6."""
+    assert mask_px.dtype == torch.uint8 and mask_px.is_cuda and mask_px.is_contiguous() and mask_px.dim() == 4
+    b, t, h, w = mask_px.shape
+    assert h % 8 == 0 and w % 8 == 0, f"strength map of {h}x{w}: H and W must be multiples of 8"
+    out = torch.empty((b, t, h // 8, w // 8), dtype=torch.uint8, device=mask_px.device)
+    hip.check(hip.lib().ccedit_mask_latent_graded(mask_px.data_ptr(), out.data_ptr(), b * t, h, w, _stream()), "ccedit_mask_latent_graded")
+    return out
+
+
+def inpaint_blend_level(x: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, strength: torch.Tensor, thr: int, sigma: float, s: float,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """inpaint_blend of a graded run: y = (strength >= thr) ? x : (x0 + noise * sigma) / s over fp32 (B, C, T, h, w) with the uint8 latent
+    strengths (B, T, h, w) broadcast over C; thr = softmask.threshold(j, n), 1 ... 255.  `out` may be `x`."""
+    if not 1 <= int(thr) <= 255:
+        raise ValueError(f"inpaint_blend_level: thr={thr} must be in 1 ... 255")
+    for tns in (x, x0, noise):
+        assert tns.dtype == torch.float32 and tns.is_cuda and tns.is_contiguous() and tns.shape == x.shape and tns.dim() == 5
+    b, c, t, h, w = x.shape
+    assert strength.dtype == torch.uint8 and strength.is_cuda and strength.is_contiguous() and tuple(strength.shape) == (b, t, h, w), \
+        f"latent strengths {tuple(strength.shape)} {strength.dtype} for a latent {tuple(x.shape)}: expected uint8 {(b, t, h, w)}"
+    y = torch.empty_like(x) if out is None else out
+    assert y.dtype == torch.float32 and y.is_contiguous() and y.shape == x.shape
+    n = x.numel()
+    _launch_mem("inpaint_blend_level", 16.0 * n + strength.numel(), lambda: hip.check(hip.lib().ccedit_inpaint_blend_level(
+        x.data_ptr(), x0.data_ptr(), noise.data_ptr(), strength.data_ptr(), y.data_ptr(), b, c, t * h * w, int(thr), float(sigma), float(s),
+        _stream()), "ccedit_inpaint_blend_level"), (b, c, t, h, w))
+    return y
+
+
+def mask_composite_graded(result: torch.Tensor, original: torch.Tensor, strength_px: torch.Tensor,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = g == 255 ? result : g == 0 ? original : original + (result - original) * (float(g) / 255) over fp32 frames (B, 3, T, H, W)
+    with the uint8 pixel strengths (B, T, H, W) broadcast over the channels, four fp32 roundings.  `out` may be `result`."""
+    for tns in (result, original):
+        assert tns.dtype == torch.float32 and tns.is_cuda and tns.is_contiguous() and tns.shape == result.shape and tns.dim() == 5
+    b, c, t, h, w = result.shape
+    assert c == 3 and strength_px.dtype == torch.uint8 and strength_px.is_cuda and strength_px.is_contiguous() \
+        and tuple(strength_px.shape) == (b, t, h, w), \
+        f"pixel strengths {tuple(strength_px.shape)} {strength_px.dtype} for frames {tuple(result.shape)}: expected uint8 {(b, t, h, w)}"
+    y = torch.empty_like(result) if out is None else out
+    assert y.dtype == torch.float32 and y.is_contiguous() and y.shape == result.shape
+    hip.check(hip.lib().ccedit_mask_composite_graded(result.data_ptr(), original.data_ptr(), strength_px.data_ptr(), y.data_ptr(), b, t * h * w,
+                                                     _stream()), "ccedit_mask_composite_graded")
+    return y
+
+
+# ------------------------------------------------------------------------------------------
 # Motion-JPEG output (csrc/mjpeg.hip; constants, header, container and the frame loop: ccedit_amd/mjpeg.py)
 # ------------------------------------------------------------------------------------------
 def mjpeg_segment_bytes(w: int) -> int:

@@ -676,6 +676,33 @@ int ccedit_masktrack_step(const void* v, const void* r, const void* mask_g, void
 int ccedit_mask_dilate(const void* src, void* tmp, void* dst, int64_t N, int32_t H, int32_t W, int32_t radius, int32_t invert, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Graded edit masks (added without an ABI bump: four new functions, CCEDIT_ABI_VERSION stays 12).  `--mask_graded`, `--mask_feather`:
+ * a STRENGTH MAP is a uint8 pixel map, byte g = edit strength g / 255 (255: what a white mask pixel is, 0: a black one).  Kernels:
+ * csrc/softmask.hip; the level re-injection is csrc/mask.hip's select kernel with the caller's threshold.  Feather and latent
+ * strengths are integer arithmetic, the composite is four fp32 roundings; all equal tests/_softmask_numpy.py bit for bit.
+ * Thresholds per step: ccedit_amd/softmask.py.  All pointers are device pointers.
+ *
+ * ccedit_mask_feather: uint8 maps [N][H][W] (W % 4 == 0, 4-byte aligned) -> dst: the mean over the (2 radius + 1)^2 square, the window
+ *   clipped at the frame border, rounded half up: with S the sum of the bytes of the clipped window and A its pixel count,
+ *   (2 S + A) / (2 A) in integers (radius 0 ... 64; 0 copies).  Two separable passes: row sums into tmp16, uint16 [N][H][W] (at most
+ *   129 * 255 = 32 895), column sums in uint32.  Per map: nothing crosses from one of the N maps to the next.  src, tmp16 and dst are
+ *   three different buffers.
+ * ccedit_mask_latent_graded: pixel strengths uint8 [N][H][W] (H % 8 == W % 8 == 0, 8-byte aligned) -> latent strengths uint8
+ *   [N][H/8][W/8]: (sum of the 64 bytes of the 8 x 8 cell + 32) >> 6; a white cell gives 255, a black one 0.
+ * ccedit_mask_composite_graded: out = g == 255 ? result : g == 0 ? original : original + (result - original) * (float(g) / 255.0f) over
+ *   fp32 [B][3][P] (P = T H W) with the strengths uint8 [B][P] broadcast over the three channels: one IEEE divide, one subtract, one
+ *   multiply, one add, not contracted.  For a 0 / 255 map bit-equal to ccedit_mask_composite.  out may alias result.
+ * ccedit_inpaint_blend_level: ccedit_inpaint_blend with m = (strength byte >= thr), thr 1 ... 255: y = m ? x : (x0 + noise * sigma) / s.
+ *   Before walked step j of n a graded run passes thr = (255 (n - j) + n - 1) / n: a cell of strength L is free iff L n >= 255 (n - j).
+ */
+int ccedit_mask_feather(const void* src, void* tmp16, void* dst, int64_t N, int32_t H, int32_t W, int32_t radius, void* stream);
+int ccedit_mask_latent_graded(const void* mask_px, void* strength_lat, int64_t N, int32_t H, int32_t W, void* stream);
+int ccedit_mask_composite_graded(const float* result, const float* original, const void* strength_px, float* out, int32_t B, int64_t P,
+                                 void* stream);
+int ccedit_inpaint_blend_level(const float* x, const float* x0, const float* noise, const void* strength, float* y, int32_t B, int32_t C,
+                               int64_t P, int32_t thr, float sigma, float s, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG (added without an ABI bump: five new functions, CCEDIT_ABI_VERSION stays 12).  `--save_type mjpeg`: uint8 frames
  * [N][H][W][3] on the device (what ccedit_frames_to_u8 writes) -> one baseline JPEG per frame (ITU-T T.81: sequential DCT, 8 bit,
  * YCbCr 4:2:0, MCU 16 x 16, restart interval = one MCU row = one SEGMENT), ccedit_amd/mjpeg.py: constants, header, container.

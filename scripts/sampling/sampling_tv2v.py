@@ -32,6 +32,12 @@ disagree — summed differences scaled by a quantile, thresholded, cleaned by a 
 csrc/automask.hip); it then goes where a painted mask goes (--mask_dilate, --mask_invert, --mask_composite, mask/).  --mask_auto_save DIR
 writes it as DIR/<video name>/%05d.png per source frame, which --mask_root DIR reads back; log_info.json gains `mask_auto`.  The quality
 of such masks on real footage has not been measured.
+`--mask_graded` reads the mask's grey levels as edit strengths g / 255 and `--mask_feather R` (0 ... 64 pixels, after --mask_dilate and
+--mask_invert) turns whatever mask the run has into such a map by a (2R + 1)^2 mean: a latent cell of strength s is held to the noised
+source for the first (1 - s) of the walked schedule and left alone afterwards, and --mask_composite mixes result and original in
+proportion to the pixel strengths (ccedit_amd/softmask.py, csrc/softmask.hip); mask/ then holds grey images and log_info.json gains
+`mask_graded` and `mask_feather`.  Refused: --mask_graded with --mask_track, a graded run with --propagate --mask_composite or with
+WORLD_SIZE > 1.  Image quality is not claimed.
 `--window_frames T` (with `--window_overlap O`, default T // 2) lifts the limit of one window of keyframes: with `--num_keyframes N` > T the
 clip is covered by overlapping windows of T frames, each evaluated by the unchanged network at every sampler evaluation and fused into
 one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everything else — inpainting, SDEdit, the prior mix,
@@ -167,6 +173,14 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
                    help="grow every mask (tracked or not) by this many pixels, 0 ... 32: a (2R + 1) x (2R + 1) square maximum, after tracking")
     p.add_argument("--mask_invert", action="store_true",
                    help="swap edit and keep (255 - mask), after tracking and --mask_dilate: with --mask_track, edit everything but the subject")
+    p.add_argument("--mask_graded", action="store_true",
+                   help="(not in the reference script) the mask's grey levels are edit STRENGTHS: luminance g edits with strength g / 255 "
+                        "(white = all the way, as before; mid grey = held to the source for the first half of the schedule, free afterwards; "
+                        "black = kept), no cut at 128 (ccedit_amd/softmask.py, csrc/softmask.hip).  Needs --inpainting_mode; not with --mask_track")
+    p.add_argument("--mask_feather", type=int, default=0,
+                   help="(not in the reference script) soften the mask's edge over this many pixels, 0 ... 64: the mean over a (2R + 1) x (2R + 1) "
+                        "square, after --mask_dilate and --mask_invert; whatever mask the run has (painted, tracked, automatic) becomes a "
+                        "graded one.  Needs --inpainting_mode")
     p.add_argument("--mask_auto", action="store_true",
                    help="(not in the reference script) no painted mask: the edit mask is computed from --source_prompt (what the video shows) and "
                         "--prompt (what it should show) — the noised source latent is evaluated under both prompts and the mask is where the "
@@ -259,6 +273,10 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
     """Combinations argparse cannot express: an error exit of the parser itself."""
     if args.mask_composite and not args.inpainting_mode:
         p.error("--mask_composite puts the original back outside the mask of --inpainting_mode: give both")
+    if getattr(args, "mask_graded", False) and not args.inpainting_mode:
+        p.error("--mask_graded reads the mask of --inpainting_mode as edit strengths: give both")
+    if getattr(args, "mask_feather", 0) and not args.inpainting_mode:
+        p.error("--mask_feather softens the edge of the mask of --inpainting_mode: give both")
     if args.window_frames < 0:
         p.error("--window_frames must be positive (0 = off)")
     if args.window_overlap is not None and not args.window_frames:
@@ -685,6 +703,7 @@ def check_mask_options(args) -> None:
     """--mask_track, --mask_frame, --mask_dilate, --mask_invert: what can be refused before a video is opened (ValueError, with what to do)."""
     from ccedit_amd import masktrack
     masktrack.check_dilate(getattr(args, "mask_dilate", 0))
+    check_graded(args)
     if not getattr(args, "mask_track", False):
         return
     if not args.inpainting_mode:
@@ -694,13 +713,49 @@ def check_mask_options(args) -> None:
         raise ValueError(f"--mask_frame {args.mask_frame} is outside the video: frames count from 0")
 
 
+def graded_on(args) -> bool:
+    """The run is graded — its mask is a map of edit strengths — when --mask_graded or --mask_feather was given; otherwise nothing of
+    the graded route is imported or called."""
+    return bool(getattr(args, "mask_graded", False) or getattr(args, "mask_feather", 0))
+
+
+def check_graded(args) -> None:
+    """--mask_graded, --mask_feather: what can be refused from the flags alone (ValueError, with what to do).  Without them everything passes."""
+    if not graded_on(args):
+        return
+    from ccedit_amd import softmask
+    softmask.check_feather(args.mask_feather)
+    if not args.inpainting_mode:
+        raise ValueError("--mask_graded / --mask_feather grade the edit mask of --inpainting_mode: give it too")
+    if getattr(args, "mask_graded", False) and getattr(args, "mask_track", False):
+        raise ValueError("--mask_graded with --mask_track: the tracker follows a BINARY mask through the clip — paint the mask black and "
+                         "white and soften the tracked masks with --mask_feather R instead")
+    if getattr(args, "propagate", False) and getattr(args, "mask_composite", False):
+        raise ValueError("--mask_graded / --mask_feather with --propagate --mask_composite: the frames between the keyframes are composited "
+                         "with a binary mask, a soft composite on the keyframes alone would flicker — drop --mask_composite, or drop "
+                         "--mask_graded / --mask_feather")
+    if _dist_rank_world()[1] > 1:
+        raise ValueError("--mask_graded / --mask_feather are not available in the multi-GPU modes (WORLD_SIZE > 1): a graded run is "
+                         "evaluated on one GPU — run it with one process")
+
+
 def finish_masks(args, masks):
-    """--mask_dilate, then --mask_invert, on the masks of a clip (tracked or not); at the defaults the masks as they are, nothing launched."""
+    """--mask_dilate, then --mask_invert, then --mask_feather, on the masks of a clip (tracked or not); at the defaults the masks as they
+    are, nothing launched."""
     from ccedit_amd import masktrack
     radius, invert = getattr(args, "mask_dilate", 0), getattr(args, "mask_invert", False)
-    if not radius and not invert:
-        return masks
-    return masktrack.finish(masks.cuda() if not masks.is_cuda else masks, radius, invert)
+    if radius or invert:
+        masks = masktrack.finish(masks.cuda() if not masks.is_cuda else masks, radius, invert)
+    feather = getattr(args, "mask_feather", 0)
+    if feather:
+        from ccedit_amd import ops
+        masks = ops.mask_feather((masks.cuda() if not masks.is_cuda else masks).contiguous(), feather)
+    return masks
+
+
+def _graded_kw(args) -> dict:
+    """load_video_mask's keyword of --mask_graded: the luminance bytes as they are; without the flag the call as before."""
+    return dict(graded=True) if getattr(args, "mask_graded", False) else {}
 
 
 _TRACKED = {}           # the last clip's tracked masks: --propagate asks for the clip clip_masks has just tracked
@@ -746,7 +801,7 @@ def clip_masks(args, video_paths, dev):
         video = resolve_video(v) if v else ""
         n_all = count_video_frames(video) if video and (os.path.isdir(video) or video.endswith((".gif", ".avi"))) else None
         out.append(finish_masks(args, load_video_mask(mpath, args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all,
-                                                      **_io_device(args))))
+                                                      **_io_device(args), **_graded_kw(args))))
     return torch.stack([m.to(dev) for m in out], dim=0).contiguous()
 
 
@@ -758,7 +813,7 @@ def all_frame_masks(args, video_path: str, n_all: int, dev):
     if getattr(args, "mask_track", False):
         return finish_masks(args, tracked_masks(args, video_path, mpath, dev)).contiguous()
     return finish_masks(args, load_video_mask(mpath, args.original_fps, args.target_fps, args.num_keyframes, (args.H, args.W), n_all,
-                                              device=dev, all_frames=True)).contiguous()
+                                              device=dev, all_frames=True, **_graded_kw(args))).contiguous()
 
 
 # ------------------------------------------------------------------------------------------
@@ -1078,7 +1133,8 @@ def make_closure(args, model, c, ref=None, regions=None):
 
 def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, regions=None):
     """sampling_tv2v.py:361-468 for one chunk: the sampled latent.  `mask`: the uint8 LATENT mask (bs, T, H / 8, W / 8) of
-    --inpainting_mode (ops.mask_latent of the pixel masks; 1 = edit).  `regions`: region_setup's dict (region prompts), or nothing."""
+    --inpainting_mode (ops.mask_latent of the pixel masks; 1 = edit) — in a graded run (--mask_graded / --mask_feather) the uint8 latent
+    STRENGTHS (ops.mask_latent_graded).  `regions`: region_setup's dict (region prompts), or nothing."""
     from scripts.sampling.util import init_sampling, prior_latent, sdedit_start
     denoiser, model = make_closure(args, model, c, ref=ref, regions=regions)
 
@@ -1094,6 +1150,8 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
         if not hasattr(sampler, "sample_inpainting"):
             raise NotImplementedError(f"{args.sampler_name} has no inpainting loop (the reference has one for the EDM and the ancestral samplers)")
         z = model.encode_first_stage(keyframes)
+        if graded_on(args):              # `mask` holds latent STRENGTHS: a cell is re-injected while its strength is below the step's threshold
+            return sampler.sample_inpainting(denoiser, start, c, uc=uc, x0=z, strength=mask)
         return sampler.sample_inpainting(denoiser, start, c, uc=uc, x0=z, mask=mask)
 
     if args.sdedit_denoise_strength == 0.0:
@@ -1116,7 +1174,8 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
 
 def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, mask_px=None, regions=None):
     """sampling_tv2v.py:361-470 for one chunk: sample, decode and — with --mask_composite and the pixel masks `mask_px` — put the
-    original pixels back outside the mask (ccedit_mask_composite)."""
+    original pixels back outside the mask (ccedit_mask_composite; in a graded run in proportion to the pixel strengths,
+    ccedit_mask_composite_graded)."""
     extra = dict(regions=regions) if regions else {}
     z = sample_latent(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=prior_type, mask=mask, **extra)
     if tiling(args) or windowing(args):
@@ -1125,7 +1184,8 @@ def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_t
     samples = model.decode_first_stage(z)
     if getattr(args, "mask_composite", False) and mask_px is not None:
         from ccedit_amd import ops
-        samples = ops.mask_composite(samples.float().contiguous(), keyframes.float().contiguous(), mask_px)
+        composite = ops.mask_composite_graded if graded_on(args) else ops.mask_composite
+        samples = composite(samples.float().contiguous(), keyframes.float().contiguous(), mask_px)
     return samples
 
 
@@ -1404,7 +1464,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
                     mask_px, auto_log, auto_fractions = auto_masks(args, model, dev, batch, batch_uc, c, cvideos, keyframes, source_txt)
                 else:
                     mask_px = clip_masks(args, cvideos, dev)
-                mask_lat = ops.mask_latent(mask_px)
+                mask_lat = ops.mask_latent_graded(mask_px) if graded_on(args) else ops.mask_latent(mask_px)
             region_kw = dict(regions=region_setup(args, model, dev, batch, batch_uc, c, cvideos[0], region_txt)) if regions_on(args) else {}
             t0 = time.time()
             samples = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref,
@@ -1423,6 +1483,8 @@ def run_jobs(args, with_ref: bool = False) -> None:
                                        save_grid=False, **io)
             if mask_px is not None:                                       # the mask as it was applied, same naming as control_hint/
                 m01 = (mask_px >= 128).float()[:, None].expand(-1, 3, -1, -1, -1).contiguous()
+                if graded_on(args):                                       # grey images: the writers' uint8(255 v) of (g + 0.5) / 255 is the byte g
+                    m01 = ((mask_px.float() + 0.5) / 255.0)[:, None].expand(-1, 3, -1, -1, -1).contiguous()
                 perform_save_locally_video(os.path.join(save_path, "mask"), m01 * 2.0 - 1.0 if io.get("signed") else m01, args.target_fps, args.save_type,
                                            save_grid=False, **io)
             if args.propagate:
@@ -1438,6 +1500,8 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 log_info["prompts"] += prompt_log
             if sched_log is not None:
                 log_info["prompt_schedule"] = sched_log
+            if graded_on(args):
+                log_info["mask_graded"], log_info["mask_feather"] = bool(args.mask_graded), int(args.mask_feather)
             if auto_log is not None:                                      # the settings once, the fraction of latent cells set per clip
                 log_info["mask_auto"] = dict(auto_log, fractions=log_info.get("mask_auto", {}).get("fractions", []) + auto_fractions)
             os.makedirs(os.path.dirname(log_path), exist_ok=True)
@@ -1456,7 +1520,7 @@ def single_clip_masks(args, dev) -> dict:
         return {}
     from ccedit_amd import ops
     mask_px = clip_masks(args, [args.video_path], dev)
-    return dict(mask=ops.mask_latent(mask_px), mask_px=mask_px)
+    return dict(mask=ops.mask_latent_graded(mask_px) if graded_on(args) else ops.mask_latent(mask_px), mask_px=mask_px)
 
 
 def job_mode(args) -> bool:

@@ -419,7 +419,7 @@ _MASK_IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".tif", ".tiff")
 
 
 def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyframes: int, size: tuple = None, num_allframes: int = None,
-                    device=None, all_frames: bool = False) -> torch.Tensor:
+                    device=None, all_frames: bool = False, graded: bool = False) -> torch.Tensor:
     """The edit mask of a clip -> uint8 (T, H, W) holding 0 (keep the original) or 255 (edit): the reference's
     x = x * mask + img_orig * (1 - mask) with white = 1.  (The reference leaves the mask to the user: sampling_tv2v.py:385-407.)
     mask_path: what load_video_keyframes accepts — a directory of images, a .gif or a Motion-JPEG .avi, one mask per frame of the VIDEO: `num_allframes`
@@ -430,14 +430,16 @@ def load_video_mask(mask_path: str, original_fps: int, target_fps: int, num_keyf
     running sum in double included: ccedit_amd/packing.py pil_nearest_index).  device=None: Pillow on the host.  With a device the
     binarised keyframe masks are uploaded once and gathered there (ccedit_mask_resize_nearest): identical bytes.
     all_frames (--propagate): the masks of ALL frames of the video, (num_allframes, H, W), instead of the keyframes'; one image file is
-    repeated num_allframes times (which must then be given)."""
+    repeated num_allframes times (which must then be given).
+    graded (--mask_graded): the luminance bytes as they are, no cut at 128 — byte g is the edit strength g / 255; the nearest resize
+    keeps bytes on both routes."""
     from PIL import Image
     if size:
         assert len(size) == 2, "size should be (H, W)"
 
     def lum(img):
         a = np.array(img.convert("L"))
-        return np.where(a >= 128, 255, 0).astype(np.uint8)
+        return np.ascontiguousarray(a, dtype=np.uint8) if graded else np.where(a >= 128, 255, 0).astype(np.uint8)
 
     kind = video_io.kind_of(mask_path, missing_ok=True)
     if kind is not None:
