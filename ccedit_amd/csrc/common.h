@@ -228,6 +228,15 @@ int cc_masktrack_select(const uint8_t* lum, const int32_t* pairs, const int32_t*
                         hipStream_t s);
 int cc_masktrack_step(const uint32_t* v, const uint32_t* r, const uint8_t* mg, uint8_t* mf, int32_t H, int32_t W, int32_t limit, hipStream_t s);
 
+// Motion-following noise launchers (noisewarp.hip); entry points and argument checks in core.cpp
+int cc_noisewarp_track(const int32_t* vec, const int32_t* key, int32_t* trk, int32_t K, int32_t F, int32_t H, int32_t W, int32_t limit,
+                       hipStream_t s);
+int cc_noisewarp_claim(const int32_t* trk, const int32_t* org, uint32_t* table, int32_t k, int32_t H, int32_t W, hipStream_t s);
+int cc_noisewarp_resolve(const int32_t* trk, int32_t* org, const uint32_t* table, int32_t* src, uint32_t* inherited, int32_t k, int32_t H,
+                         int32_t W, hipStream_t s);
+int cc_noisewarp_check(const int32_t* src, int64_t total, int64_t N, uint32_t* flag, hipStream_t s);
+int cc_noise_warp(const float* raw, const int32_t* src, float* out, int32_t B, int32_t C, int64_t N, hipStream_t s);
+
 // Motion-JPEG launchers (mjpeg.hip); entry points and argument checks in core.cpp
 int64_t cc_mjpeg_segment_bytes(int32_t W);
 int cc_mjpeg_transform(const uint8_t* frames, const int32_t* tab, int16_t* coef, int32_t N, int32_t H, int32_t W, int32_t quality, hipStream_t s);

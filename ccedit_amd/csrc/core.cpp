@@ -473,6 +473,65 @@ extern "C" int ccedit_masktrack_step(const void* v, const void* r, const void* m
     return cc_masktrack_step((const uint32_t*)v, (const uint32_t*)r, (const uint8_t*)mask_g, (uint8_t*)mask_f, H, W, limit, (hipStream_t)stream);
 }
 
+// ---- motion-following noise (kernels and launchers: noisewarp.hip).  Everything the host can see is checked here, before any HIP call;
+// the keyframe numbers, the block vectors, the tracked positions, the origins and the index maps are device data, held in range by
+// the kernels.  A clip of K keyframes with h w cells each must keep K h w below 2^31: the index map is int32 (and the claims, which
+// reach K h w, stay inside 32 bits).
+static int noisewarp_shape_ok(const char* fn, int32_t K, int32_t H, int32_t W) {
+    CC_CHECK_ARG(K >= 1 && K <= 65535, "%s: K=%d keyframes (1 ... 65535)", fn, K);
+    CC_CHECK_ARG(H >= 64 && W >= 64 && H % 64 == 0 && W % 64 == 0 && H <= 8192 && W <= 8192,
+                 "%s: frames of %dx%d (H and W multiples of 64, 64 ... 8192: the matcher's four pyramid levels of 8 x 8 blocks)", fn, H, W);
+    CC_CHECK_ARG((int64_t)K * (H / 8) * (W / 8) < kPixelMax, "%s: K=%d keyframes of %dx%d cells are 2^31 samples or more: the index map is int32", fn, K,
+                 H / 8, W / 8);
+    return CCEDIT_OK;
+}
+
+extern "C" int ccedit_noisewarp_track(const int32_t* vec, const int32_t* key, int32_t* track, int32_t K, int32_t F, int32_t H, int32_t W,
+                                      int32_t limit, void* stream) {
+    CC_CHECK_ARG(vec && key && track, "ccedit_noisewarp_track: null pointer");
+    if (int rc = noisewarp_shape_ok("ccedit_noisewarp_track", K, H, W)) return rc;
+    CC_CHECK_ARG(K >= 2 && F >= 2 && F <= 32767 && K <= F, "ccedit_noisewarp_track: K=%d keyframes among F=%d frames (2 <= K <= F <= 32767)", K, F);
+    CC_CHECK_ARG(limit >= 0, "ccedit_noisewarp_track: limit=%d (not negative)", limit);
+    CC_CHECK_ARG((int64_t)2 * (F - 1) * (H / 8) * (W / 8) * 2 < kPixelMax, "ccedit_noisewarp_track: F=%d frames of %dx%d: 2^31 vector components or more", F, H, W);
+    return cc_noisewarp_track(vec, key, track, K, F, H, W, limit, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_noisewarp_claim(const int32_t* track, const int32_t* org, void* table, int32_t k, int32_t K, int32_t H, int32_t W,
+                                      void* stream) {
+    CC_CHECK_ARG(track && org && table, "ccedit_noisewarp_claim: null pointer");
+    if (int rc = noisewarp_shape_ok("ccedit_noisewarp_claim", K, H, W)) return rc;
+    CC_CHECK_ARG(k >= 1 && k < K, "ccedit_noisewarp_claim: k=%d (1 ... K - 1 = %d: keyframe 0 inherits nothing)", k, K - 1);
+    CC_CHECK_ARG(((uintptr_t)table & 3) == 0, "ccedit_noisewarp_claim: table must be 4-byte aligned");
+    return cc_noisewarp_claim(track, org, (uint32_t*)table, k, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_noisewarp_resolve(const int32_t* track, int32_t* org, const void* table, int32_t* src, void* inherited, int32_t k,
+                                        int32_t K, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(track && org && table && src && inherited, "ccedit_noisewarp_resolve: null pointer");
+    if (int rc = noisewarp_shape_ok("ccedit_noisewarp_resolve", K, H, W)) return rc;
+    CC_CHECK_ARG(k >= 0 && k < K, "ccedit_noisewarp_resolve: k=%d (0 ... K - 1 = %d)", k, K - 1);
+    CC_CHECK_ARG((((uintptr_t)table | (uintptr_t)inherited) & 3) == 0, "ccedit_noisewarp_resolve: table and inherited must be 4-byte aligned");
+    return cc_noisewarp_resolve(track, org, (const uint32_t*)table, src, (uint32_t*)inherited, k, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_noisewarp_check(const int32_t* src, int64_t maps, int64_t N, void* flag, void* stream) {
+    CC_CHECK_ARG(src && flag, "ccedit_noisewarp_check: null pointer");
+    CC_CHECK_ARG(maps >= 1 && N >= 1 && N < kPixelMax && maps * N < kPixelMax * 4, "ccedit_noisewarp_check: %lld maps of N=%lld indices (N below 2^31)",
+                 (long long)maps, (long long)N);
+    CC_CHECK_ARG((((uintptr_t)src | (uintptr_t)flag) & 3) == 0, "ccedit_noisewarp_check: src and flag must be 4-byte aligned");
+    return cc_noisewarp_check(src, maps * N, N, (uint32_t*)flag, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_noise_warp(const float* raw, const int32_t* src, float* out, int32_t B, int32_t C, int64_t N, void* stream) {
+    CC_CHECK_ARG(raw && src && out, "ccedit_noise_warp: null pointer");
+    CC_CHECK_ARG(B >= 1 && C >= 1 && N >= 1 && N < kPixelMax, "ccedit_noise_warp: B=%d C=%d N=%lld (positive, N below 2^31: the map is int32)", B, C,
+                 (long long)N);
+    CC_CHECK_ARG((int64_t)B * C < kPixelMax && (int64_t)B * C * N < kPixelMax * 4, "ccedit_noise_warp: more than 2^33 samples in one call");
+    CC_CHECK_ARG((((uintptr_t)raw | (uintptr_t)src | (uintptr_t)out) & 3) == 0, "ccedit_noise_warp: raw, src and out must be 4-byte aligned");
+    CC_CHECK_ARG(raw != out, "ccedit_noise_warp: out is gathered from raw: two buffers");
+    return cc_noise_warp(raw, src, out, B, C, N, (hipStream_t)stream);
+}
+
 // ---- Motion-JPEG (kernels and launchers: mjpeg.hip).  Everything the host can see is checked here, before any HIP call; the device
 // tables (constants, segment lengths and offsets) are held in range by the kernels themselves.
 static int mjpeg_shape_ok(const char* fn, int32_t N, int32_t H, int32_t W) {

@@ -190,6 +190,13 @@ _SIGS = {
     "ccedit_mask_composite_graded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "ccedit_inpaint_blend_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
                                              C.c_float, C.c_float, C.c_void_p]),
+    # motion-following noise (csrc/noisewarp.hip): added within ABI 12, nothing existing changed
+    "ccedit_noisewarp_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_noisewarp_claim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_noisewarp_resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p]),
+    "ccedit_noisewarp_check": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ccedit_noise_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     # Motion-JPEG output (csrc/mjpeg.hip): added within ABI 12, nothing existing changed
     "ccedit_mjpeg_segment_bytes": (C.c_int64, [C.c_int32]),
     "ccedit_mjpeg_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

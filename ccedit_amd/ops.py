@@ -1401,6 +1401,77 @@ def mask_composite_graded(result: torch.Tensor, original: torch.Tensor, strength
 
 
 # ------------------------------------------------------------------------------------------
+# Motion-following noise (csrc/noisewarp.hip; constants, the clip's build and the sampler wrap: ccedit_amd/noisewarp.py)
+# ------------------------------------------------------------------------------------------
+def noisewarp_track(vec: torch.Tensor, key, h: int, w: int, limit: int) -> torch.Tensor:
+    """vec: the block vectors int32 (2 (F - 1), h / 8, w / 8, 2) of the adjacent pairs of F frames, for frame f row 2 (f - 1) = (f, f - 1)
+    and row 2 (f - 1) + 1 = (f - 1, f); key: the keyframes' frame numbers (host integers, key[0] = 0, strictly increasing, below F)
+    -> int32 (K, cells, 3) = (valid, Q_y, Q_x): every cell's centre followed from keyframe k back to keyframe k - 1; row 0 is zero."""
+    if vec.dim() != 4 or vec.shape[0] % 2 or vec.shape[0] < 2:
+        raise ValueError(f"noisewarp_track: vec (2 (F - 1), h / 8, w / 8, 2) of at least two frames, got {tuple(vec.shape)}")
+    frames = vec.shape[0] // 2 + 1
+    _chk_i32(vec, "noisewarp_track: vec", (2 * (frames - 1), h // 8, w // 8, 2))
+    key = [int(i) for i in key]
+    if len(key) < 2 or key[0] != 0 or key[-1] >= frames or any(b <= a for a, b in zip(key, key[1:])):
+        raise ValueError(f"noisewarp_track: keyframes {key} of {frames} frames: at least two, from 0, strictly increasing, below the frame count")
+    out = torch.zeros((len(key), (h // 8) * (w // 8), 3), dtype=torch.int32, device=vec.device)
+    kd = torch.tensor(key, dtype=torch.int32).to(vec.device)
+    hip.check(hip.lib().ccedit_noisewarp_track(vec.data_ptr(), kd.data_ptr(), out.data_ptr(), len(key), frames, h, w, int(limit), _stream()),
+              "ccedit_noisewarp_track")
+    return out
+
+
+def noisewarp_origins(track: torch.Tensor, h: int, w: int):
+    """track: int32 (K, cells, 3) of noisewarp_track -> (org int32 (K, cells, 3) = (R, P_y, P_x), src int32 (K, cells), inherited int32
+    (K,)): keyframe 0 is its own origin; then per keyframe a claim and a resolve launch — of the cells that arrive at one sample of an
+    earlier keyframe the smallest index inherits it, every other cell is fresh.  The counts stay on the device."""
+    cells = (h // 8) * (w // 8)
+    k_all = track.shape[0]
+    _chk_i32(track, "noisewarp_origins: track", (k_all, cells, 3))
+    dev = track.device
+    org = torch.empty((k_all, cells, 3), dtype=torch.int32, device=dev)
+    src = torch.empty((k_all, cells), dtype=torch.int32, device=dev)
+    table = torch.zeros(k_all * cells, dtype=torch.int32, device=dev)          # (read and written as uint32)
+    inherited = torch.zeros(k_all, dtype=torch.int32, device=dev)
+    lib, st = hip.lib(), _stream()
+    for k in range(k_all):
+        if k:
+            hip.check(lib.ccedit_noisewarp_claim(track.data_ptr(), org.data_ptr(), table.data_ptr(), k, k_all, h, w, st), "ccedit_noisewarp_claim")
+        hip.check(lib.ccedit_noisewarp_resolve(track.data_ptr(), org.data_ptr(), table.data_ptr(), src.data_ptr(), inherited.data_ptr(), k, k_all,
+                                               h, w, st), "ccedit_noisewarp_resolve")
+    return org, src, inherited
+
+
+def noisewarp_check(src: torch.Tensor) -> None:
+    """src: int32 (B, K, cells) index maps.  An index outside 0 ... K cells - 1 is an error status (hip.HipLibraryError).  Waits for the device:
+    once per map (noisewarp.wrap), never per draw."""
+    if src.dtype != torch.int32 or not src.is_cuda or not src.is_contiguous() or src.dim() != 3:
+        raise ValueError(f"noisewarp_check: expected a contiguous cuda int32 map (B, K, cells), got {src.dtype} {src.device} {tuple(src.shape)}")
+    flag = torch.empty(1, dtype=torch.int32, device=src.device)
+    hip.check(hip.lib().ccedit_noisewarp_check(src.data_ptr(), src.shape[0], src.shape[1] * src.shape[2], flag.data_ptr(), _stream()),
+              "ccedit_noisewarp_check")
+
+
+def noise_warp(raw: torch.Tensor, src: torch.Tensor, out: Optional[torch.Tensor] = None, checked: bool = False) -> torch.Tensor:
+    """out[b][c][k][cell] = raw[b][c].flat[src[b][k][cell]] over fp32 (B, C, K, h, w) with int32 maps (B, K, h w): a 4-byte bit copy.
+    checked=False: the map's indices are verified first (noisewarp_check: a device round trip) — a caller that verified its map once
+    passes checked=True.  `out`: where to write (fp32, the shape of raw, dense; another buffer than raw)."""
+    if raw.dtype != torch.float32 or not raw.is_cuda or not raw.is_contiguous() or raw.dim() != 5:
+        raise ValueError(f"noise_warp: raw must be a contiguous cuda fp32 tensor (B, C, K, h, w), got {raw.dtype} {raw.device} {tuple(raw.shape)}")
+    b, c, k, h, w = raw.shape
+    _chk_i32(src, "noise_warp: src", (b, k, h * w))
+    y = torch.empty_like(raw) if out is None else out
+    if y.dtype != torch.float32 or not y.is_cuda or not y.is_contiguous() or tuple(y.shape) != tuple(raw.shape):
+        raise ValueError(f"noise_warp: out must be a contiguous cuda fp32 tensor {tuple(raw.shape)}, got {y.dtype} {y.device} {tuple(y.shape)}")
+    if not checked:
+        noisewarp_check(src)
+    n = k * h * w
+    _launch_mem("noise_warp", 12.0 * b * c * n, lambda: hip.check(hip.lib().ccedit_noise_warp(
+        raw.data_ptr(), src.data_ptr(), y.data_ptr(), b, c, n, _stream()), "ccedit_noise_warp"), (b, c, k, h, w))
+    return y
+
+
+# ------------------------------------------------------------------------------------------
 # Motion-JPEG output (csrc/mjpeg.hip; constants, header, container and the frame loop: ccedit_amd/mjpeg.py)
 # ------------------------------------------------------------------------------------------
 def mjpeg_segment_bytes(w: int) -> int:

@@ -703,6 +703,41 @@ int ccedit_inpaint_blend_level(const float* x, const float* x0, const float* noi
                                int64_t P, int32_t thr, float sigma, float s, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Motion-following noise (added without an ABI bump: five new functions, CCEDIT_ABI_VERSION stays 12).  `--noise_warp`: once per clip
+ * it is decided which noise sample every latent cell (8 x 8 pixels) of every keyframe inherits from an earlier keyframe along the
+ * source's motion, and every noise draw of the run is gathered through that decision (ccedit_amd/noisewarp.py: constants, build, wrap).
+ * Kernels: csrc/noisewarp.hip.  Integer arithmetic and bit copies; all equal tests/_noisewarp_numpy.py bit for bit.  A clip is F
+ * source frames of H x W (multiples of 64) with K keyframes; h = H / 8, w = W / 8, cells = h w, K cells < 2^31; the centre of cell
+ * (i, j) is the pixel (8 i + 4, 8 j + 4).  All pointers are device pointers; device data is held in range by the kernels.
+ *
+ * ccedit_noisewarp_track: vec: block vectors int32 [2 (F - 1)][h][w][2] of ccedit_prop_match, for frame f >= 1 row 2 (f - 1) is the pair
+ *   (f, f - 1) and row 2 (f - 1) + 1 the pair (f - 1, f); every component is clamped into +-64 where it is read.  key: int32 [K], the
+ *   keyframes' frame numbers, key[0] = 0, strictly increasing.  One thread per (k >= 1, cell): p = the cell's centre; for f = key[k]
+ *   down to key[k - 1] + 1: v = vec(f -> f - 1) at cell p >> 3, q = p + v, inside = q lies in the frame, q is clamped into it,
+ *   r = vec(f - 1 -> f) at cell q >> 3, valid &= inside & (|v_y + r_y| + |v_x + r_x| <= limit), p = q.  track [K][cells][3] =
+ *   (valid, Q_y, Q_x); row 0 is not written.
+ * ccedit_noisewarp_claim: keyframe k >= 1.  A cell with valid track: c' = Q >> 3, (R', P') = org[k - 1][c'], P = P' + Q - centre(c');
+ *   where P lies in the frame it bids atomicMax(table[R' cells + (P_y >> 3) w + (P_x >> 3)], k cells + (cells - 1 - idx) + 1).
+ *   table: uint32 [K cells], zeroed once per clip.
+ * ccedit_noisewarp_resolve: keyframe k, after its claim (k = 0: no claim, nothing is read).  A cell whose own bid the table holds gets
+ *   org[k][idx] = (R', P), every other cell (k, own centre); src[k][idx] = R cells + (P_y >> 3) w + (P_x >> 3); inherited[k] (uint32 [K],
+ *   zeroed once per clip) += the number of cells with R != k.  org [K][cells][3], src [K][cells].  Claim and resolve of the keyframes
+ *   run in order on one stream: the kernel boundary is the ordering.
+ * ccedit_noisewarp_check: CCEDIT_EINVAL where any of the maps' indices src [maps][N] lies outside 0 ... N - 1.  flag: one uint32 of
+ *   workspace.  Waits for the stream (one word comes back to the host): once per map, not per draw.
+ * ccedit_noise_warp: out[b][c][n] = raw[b][c][src[b][n]] over fp32 [B][C][N] moved as 32-bit words (NaN payloads survive), src int32
+ *   [B][N], one map per clip; an index is held inside 0 ... N - 1.  16-byte stores where N % 4 == 0 and src and out are 16-byte aligned,
+ *   4-byte accesses otherwise.  raw and out are two buffers.
+ */
+int ccedit_noisewarp_track(const int32_t* vec, const int32_t* key, int32_t* track, int32_t K, int32_t F, int32_t H, int32_t W, int32_t limit,
+                           void* stream);
+int ccedit_noisewarp_claim(const int32_t* track, const int32_t* org, void* table, int32_t k, int32_t K, int32_t H, int32_t W, void* stream);
+int ccedit_noisewarp_resolve(const int32_t* track, int32_t* org, const void* table, int32_t* src, void* inherited, int32_t k, int32_t K,
+                             int32_t H, int32_t W, void* stream);
+int ccedit_noisewarp_check(const int32_t* src, int64_t maps, int64_t N, void* flag, void* stream);
+int ccedit_noise_warp(const float* raw, const int32_t* src, float* out, int32_t B, int32_t C, int64_t N, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG (added without an ABI bump: five new functions, CCEDIT_ABI_VERSION stays 12).  `--save_type mjpeg`: uint8 frames
  * [N][H][W][3] on the device (what ccedit_frames_to_u8 writes) -> one baseline JPEG per frame (ITU-T T.81: sequential DCT, 8 bit,
  * YCbCr 4:2:0, MCU 16 x 16, restart interval = one MCU row = one SEGMENT), ccedit_amd/mjpeg.py: constants, header, container.

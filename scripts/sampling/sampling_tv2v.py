@@ -38,6 +38,12 @@ source for the first (1 - s) of the walked schedule and left alone afterwards, a
 proportion to the pixel strengths (ccedit_amd/softmask.py, csrc/softmask.hip); mask/ then holds grey images and log_info.json gains
 `mask_graded` and `mask_feather`.  Refused: --mask_graded with --mask_track, a graded run with --propagate --mask_composite or with
 WORLD_SIZE > 1.  Image quality is not claimed.
+`--noise_warp` carries every noise draw of the run — the start latent, the ancestral / churn noise of every step, the re-injection noise
+of --inpainting_mode, the SDEdit start — from keyframe to keyframe along the SOURCE's motion: once per clip an index map says which sample
+every latent cell of every keyframe inherits (the matcher of --propagate, every frame reads distinct samples: its noise stays white), and
+every draw is gathered through it (ccedit_amd/noisewarp.py, csrc/noisewarp.hip); `--noise_warp_rho R` (0 ... 1, default 1) mixes
+sqrt(1 - R^2) of a fresh draw in; log_info.json gains `noise_warp`.  Needs a video and --H, --W multiples of 64; refused with a
+reference image and with WORLD_SIZE > 1.  Image quality is not claimed.
 `--window_frames T` (with `--window_overlap O`, default T // 2) lifts the limit of one window of keyframes: with `--num_keyframes N` > T the
 clip is covered by overlapping windows of T frames, each evaluated by the unchanged network at every sampler evaluation and fused into
 one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everything else — inpainting, SDEdit, the prior mix,
@@ -91,6 +97,14 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GUIDER = "sgm.modules.diffusionmodules.guiders.VanillaCFGTV2V"
+
+
+class _StoreGiven(argparse.Action):
+    """store, and note on the namespace (<dest>_given) that the flag was on the command line: a default cannot tell."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
 
 
 def add_common_args(p: argparse.ArgumentParser) -> None:
@@ -247,6 +261,15 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(not in the reference script) draw the samplers' per-step noise from a CPU generator with this seed instead of "
                         "torch.randn_like on the device: the same clip on any GPU / against the CPU oracle (tests)")
+    p.add_argument("--noise_warp", action="store_true",
+                   help="(not in the reference script) motion-following noise: every noise draw of the run — the start latent, the ancestral "
+                        "noise of every step, the re-injection noise of --inpainting_mode, the SDEdit start — is carried from keyframe to "
+                        "keyframe along the SOURCE's motion, so that a moving surface keeps its noise; the noise of every single frame stays "
+                        "white (ccedit_amd/noisewarp.py, csrc/noisewarp.hip).  Needs --video_path (or its kin) and --H, --W multiples of 64; "
+                        "log_info.json gains `noise_warp`")
+    p.add_argument("--noise_warp_rho", type=float, default=1.0, action=_StoreGiven,
+                   help="with --noise_warp: the correlation of a keyframe's noise with the noise it inherits, 0 ... 1 (default 1: carried "
+                        "exactly; below 1 a second, independent draw is mixed in: rho * carried + sqrt(1 - rho^2) * fresh)")
     p.add_argument("--disable_check_repeat", action="store_true")
     p.add_argument("--gpu_io", action="store_true",
                    help="pixel I/O on the GPU (ccedit_amd/csrc/pixel.hip): frame / depth resize, depth hint normalisation and the uint8 "
@@ -308,6 +331,7 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
     check_region_options(args)               # (--region_prompt and its kin: ValueError; nothing is imported or checked without the flags)
     check_mask_auto(args)                    # (--mask_auto and its kin: ValueError; nothing is imported or checked without the flag)
     check_prompt_schedule(args)              # (--prompt_at: ValueError / NotImplementedError; nothing is imported or checked without the flag)
+    check_noise_warp(args)                   # (--noise_warp and its rho: ValueError; nothing is imported without the flag)
 
 
 def windowing(args) -> bool:
@@ -662,6 +686,13 @@ def save_result(args, tag, x):
         perform_save_locally_video(os.path.join(args.save_path, "result"), torch.clamp((x + 1.0) / 2.0, 0.0, 1.0),
                                    fps=args.target_fps, savetype=args.save_type, **options)
     save_frames(args.save_path, tag, x)
+
+
+def _once(first):
+    """A noise source whose FIRST draw is the tensor the caller already holds (the start latent's randn, drawn from the run's CPU
+    generator as always); whatever is drawn after it is torch.randn_like — the fresh part of --noise_warp_rho < 1."""
+    held = [first]
+    return lambda x: held.pop() if held else torch.randn_like(x)
 
 
 def _cpu_noise(sampler, args) -> None:
@@ -1096,6 +1127,64 @@ def region_log(args) -> list:
             for q, m in zip(args.region_prompt, args.region_mask)]
 
 
+# ------------------------------------------------------------------------------------------
+# Motion-following noise: --noise_warp (ccedit_amd/noisewarp.py)
+# ------------------------------------------------------------------------------------------
+def noise_warp_on(args) -> bool:
+    """Motion-following noise is active when --noise_warp was given; otherwise nothing of it is imported or called."""
+    return bool(getattr(args, "noise_warp", False))
+
+
+def check_noise_warp(args, with_ref: bool = False) -> None:
+    """Before any GPU work, from the flags alone: what --noise_warp needs and what it cannot be combined with (ValueError naming the
+    flags, with what to do).  Without the flag only a stray --noise_warp_rho is refused."""
+    if not noise_warp_on(args):
+        if getattr(args, "noise_warp_rho_given", False):
+            raise ValueError("--noise_warp_rho is the correlation of --noise_warp's carried noise: give --noise_warp too, or drop it")
+        return
+    from ccedit_amd import noisewarp
+    noisewarp.check_rho(getattr(args, "noise_warp_rho", 1.0))
+    if with_ref:
+        raise ValueError("--noise_warp is not available with a reference image (sampling_tv2v_ref.py): the reference image pins the centre "
+                         "frame, the carried noise belongs to a run of sampling_tv2v.py — run that script, or drop --noise_warp")
+    if _dist_rank_world()[1] > 1:
+        raise ValueError("--noise_warp is not available in the multi-GPU modes (WORLD_SIZE > 1): the noise map of a clip is built and "
+                         "applied on one GPU — run it with one process")
+    if not (args.video_path or getattr(args, "video_listpath", "") or args.videos_directory or args.json_path):
+        raise ValueError("--noise_warp carries the noise along the motion of a source video: give --video_path (or --video_listpath / "
+                         "--videos_directory / --json_path)")
+    if args.H % 64 or args.W % 64:
+        raise ValueError(f"--noise_warp with --H {args.H} --W {args.W}: the motion matcher's pyramid (four levels of 8 x 8 blocks) takes frame "
+                         "sides that are multiples of 64 — choose such a size, or drop --noise_warp")
+    noisewarp.check_clip(args.num_keyframes, args.H, args.W)
+
+
+_WARPED = {}            # the last clip's noise map and shares: the samples of a clip (--num_samples) share one build
+
+
+def noise_map(args, video_path: str, dev):
+    """--noise_warp for one clip: all source frames on the device the way --propagate's come (load_video_frames_u8), the keyframes'
+    frame numbers by keyframe_indices -> (src int32 (K, cells) on `dev`, shares per keyframe).  Cached per clip like the tracked masks."""
+    from ccedit_amd import noisewarp
+    from scripts.sampling.util import keyframe_indices, load_video_frames_u8
+    if not video_path:
+        raise ValueError("--noise_warp carries the noise along the motion of a source video: this clip has none — give --video_path")
+    video = resolve_video(video_path)
+    key = (video, args.original_fps, args.target_fps, args.num_keyframes, args.H, args.W, str(dev), getattr(args, "gif_decoder", "pillow"))
+    if key not in _WARPED:
+        source = load_video_frames_u8(video, (args.H, args.W), dev, **_gif_decoder(args))
+        idx = keyframe_indices(source.shape[0], args.original_fps, args.target_fps, args.num_keyframes)
+        _WARPED.clear()
+        _WARPED[key] = noisewarp.build(source, idx)
+    return _WARPED[key]
+
+
+def noise_maps(args, video_paths, dev):
+    """The maps of a chunk -> (src int32 (bs, K, cells) on `dev`, [shares per keyframe] per clip)."""
+    built = [noise_map(args, v, dev) for v in video_paths]
+    return torch.stack([b[0] for b in built], dim=0).contiguous(), [b[1] for b in built]
+
+
 def make_closure(args, model, c, ref=None, regions=None):
     """The closure `denoiser(input, sigma, cond)` every sampler evaluation of a chunk goes through — plain, windowed (--window_frames),
     tiled (--tile_h / --tile_w), region prompts outermost — and the engine whose first stage works in groups that fit it.  Used by
@@ -1131,10 +1220,11 @@ def make_closure(args, model, c, ref=None, regions=None):
     return denoiser, model
 
 
-def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, regions=None):
+def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, regions=None, noise_src=None):
     """sampling_tv2v.py:361-468 for one chunk: the sampled latent.  `mask`: the uint8 LATENT mask (bs, T, H / 8, W / 8) of
     --inpainting_mode (ops.mask_latent of the pixel masks; 1 = edit) — in a graded run (--mask_graded / --mask_feather) the uint8 latent
-    STRENGTHS (ops.mask_latent_graded).  `regions`: region_setup's dict (region prompts), or nothing."""
+    STRENGTHS (ops.mask_latent_graded).  `regions`: region_setup's dict (region prompts), or nothing.  `noise_src`: the chunk's noise
+    maps (bs, T, cells) of --noise_warp (noise_maps), or nothing: the start noise and every draw of the sampler go through them."""
     from scripts.sampling.util import init_sampling, prior_latent, sdedit_start
     denoiser, model = make_closure(args, model, c, ref=ref, regions=regions)
 
@@ -1154,13 +1244,28 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
             return sampler.sample_inpainting(denoiser, start, c, uc=uc, x0=z, strength=mask)
         return sampler.sample_inpainting(denoiser, start, c, uc=uc, x0=z, mask=mask)
 
+    def warp_noise(sampler):
+        """--noise_warp: around whatever the noise source is by now (--noise_seed's CPU generator or the device's), so that every draw
+        of the walk — ancestral, churn, re-injection — is carried.  -> the source sdedit_start draws from, or None: its own."""
+        if noise_src is None:
+            return None
+        from ccedit_amd import noisewarp
+        wrapped = noisewarp.wrap(getattr(sampler, "noise_sampler", torch.randn_like), noise_src, args.noise_warp_rho)
+        if hasattr(sampler, "noise_sampler"):
+            sampler.noise_sampler = wrapped
+        return wrapped
+
     if args.sdedit_denoise_strength == 0.0:
+        if noise_src is not None:            # the start noise is carried like every later draw (at rho < 1 with a fresh part from the device)
+            from ccedit_amd import noisewarp
+            randn = noisewarp.wrap(_once(randn), noise_src, args.noise_warp_rho)(randn)
         if args.prior_coefficient_x != 0.0:
             randn = prior_latent(model, randn, args.prior_coefficient_x, args.prior_coefficient_noise, keyframes, ref, prior_type)
         sampler = init_sampling(sample_steps=args.sample_steps, sampler_name=args.sampler_name,
                                 discretization_name=args.discretization_name, guider_config_target=GUIDER,
                                 cfg_scale=args.cfg_scale)
         _cpu_noise(sampler, args)
+        warp_noise(sampler)
         return run(sampler, randn)
     else:
         assert 0.0 < args.sdedit_denoise_strength <= 1.0, "sdedit_denoise_strength should be in (0, 1]"
@@ -1169,14 +1274,18 @@ def sample_latent(args, model, dev, c, uc, randn, keyframes=None, ref=None, prio
                                 discretization_name=args.discretization_name, guider_config_target=GUIDER,
                                 cfg_scale=args.cfg_scale, img2img_strength=args.sdedit_denoise_strength)
         _cpu_noise(sampler, args)
-        return run(sampler, sdedit_start(model, sampler, keyframes))
+        carried = warp_noise(sampler)
+        return run(sampler, sdedit_start(model, sampler, keyframes, **(dict(noise=carried) if carried is not None else {})))
 
 
-def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, mask_px=None, regions=None):
+def sample_one(args, model, dev, c, uc, randn, keyframes=None, ref=None, prior_type="video", mask=None, mask_px=None, regions=None,
+               noise_src=None):
     """sampling_tv2v.py:361-470 for one chunk: sample, decode and — with --mask_composite and the pixel masks `mask_px` — put the
     original pixels back outside the mask (ccedit_mask_composite; in a graded run in proportion to the pixel strengths,
     ccedit_mask_composite_graded)."""
     extra = dict(regions=regions) if regions else {}
+    if noise_src is not None:
+        extra["noise_src"] = noise_src
     z = sample_latent(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref, prior_type=prior_type, mask=mask, **extra)
     if tiling(args) or windowing(args):
         from ccedit_amd.windows import GroupedFirstStage
@@ -1350,6 +1459,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
     check_region_options(args, with_ref)
     check_mask_auto(args, with_ref)
     check_prompt_schedule(args, with_ref)
+    check_noise_warp(args, with_ref)
     from ccedit_amd.parallel import shard_clips
     from scripts.sampling.util import chunk, load_img, load_video_keyframes, model_load_ckpt, perform_save_locally_video
     prompts, video_paths, video_save_paths, ref_paths = expand_jobs(args, with_ref)
@@ -1466,6 +1576,9 @@ def run_jobs(args, with_ref: bool = False) -> None:
                     mask_px = clip_masks(args, cvideos, dev)
                 mask_lat = ops.mask_latent_graded(mask_px) if graded_on(args) else ops.mask_latent(mask_px)
             region_kw = dict(regions=region_setup(args, model, dev, batch, batch_uc, c, cvideos[0], region_txt)) if regions_on(args) else {}
+            warp_shares = None
+            if noise_warp_on(args):                                       # one map per clip of the chunk, built once per clip
+                region_kw["noise_src"], warp_shares = noise_maps(args, cvideos, dev)
             t0 = time.time()
             samples = sample_one(args, model, dev, c, uc, randn, keyframes=keyframes, ref=ref,
                                  prior_type=getattr(args, "prior_type", "video"), mask=mask_lat, mask_px=mask_px, **region_kw)
@@ -1502,6 +1615,9 @@ def run_jobs(args, with_ref: bool = False) -> None:
                 log_info["prompt_schedule"] = sched_log
             if graded_on(args):
                 log_info["mask_graded"], log_info["mask_feather"] = bool(args.mask_graded), int(args.mask_feather)
+            if warp_shares is not None:                                   # rho once; per clip the share of cells of every keyframe that inherit
+                log_info["noise_warp"] = dict(rho=float(args.noise_warp_rho), inherited=warp_shares[-1],       # (the clip done last; all of them:)
+                                              clips=log_info.get("noise_warp", {}).get("clips", []) + warp_shares)
             if auto_log is not None:                                      # the settings once, the fraction of latent cells set per clip
                 log_info["mask_auto"] = dict(auto_log, fractions=log_info.get("mask_auto", {}).get("fractions", []) + auto_fractions)
             os.makedirs(os.path.dirname(log_path), exist_ok=True)
@@ -1536,6 +1652,7 @@ def main():
     check_windowing(args)
     check_tiling(args)
     check_region_jobs(args, 1)
+    check_noise_warp(args)
     from scripts.sampling.util import ResumeLog, save_frames
     model, dev = build_model(args)
     T, h, w = args.num_keyframes, args.H // 8, args.W // 8
@@ -1566,6 +1683,9 @@ def main():
     keyframes = cond["keyframes"].to(dev) if need_frames else None
     if regions_on(args):
         masks["regions"] = region_setup(args, model, dev, batch, batch_uc, c, args.video_path, region_txt)
+    warp_shares = None
+    if noise_warp_on(args):
+        masks["noise_src"], warp_shares = noise_maps(args, [args.video_path], dev)
     log = ResumeLog(args.save_path)
     for i in range(args.num_samples):
         tag = f"sample_{i:04d}"
@@ -1581,6 +1701,8 @@ def main():
             log.log["regions"] = region_log(args)
         if prompt_log is not None:
             log.log["prompts"] = prompt_log
+        if warp_shares is not None:
+            log.log["noise_warp"] = dict(rho=float(args.noise_warp_rho), inherited=warp_shares[0])
         log.add(tag)
 
 

@@ -89,12 +89,13 @@ def prior_latent(model, randn: torch.Tensor, coeff_x: float, coeff_noise: float,
     return ops.axpby(prior.contiguous(), randn.float().contiguous(), coeff_x, coeff_noise)
 
 
-def sdedit_start(model, sampler, keyframes: torch.Tensor) -> torch.Tensor:
+def sdedit_start(model, sampler, keyframes: torch.Tensor, noise=None) -> torch.Tensor:
     """z = encode(keyframes); noised_z = (z + randn_like(z) * sigma0) / sqrt(1 + sigma0^2) with sigma0 the first of the
-    pruned schedule (hard-coded DDPM-like scaling, as in the reference)."""
+    pruned schedule (hard-coded DDPM-like scaling, as in the reference).  noise: a noise source x -> noise of x's shape to draw from
+    in place of torch.randn_like (--noise_warp's carried source); None: as before."""
     from ccedit_amd import ops
     z = model.encode_first_stage(keyframes)
-    noise = torch.randn_like(z)
+    noise = torch.randn_like(z) if noise is None else noise(z).to(z.dtype)
     sigmas = sampler.discretization(sampler.num_steps)
     s0 = float(sigmas[0])
     inv = 1.0 / float(torch.sqrt(1.0 + sigmas[0].float() ** 2.0))
