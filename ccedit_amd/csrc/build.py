@@ -13,14 +13,14 @@ import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.abspath(os.path.join(HERE, "..", "libccedit_hip.so"))
-SOURCES = ["gemm.hip", "gemm8p.hip", "convhalo.hip", "smallconv.hip", "lin320.hip", "lin640.hip", "temp320.hip", "ff320.hip", "norm.hip", "attention.hip", "attnspatial.hip", "attnshort.hip", "attntext.hip", "attntextlong.hip", "elementwise.hip", "f32vae.hip", "pixel.hip", "mask.hip", "softmask.hip", "window.hip", "tile.hip", "region.hip", "automask.hip", "prompt.hip", "propagate.hip", "masktrack.hip", "noisewarp.hip", "mjpeg.hip", "jpegdec.hip", "gif.hip", "png.hip", "pngdec.hip", "gifdec.hip", "core.cpp"]
+SOURCES = ["gemm.hip", "gemm8p.hip", "convhalo.hip", "smallconv.hip", "lin320.hip", "lin640.hip", "temp320.hip", "ff320.hip", "norm.hip", "attention.hip", "attnspatial.hip", "attnshort.hip", "attntext.hip", "attntextlong.hip", "elementwise.hip", "f32vae.hip", "pixel.hip", "mask.hip", "softmask.hip", "window.hip", "tile.hip", "region.hip", "automask.hip", "prompt.hip", "propagate.hip", "masktrack.hip", "noisewarp.hip", "quality.hip", "mjpeg.hip", "jpegdec.hip", "gif.hip", "png.hip", "pngdec.hip", "gifdec.hip", "core.cpp"]
 ARCH = "gfx950"
 # per-file flags: ff320's GEGLU must stay scalar fp32 (packed fp32 VALU is several times slower beside MFMAs, see the file).
 # norm.hip / attnshort.hip: without the SLP vectoriser nothing there becomes a packed-fp32 op whose LOW lane reads the HIGH half of
 # a register pair (`v_pk_add_f32 ... op_sel:[0,1]`).  That form returned 0 for the swizzled operand in lanes 48-63 about once per
 # 10^7 waves when another stream's tap_gemm kernel (AGPR-resident accumulators) shared the SIMD: LayerNorm beside a GEMM on a
 # second stream was not run-to-run reproducible (tools/exp/repro_e4.py; DESIGN.md section 3, streams).  check_isa() refuses it.
-# pixel.hip, mask.hip, softmask.hip, window.hip, tile.hip, region.hip, automask.hip, prompt.hip, propagate.hip, masktrack.hip, noisewarp.hip, mjpeg.hip, jpegdec.hip, gif.hip, png.hip, pngdec.hip and gifdec.hip reproduce host results bit for bit: no multiply-add contraction where the reference rounds twice.
+# pixel.hip, mask.hip, softmask.hip, window.hip, tile.hip, region.hip, automask.hip, prompt.hip, propagate.hip, masktrack.hip, noisewarp.hip, quality.hip, mjpeg.hip, jpegdec.hip, gif.hip, png.hip, pngdec.hip and gifdec.hip reproduce host results bit for bit: no multiply-add contraction where the reference rounds twice.
 EXTRA_FLAGS = {"ff320.hip": ["-fno-slp-vectorize"], "norm.hip": ["-fno-slp-vectorize"], "attnshort.hip": ["-fno-slp-vectorize"],
                "pixel.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "mask.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "softmask.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
@@ -31,6 +31,7 @@ EXTRA_FLAGS = {"ff320.hip": ["-fno-slp-vectorize"], "norm.hip": ["-fno-slp-vecto
                "propagate.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "masktrack.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "noisewarp.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+               "quality.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "mjpeg.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "jpegdec.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "gif.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "png.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "pngdec.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "gifdec.hip": ["-ffp-contract=off", "-fno-slp-vectorize"]}

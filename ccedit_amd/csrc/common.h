@@ -237,6 +237,11 @@ int cc_noisewarp_resolve(const int32_t* trk, int32_t* org, const uint32_t* table
 int cc_noisewarp_check(const int32_t* src, int64_t total, int64_t N, uint32_t* flag, hipStream_t s);
 int cc_noise_warp(const float* raw, const int32_t* src, float* out, int32_t B, int32_t C, int64_t N, hipStream_t s);
 
+// Quality-report launchers (quality.hip); entry points and argument checks in core.cpp
+int cc_quality_pair(const uint8_t* a, const uint8_t* b, const uint8_t* mask, uint64_t* acc, int64_t N, int32_t H, int32_t W, hipStream_t s);
+int cc_quality_warp(const uint8_t* x, const uint8_t* y, const uint32_t* vsel, const int32_t* pairs, const uint8_t* mask, uint64_t* acc, int32_t P,
+                    int32_t F, int32_t H, int32_t W, int32_t limit, int32_t sel, hipStream_t s);
+
 // Motion-JPEG launchers (mjpeg.hip); entry points and argument checks in core.cpp
 int64_t cc_mjpeg_segment_bytes(int32_t W);
 int cc_mjpeg_transform(const uint8_t* frames, const int32_t* tab, int16_t* coef, int32_t N, int32_t H, int32_t W, int32_t quality, hipStream_t s);

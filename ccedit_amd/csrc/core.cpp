@@ -532,6 +532,34 @@ extern "C" int ccedit_noise_warp(const float* raw, const int32_t* src, float* ou
     return cc_noise_warp(raw, src, out, B, C, N, (hipStream_t)stream);
 }
 
+// ---- quality report (kernels and launchers: quality.hip).  Everything the host can see is checked here, before any HIP call; the pair
+// list and the per-pixel vectors are device data, held in range by the kernel (frame numbers clamped into the clip, positions into
+// the frame).  Both functions zero their accumulators themselves, on the stream.
+extern "C" int ccedit_quality_pair(const void* a, const void* b, const void* mask, void* acc, int64_t N, int32_t H, int32_t W, void* stream) {
+    CC_CHECK_ARG(a && b && acc, "ccedit_quality_pair: null pointer (mask alone may be null: every pixel is kept)");
+    CC_CHECK_ARG(N >= 1 && N <= 65535, "ccedit_quality_pair: N=%lld frames (1 ... 65535)", (long long)N);
+    CC_CHECK_ARG(H >= 8 && W >= 8 && H % 4 == 0 && W % 4 == 0 && H <= 16384 && W <= 16384,
+                 "ccedit_quality_pair: frames of %dx%d (H and W multiples of 4, 8 ... 16384: 8 x 8 windows at stride 4)", H, W);
+    CC_CHECK_ARG(N * H * W * 3 < kPixelMax * 4, "ccedit_quality_pair: more than 2^33 bytes in one call (N=%lld %dx%d)", (long long)N, H, W);
+    CC_CHECK_ARG((((uintptr_t)a | (uintptr_t)b | (uintptr_t)mask) & 3) == 0 && ((uintptr_t)acc & 7) == 0,
+                 "ccedit_quality_pair: a, b and mask must be 4-byte, acc 8-byte aligned");
+    return cc_quality_pair((const uint8_t*)a, (const uint8_t*)b, (const uint8_t*)mask, (uint64_t*)acc, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int ccedit_quality_warp(const void* x, const void* y, const void* vsel, const int32_t* pairs, const void* mask, void* acc, int32_t P,
+                                   int32_t F, int32_t H, int32_t W, int32_t limit, int32_t sel, void* stream) {
+    CC_CHECK_ARG(x && vsel && pairs && acc, "ccedit_quality_warp: null pointer (y and, with sel = 0, mask may be null)");
+    CC_CHECK_ARG(P >= 1 && P <= 32767, "ccedit_quality_warp: P=%d measurements (1 ... 32767: two pair rows each)", P);
+    if (int rc = prop_shape_ok("ccedit_quality_warp", 2 * P, F, H, W)) return rc;
+    CC_CHECK_ARG(limit >= 0, "ccedit_quality_warp: limit=%d (not negative)", limit);
+    CC_CHECK_ARG(sel >= 0 && sel <= 2, "ccedit_quality_warp: sel=%d (0: all pixels, 1: mask >= 128, 2: mask < 128)", sel);
+    CC_CHECK_ARG(sel == 0 || mask, "ccedit_quality_warp: sel=%d chooses pixels by the mask: give one", sel);
+    CC_CHECK_ARG(((uintptr_t)vsel & 15) == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)mask) & 3) == 0 && ((uintptr_t)acc & 7) == 0,
+                 "ccedit_quality_warp: vsel must be 16-byte, x, y and mask 4-byte, acc 8-byte aligned");
+    return cc_quality_warp((const uint8_t*)x, (const uint8_t*)y, (const uint32_t*)vsel, pairs, (const uint8_t*)mask, (uint64_t*)acc, P, F, H, W,
+                           limit, sel, (hipStream_t)stream);
+}
+
 // ---- Motion-JPEG (kernels and launchers: mjpeg.hip).  Everything the host can see is checked here, before any HIP call; the device
 // tables (constants, segment lengths and offsets) are held in range by the kernels themselves.
 static int mjpeg_shape_ok(const char* fn, int32_t N, int32_t H, int32_t W) {

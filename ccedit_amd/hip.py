@@ -197,6 +197,10 @@ _SIGS = {
                                            C.c_void_p]),
     "ccedit_noisewarp_check": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "ccedit_noise_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
+    # quality report (csrc/quality.hip): added within ABI 12, nothing existing changed
+    "ccedit_quality_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ccedit_quality_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     # Motion-JPEG output (csrc/mjpeg.hip): added within ABI 12, nothing existing changed
     "ccedit_mjpeg_segment_bytes": (C.c_int64, [C.c_int32]),
     "ccedit_mjpeg_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

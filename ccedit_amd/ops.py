@@ -1472,6 +1472,67 @@ def noise_warp(raw: torch.Tensor, src: torch.Tensor, out: Optional[torch.Tensor]
 
 
 # ------------------------------------------------------------------------------------------
+# Quality report (csrc/quality.hip; constants, what is derived from the integers and the clip's loop: ccedit_amd/quality.py)
+# ------------------------------------------------------------------------------------------
+def quality_pair(a: torch.Tensor, b: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a, b: uint8 frames (N, H, W, 3); mask: uint8 (N, H, W) or None — a pixel is kept where there is no mask or its byte is < 128
+    -> int64 (N, 8) on the device, the accumulators' 64 bits as they are: per frame the squared error of R, G, B over the kept pixels,
+    their number, the sum of the SSIM quotient q (scaled by 2^32, signed) over the 8 x 8 windows at stride 4 that are kept whole, the
+    number of those windows, and the luma sums of a and of b over the kept pixels."""
+    _chk_u8(a, "quality_pair: a", 4)
+    _chk_u8(b, "quality_pair: b", 4)
+    n, h, w, c = a.shape
+    if c != 3 or tuple(b.shape) != tuple(a.shape) or b.device != a.device:
+        raise ValueError(f"quality_pair: two clips of RGB frames (N, H, W, 3) on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if n < 1 or h < 8 or w < 8 or h % 4 or w % 4:
+        raise ValueError(f"quality_pair: {n} frames of {h}x{w}: at least one frame, H and W multiples of 4 and at least 8 (8 x 8 windows at stride 4)")
+    if mask is not None:
+        _chk_u8(mask, "quality_pair: mask", 3)
+        if tuple(mask.shape) != (n, h, w) or mask.device != a.device:
+            raise ValueError(f"quality_pair: mask {tuple(mask.shape)} for {n} frames of {h}x{w}")
+    acc = torch.empty((n, 8), dtype=torch.int64, device=a.device)
+    _launch_mem("quality_pair", float(n * h * w * (6 + (mask is not None))), lambda: hip.check(hip.lib().ccedit_quality_pair(
+        a.data_ptr(), b.data_ptr(), _ptr(mask), acc.data_ptr(), n, h, w, _stream()), "ccedit_quality_pair"), (n, h, w))
+    return acc
+
+
+def quality_warp(x: torch.Tensor, vsel: torch.Tensor, pairs: torch.Tensor, limit: int, y: Optional[torch.Tensor] = None,
+                 mask: Optional[torch.Tensor] = None, sel: int = 0) -> torch.Tensor:
+    """x: uint8 frames (F, H, W, 3), the sequence measured; y: a second one of that shape measured along the same vectors, or None;
+    pairs: int32 (2 P, 4), rows 2 j = (f, g, ., .) and 2 j + 1 = (g, f, ., .); vsel: int16 (2 P, H, W, 2), masktrack_select's vectors of those
+    rows; mask: uint8 (F, H, W) or None; sel: 0 all pixels, 1 those of frame f with mask >= 128, 2 those with mask < 128.
+    -> int64 (P, 4) on the device: the squared error of x and of y (0 without y) over the valid pixels and the three channels, the valid
+    pixels — q = p + v(p) lies in frame g and |v(p) + r(q)|_1 <= limit — and the selected pixels."""
+    _chk_u8(x, "quality_warp: x", 4)
+    f, h, w, c = x.shape
+    if c != 3:
+        raise ValueError(f"quality_warp: RGB frames (F, H, W, 3), got {tuple(x.shape)}")
+    if y is not None:
+        _chk_u8(y, "quality_warp: y", 4)
+        if tuple(y.shape) != tuple(x.shape) or y.device != x.device:
+            raise ValueError(f"quality_warp: y {tuple(y.shape)} shares x's vectors: the shape of x {tuple(x.shape)}, on its device")
+    if pairs.dim() != 2 or pairs.shape[0] < 2 or pairs.shape[0] % 2:
+        raise ValueError(f"quality_warp: pairs (2 P, 4), two rows per measurement, got {tuple(pairs.shape)}")
+    p2 = pairs.shape[0]
+    _chk_i32(pairs, "quality_warp: pairs", (p2, 4))
+    _chk_i16(vsel, "quality_warp: vsel", (p2, h, w, 2))
+    if int(sel) not in (0, 1, 2):
+        raise ValueError(f"quality_warp: sel={sel} (0: all pixels, 1: mask >= 128, 2: mask < 128)")
+    if int(limit) < 0:
+        raise ValueError(f"quality_warp: limit={limit} (not negative)")
+    if mask is not None:
+        _chk_u8(mask, "quality_warp: mask", 3)
+        if tuple(mask.shape) != (f, h, w) or mask.device != x.device:
+            raise ValueError(f"quality_warp: mask {tuple(mask.shape)} for {f} frames of {h}x{w}")
+    acc = torch.empty((p2 // 2, 4), dtype=torch.int64, device=x.device)
+    nbytes = (p2 // 2) * h * w * (8 + 6 * (1 + (y is not None)) + (mask is not None))
+    _launch_mem("quality_warp", float(nbytes), lambda: hip.check(hip.lib().ccedit_quality_warp(
+        x.data_ptr(), _ptr(y), vsel.data_ptr(), pairs.data_ptr(), _ptr(mask), acc.data_ptr(), p2 // 2, f, h, w, int(limit), int(sel),
+        _stream()), "ccedit_quality_warp"), (p2 // 2, h, w))
+    return acc
+
+
+# ------------------------------------------------------------------------------------------
 # Motion-JPEG output (csrc/mjpeg.hip; constants, header, container and the frame loop: ccedit_amd/mjpeg.py)
 # ------------------------------------------------------------------------------------------
 def mjpeg_segment_bytes(w: int) -> int:

@@ -738,6 +738,36 @@ int ccedit_noisewarp_check(const int32_t* src, int64_t maps, int64_t N, void* fl
 int ccedit_noise_warp(const float* raw, const int32_t* src, float* out, int32_t B, int32_t C, int64_t N, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Quality report (added without an ABI bump: two new functions, CCEDIT_ABI_VERSION stays 12).  `--report_quality`: how faithful a
+ * result is to its source (squared error, SSIM) and how steady a clip is along the source's motion (warp error); ccedit_amd/quality.py:
+ * constants, compare, temporal, report.  Kernels: csrc/quality.hip.  Everything is integer arithmetic with 64-bit accumulators and
+ * equals tests/_quality_numpy.py bit for bit; PSNR, SSIM and the means are formed from the exact integers on the host.  Frames are
+ * uint8 [frames][H][W][3], masks uint8 [frames][H][W] (>= 128 = edited).  All pointers are device pointers; both functions zero acc
+ * themselves, ordered on the stream.
+ *
+ * ccedit_quality_pair: a, b [N][H][W][3], mask [N][H][W] or null; a pixel is KEPT where mask is null or its byte is < 128.  H and W
+ *   multiples of 4, 8 ... 16384; a, b, mask 4-byte, acc 8-byte aligned.  acc uint64 [N][8], per frame: [0 .. 2] sum of (a - b)^2 over the
+ *   kept pixels for R, G, B; [3] the kept pixels; [4] sum of q over the counted windows (int64, two's complement); [5] the counted
+ *   windows; [6], [7] sum of the luma (77 R + 150 G + 29 B + 128) >> 8 of a and of b over the kept pixels.  Windows: 8 x 8 at stride 4,
+ *   at (4 i, 4 j) with 4 i + 8 <= H and 4 j + 8 <= W; a window counts iff all its 64 pixels are kept.  Per window over the lumas:
+ *   s1 = sum a, s2 = sum b, saa, sbb, sab; va = 64 saa - s1^2, vb = 64 sbb - s2^2, cov = 64 sab - s1 s2; c1 = 26634, c2 = 239708
+ *   ((0.01 * 255)^2 and (0.03 * 255)^2 times 4096); Nw = (2 s1 s2 + c1)(2 cov + c2), Dw = (s1^2 + s2^2 + c1)(va + vb + c2), both below
+ *   2^63, |Nw| <= Dw; q = sign(Nw) floor(|Nw| 2^32 / Dw) exactly (an integer part of 0 or 1 and 32 shift-subtract steps; no
+ *   floating-point divide).  Identical frames give q = 2^32 in every window.
+ * ccedit_quality_warp: x [F][H][W][3], the sequence measured; y: a second one of the same shape that shares the vectors, or null;
+ *   pairs int32 [2 P][4]: row 2 j = (f, g, ., .), row 2 j + 1 = (g, f, ., .) (ccedit_amd/masktrack.py pair_rows; f and g of row 2 j are
+ *   read and clamped into 0 ... F - 1); vsel int16 [2 P][H][W][2] as ccedit_masktrack_select writes it for those rows (16-byte aligned);
+ *   mask [F][H][W] or null; sel: 0 all pixels, 1 mask_f(p) >= 128, 2 mask_f(p) < 128 (sel != 0 with a null mask: status -1).  H and W as
+ *   in "Propagation".  Per selected pixel p of frame f: v = vsel[2 j](p), q0 = p + v, inside = q0 lies in the frame, q = clamp(q0),
+ *   r = vsel[2 j + 1](q), valid = inside and |v_y + r_y| + |v_x + r_x| <= limit.  acc uint64 [P][4], per measurement: sum over the valid
+ *   pixels and the channels of (x_f(p) - x_g(q))^2, the same of y (0 where y is null), the valid pixels, the selected pixels.  Every
+ *   access stays in range for any int16 content of vsel and any int32 content of pairs.
+ */
+int ccedit_quality_pair(const void* a, const void* b, const void* mask, void* acc, int64_t N, int32_t H, int32_t W, void* stream);
+int ccedit_quality_warp(const void* x, const void* y, const void* vsel, const int32_t* pairs, const void* mask, void* acc, int32_t P, int32_t F,
+                        int32_t H, int32_t W, int32_t limit, int32_t sel, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-JPEG (added without an ABI bump: five new functions, CCEDIT_ABI_VERSION stays 12).  `--save_type mjpeg`: uint8 frames
  * [N][H][W][3] on the device (what ccedit_frames_to_u8 writes) -> one baseline JPEG per frame (ITU-T T.81: sequential DCT, 8 bit,
  * YCbCr 4:2:0, MCU 16 x 16, restart interval = one MCU row = one SEGMENT), ccedit_amd/mjpeg.py: constants, header, container.

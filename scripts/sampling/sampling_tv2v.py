@@ -44,6 +44,15 @@ every latent cell of every keyframe inherits (the matcher of --propagate, every 
 every draw is gathered through it (ccedit_amd/noisewarp.py, csrc/noisewarp.hip); `--noise_warp_rho R` (0 ... 1, default 1) mixes
 sqrt(1 - R^2) of a fresh draw in; log_info.json gains `noise_warp`.  Needs a video and --H, --W multiples of 64; refused with a
 reference image and with WORLD_SIZE > 1.  Image quality is not claimed.
+`--report_quality` (job mode) measures every clip after it is saved, on the GPU and on the uint8 frames original/ and result/ hold
+(ccedit_amd/quality.py, csrc/quality.hip): fidelity of the result to the source keyframes — squared error per channel, PSNR, SSIM on
+8 x 8 luma windows; with --inpainting_mode over the pixels the clip's mask keeps — and temporal consistency: the warp error of the result
+along the SOURCE's motion between neighbouring keyframes beside the source's own, over the pixels the previous frame shows, with the share
+of pixels the motion estimate could follow (keyframes lie original_fps / target_fps source frames apart: that share says how far the
+matcher reached).  With --propagate the same over every source frame against result_full/ (`full_rate`).  The report is written to
+<save_path>/<basemodel>/quality/<clip number>.json and log_info.json gains `quality`; sizes off the 64 grid and single frames get
+`"temporal": null` with the reason.  Refused with WORLD_SIZE > 1.  These are measures of fidelity and steadiness, not of how well the
+prompt was followed; on synthetic weights they measure the pipeline, not a model.
 `--window_frames T` (with `--window_overlap O`, default T // 2) lifts the limit of one window of keyframes: with `--num_keyframes N` > T the
 clip is covered by overlapping windows of T frames, each evaluated by the unchanged network at every sampler evaluation and fused into
 one denoised latent of N frames (ccedit_amd/windows.py, csrc/window.hip); everything else — inpainting, SDEdit, the prior mix,
@@ -270,6 +279,13 @@ def add_common_args(p: argparse.ArgumentParser) -> None:
     p.add_argument("--noise_warp_rho", type=float, default=1.0, action=_StoreGiven,
                    help="with --noise_warp: the correlation of a keyframe's noise with the noise it inherits, 0 ... 1 (default 1: carried "
                         "exactly; below 1 a second, independent draw is mixed in: rho * carried + sqrt(1 - rho^2) * fresh)")
+    p.add_argument("--report_quality", action="store_true",
+                   help="(not in the reference script) after a clip is saved, measure it on the GPU (ccedit_amd/quality.py, csrc/quality.hip): "
+                        "fidelity of the result to the source keyframes (PSNR, SSIM; with --inpainting_mode over the pixels the mask keeps) "
+                        "and the warp error of result and source along the source's motion, with the share of pixels the motion estimate "
+                        "could follow; with --propagate also over every source frame against result_full/ (`full_rate`).  Written to "
+                        "<save_path>/quality/<clip number>.json; log_info.json gains `quality`.  Job mode only.  Measures of fidelity and "
+                        "steadiness, not of how well the prompt was followed")
     p.add_argument("--disable_check_repeat", action="store_true")
     p.add_argument("--gpu_io", action="store_true",
                    help="pixel I/O on the GPU (ccedit_amd/csrc/pixel.hip): frame / depth resize, depth hint normalisation and the uint8 "
@@ -332,6 +348,7 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
     check_mask_auto(args)                    # (--mask_auto and its kin: ValueError; nothing is imported or checked without the flag)
     check_prompt_schedule(args)              # (--prompt_at: ValueError / NotImplementedError; nothing is imported or checked without the flag)
     check_noise_warp(args)                   # (--noise_warp and its rho: ValueError; nothing is imported without the flag)
+    check_report_quality(args)               # (--report_quality: ValueError; nothing is imported without the flag)
 
 
 def windowing(args) -> bool:
@@ -437,11 +454,13 @@ def video_writer(args):
     return writer, {k: getattr(args, k) for k in (writer.options if writer else ())}
 
 
-def propagate_chunk(args, cvideos, samples, dev, save_path):
+def propagate_chunk(args, cvideos, samples, dev, save_path, keep=None):
     """--propagate for one chunk: per clip all source frames on the device, the edited keyframes as the uint8 frames result/ holds
     (frames_to_u8 without rounding of the decoder output), propagate_clip, <save_path>/result_full/gif/animation-XXXX.gif (--save_type
     mjpeg: result_full/mjpeg/animation-XXXX.avi, --save_type png: result_full/png/animation-XXXX.png, encoded from the frames where they
-    are, on the device; so is the gif with --gif_encoder device) at --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written."""
+    are, on the device; so is the gif with --gif_encoder device) at --original_fps.  With --mask_composite every in-between frame keeps the source outside ITS OWN mask.  -> the paths written.
+    `keep` (a list, --report_quality): per clip (the source frames from the first to the last keyframe, the frames written, their masks or None)
+    is appended to it."""
     from ccedit_amd import ops
     from ccedit_amd.propagate import propagate_clip
     from scripts.sampling import util
@@ -457,6 +476,9 @@ def propagate_chunk(args, cvideos, samples, dev, save_path):
             masks = all_frame_masks(args, v, n_all, dev)
         idx = keyframe_indices(n_all, args.original_fps, args.target_fps, args.num_keyframes)
         full = propagate_clip(source, idx, edited[b], masks=masks)
+        if keep is not None:
+            first = int(idx[0])
+            keep.append((source[first:first + full.shape[0]], full, None if masks is None else masks[first:first + full.shape[0]]))
         frames = full.contiguous() if writer.on_device else full.cpu().numpy()      # (a device writer encodes the frames where they are)
         save = getattr(util, writer.saver)                                         # (found on the module now: save_gif_u8(path, host frames, fps) for Pillow's gif)
         paths.append(save(os.path.join(save_path, "result_full"), frames, args.original_fps, *options.values()))
@@ -1185,6 +1207,57 @@ def noise_maps(args, video_paths, dev):
     return torch.stack([b[0] for b in built], dim=0).contiguous(), [b[1] for b in built]
 
 
+# ------------------------------------------------------------------------------------------
+# Quality report: --report_quality (ccedit_amd/quality.py)
+# ------------------------------------------------------------------------------------------
+def report_quality_on(args) -> bool:
+    """The report is made when --report_quality was given; otherwise nothing of it is imported or launched."""
+    return bool(getattr(args, "report_quality", False))
+
+
+def check_report_quality(args) -> None:
+    """Before any GPU work, from the flags alone: what --report_quality needs (ValueError naming the flags, with what to do)."""
+    if not report_quality_on(args):
+        return
+    if not job_mode(args):
+        raise ValueError("--report_quality measures a saved clip against its source video: give --prompt with --video_path (or "
+                         "--prompt_listpath / --videos_directory / --json_path)")
+    if _dist_rank_world()[1] > 1:
+        raise ValueError("--report_quality is not available in the multi-GPU modes (WORLD_SIZE > 1): a clip's report is made on the GPU "
+                         "that holds its frames — run it with one process")
+    if args.H < 8 or args.W < 8 or args.H % 4 or args.W % 4:
+        raise ValueError(f"--report_quality with --H {args.H} --W {args.W}: SSIM takes 8 x 8 windows at stride 4 — frame sides must be "
+                         "multiples of 4 and at least 8; choose such a size, or drop --report_quality")
+
+
+def quality_chunk(args, keyframes, samples, mask_px, keyframes_paths, save_path, full=()):
+    """--report_quality for one chunk: per clip the source keyframes and the result as the uint8 frames original/ and result/ hold (one
+    frames_to_u8 call for both, propagate_chunk's arguments), ccedit_amd.quality.report — over the pixels the clip's mask keeps with
+    --inpainting_mode — and, with --propagate, the same over every source frame against result_full/ (`full`: what propagate_chunk kept).
+    -> per clip the summary log_info.json keeps; the whole report goes to <save_path>/quality/<clip number>.json."""
+    import json
+    import re
+    from ccedit_amd import ops, quality
+    n = samples.shape[0]
+    u8 = ops.frames_to_u8(torch.cat([keyframes.float(), samples.float()], dim=0).contiguous(), rounding=False, unit_range=False)
+    out = []
+    for b in range(n):
+        rep = quality.report(u8[b], u8[n + b], None if mask_px is None else mask_px[b] >= 128)
+        if b < len(full):
+            source, result, masks = full[b]
+            rep["full_rate"] = quality.report(source.contiguous(), result.contiguous(), masks)
+        number = re.search(r"(\d+)\.\w+$", os.path.basename(keyframes_paths[b])).group(1)
+        os.makedirs(os.path.join(save_path, "quality"), exist_ok=True)
+        path = os.path.join(save_path, "quality", f"{number}.json")
+        with open(path, "w") as f:
+            json.dump(rep, f, indent=4)
+        entry = dict(quality.summary(rep), path=path)
+        if "full_rate" in rep:
+            entry["full_rate"] = quality.summary(rep["full_rate"])
+        out.append(entry)
+    return out
+
+
 def make_closure(args, model, c, ref=None, regions=None):
     """The closure `denoiser(input, sigma, cond)` every sampler evaluation of a chunk goes through — plain, windowed (--window_frames),
     tiled (--tile_h / --tile_w), region prompts outermost — and the engine whose first stage works in groups that fit it.  Used by
@@ -1460,6 +1533,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
     check_mask_auto(args, with_ref)
     check_prompt_schedule(args, with_ref)
     check_noise_warp(args, with_ref)
+    check_report_quality(args)
     from ccedit_amd.parallel import shard_clips
     from scripts.sampling.util import chunk, load_img, load_video_keyframes, model_load_ckpt, perform_save_locally_video
     prompts, video_paths, video_save_paths, ref_paths = expand_jobs(args, with_ref)
@@ -1600,9 +1674,13 @@ def run_jobs(args, with_ref: bool = False) -> None:
                     m01 = ((mask_px.float() + 0.5) / 255.0)[:, None].expand(-1, 3, -1, -1, -1).contiguous()
                 perform_save_locally_video(os.path.join(save_path, "mask"), m01 * 2.0 - 1.0 if io.get("signed") else m01, args.target_fps, args.save_type,
                                            save_grid=False, **io)
+            full_kept = [] if report_quality_on(args) else None
             if args.propagate:
                 log_info.setdefault("fullrate_paths", [])
-                log_info["fullrate_paths"] += propagate_chunk(args, cvideos, samples, dev, save_path)
+                log_info["fullrate_paths"] += propagate_chunk(args, cvideos, samples, dev, save_path, keep=full_kept)
+            if report_quality_on(args):                                   # measured on the frames just saved; no step code runs
+                log_info.setdefault("quality", [])
+                log_info["quality"] += quality_chunk(args, keyframes, samples, mask_px, keyframes_paths, save_path, full_kept)
             print("Saved samples to {}. Enjoy.".format(save_path))
             log_info["video_paths"] += cvideos
             log_info["keyframes_paths"] += keyframes_paths
