@@ -31,6 +31,20 @@ def _ceil(a, b):
     return (a + b - 1) // b * b
 
 
+BF16_ATTN_MAX_COLS = 8192      # ccedit_softmax_rows (csrc/elementwise.hip) holds a padded row of scores in registers: cols_pad <= 256 * 32
+
+
+def check_bf16_frame(lh: int, lw: int) -> None:
+    """The bf16 first stage's mid-block attention (AttnBlock.run) pads a frame's L = lh lw score columns to a multiple of 64 for
+    ccedit_softmax_rows, which refuses more than BF16_ATTN_MAX_COLS of them from inside the per-frame loop — at decode, i.e. after
+    the whole sampling loop.  Refused here instead (ValueError), before any launch; the fp32 first stage has no such limit."""
+    L = int(lh) * int(lw)
+    if _ceil(L, 64) > BF16_ATTN_MAX_COLS:
+        raise ValueError(f"a frame of {8 * int(lh)}x{8 * int(lw)} px has {L} latent pixels: the bf16 first stage's mid-block attention takes at "
+                         f"most {BF16_ATTN_MAX_COLS} per frame — run the first stage in fp32 (CCEDIT_POLICY=vae_fp32=1, or "
+                         f"`disable_first_stage_autocast: True` in the yaml), or use a smaller frame")
+
+
 class ResnetBlock(nn.Module):
     def __init__(self, in_channels: int, out_channels: int):
         super().__init__()
@@ -266,6 +280,8 @@ class AutoencoderKLInferenceWrapper(AutoencoderKL):
         b, c, t, h, w = x5.shape
         if h % 8 or w % 8:
             raise ValueError(f"frame size {h}x{w} must be a multiple of 8")
+        if self.precision == "bf16":
+            check_bf16_frame(h // 8, w // 8)
         if self.precision == "fp32":
             mom = vae_f32.encode_moments(self, x5.float())
             zc = self.quant_conv.cout // 2
@@ -284,6 +300,8 @@ class AutoencoderKLInferenceWrapper(AutoencoderKL):
         is_video = z.dim() == 5
         z5 = z if is_video else z[:, :, None]
         b, c, t, h, w = z5.shape
+        if self.precision == "bf16":
+            check_bf16_frame(h, w)
         if self.precision == "fp32":
             dec = vae_f32.decode_frames(self, z5.float())
         else:

@@ -427,6 +427,31 @@ def check_tiling(args, with_ref: bool = False) -> None:
             tiles.check_supported(config=f.read())
 
 
+def first_stage_precision(args) -> str:
+    """"fp32" or "bf16", as the engine will set it (ccedit_amd/engine.py): policy vae_fp32 = 1 / 0 decide alone, 2 (the default) follows
+    the yaml's `disable_first_stage_autocast`."""
+    from ccedit_amd import policy
+    v = policy.get("vae_fp32")
+    if v != 2:
+        return "fp32" if v == 1 else "bf16"
+    flag = False
+    if args.config_path and os.path.exists(args.config_path):
+        from ccedit_amd.config import load_config
+        flag = bool(load_config(args.config_path).model.params.get("disable_first_stage_autocast", False))
+    return "fp32" if flag else "bf16"
+
+
+def check_first_stage(args) -> None:
+    """Before any GPU work, with tiles or without (the first stage runs on whole frames either way; check_tiling's tiles.check_frame_cap
+    bounds its score matrix in both precisions): the bf16 first stage takes fewer latent pixels per frame (vae.check_bf16_frame) and
+    would otherwise say so only at decode, after the sampling loop."""
+    if args.H % 8 or args.W % 8:
+        return                                                                       # (refused where the frames are encoded / decoded)
+    from ccedit_amd.vae import check_bf16_frame
+    if first_stage_precision(args) == "bf16":
+        check_bf16_frame(args.H // 8, args.W // 8)
+
+
 def check_propagate(args, video_paths) -> None:
     """Before any GPU work: --propagate needs strictly increasing keyframe indices on every clip (ValueError from ccedit_amd.propagate.plan —
     keyframe_indices' linspace fallback on a video that is too short repeats frames).  Clips that cannot be counted here (no decoder)
@@ -1529,6 +1554,7 @@ def run_jobs(args, with_ref: bool = False) -> None:
     import json
     check_windowing(args, with_ref)
     check_tiling(args, with_ref)
+    check_first_stage(args)
     check_region_options(args, with_ref)
     check_mask_auto(args, with_ref)
     check_prompt_schedule(args, with_ref)
@@ -1729,6 +1755,7 @@ def main():
         return run_jobs(args)
     check_windowing(args)
     check_tiling(args)
+    check_first_stage(args)
     check_region_jobs(args, 1)
     check_noise_warp(args)
     from scripts.sampling.util import ResumeLog, save_frames

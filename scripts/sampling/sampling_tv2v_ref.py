@@ -21,7 +21,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from scripts.sampling.sampling_tv2v import (add_common_args, build_model, check_args, check_mask_auto, check_noise_warp, check_prompt_schedule, check_region_options, check_tiling, check_windowing, cond_text, conditioning_tensors, job_mode, run_jobs,  # noqa: E402
+from scripts.sampling.sampling_tv2v import (add_common_args, build_model, check_args, check_first_stage, check_mask_auto, check_noise_warp, check_prompt_schedule, check_region_options, check_tiling, check_windowing, cond_text, conditioning_tensors, job_mode, run_jobs,  # noqa: E402
                                             sample_one, save_result, single_clip_masks, text_inputs)
 
 
@@ -48,6 +48,7 @@ def main():
     torch.set_grad_enabled(False)
     check_windowing(args, with_ref=True)      # --window_frames: refused here, one reference image belongs to one centre frame
     check_tiling(args, with_ref=True)         # --tile_h / --tile_w: refused here, the reference latent belongs to the whole frame
+    check_first_stage(args)                   # the first stage's frame limits, by its precision
     check_region_options(args, with_ref=True)     # --region_prompt / --region_mask: refused here, the reference conditions the whole frame
     check_mask_auto(args, with_ref=True)          # --mask_auto: refused here, the reference conditions the whole frame
     check_prompt_schedule(args, with_ref=True)    # --prompt_at: refused here, the reference belongs to one centre frame
